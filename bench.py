@@ -1,12 +1,22 @@
 #!/usr/bin/env python3
 """Headline benchmark: Marin-path modular squaring x <- x^2 mod 2^p-1 at p ~ 136M on MI355X.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one square_mul on every rank's own exponent (independent residues, one exponent per GPU,
 no data-path collective: SURVEY.md 8e).  The residue vector is resident in HBM before the timed
-region.  Rank 0 prints ONE JSON line.  Extra objects:
+region.  Before --warmup, untimed squarings run until the GPU clock has ramped (preheat: a cold box runs the
+first tens of milliseconds slower; --steps/--warmup keep their meaning).  The residue is set to the same
+seeded digits again after the preheat and the warm-up, so that the K timed
+steps start from an input that is identical from run to run.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, preheats, warms up, times the K steps and prints the line (metric, value, unit,
+ms_per_step, dtype, ...).  --dump-outputs DIR: rank 0 then writes what the timed steps computed, the
+residue after the last one as its canonical little-endian 32-bit words (what get_mpz / get_words hands a
+caller), to DIR/residue_words.npy in float64 (exact: every word is below 2^32).  --full adds the objects
+below, each from measurements of its own after the timed steps:
+  ll_ms_per_step, gerbicz_check -- the LL form x^2 - 2 of the same loop; a device-side compare + res64
   roofline     -- dominant kernel: algorithmic bytes per launch (16*n: one read+write sweep of the
                   8-byte residue vector, SURVEY.md 8d: 48*n per squaring = 3 sweeps) / its average
                   duration from HIP events on the engine's stream (one event between kernels, minus the
@@ -17,8 +27,6 @@ region.  Rank 0 prints ONE JSON line.  Extra objects:
                   predicted_us = waves per SIMD x cycles / the shader clock READ DURING THIS RUN (hwmon sclk sampled while a
                   batch of squarings runs), frac = predicted / measured per kernel and for the squaring; without a readable
                   clock the time prediction is left out (cycles only)
-  preheat      -- untimed squarings before --warmup until the GPU clock has ramped (a cold box runs the
-                  first tens of milliseconds slower; --steps/--warmup keep their meaning)
   cpu_baseline -- the CPU oracle (a port of the reference's algorithm; the reference has no CPU
                   implementation of this path) timed on this box's host cores, N=1 only
 """
@@ -140,7 +148,8 @@ def bench_crt(args):
     j = np.arange(n + 1, dtype=np.uint64)
     ceil = (j * np.uint64(p) + np.uint64(n - 1)) // np.uint64(n)
     width = (ceil[1:] - ceil[:-1]).astype(np.uint64)
-    eng.set_digits(0, np.random.default_rng(1000).integers(0, 1 << 62, n, dtype=np.uint64) & ((np.uint64(1) << width) - np.uint64(1)))
+    digits = np.random.default_rng(1000).integers(0, 1 << 62, n, dtype=np.uint64) & ((np.uint64(1) << width) - np.uint64(1))
+    eng.set_digits(0, digits)
     t_start = time.perf_counter()
     while args.preheat_seconds > 0 and time.perf_counter() - t_start < args.preheat_seconds:
         for _ in range(50):
@@ -148,34 +157,45 @@ def bench_crt(args):
         eng.sync()
     for _ in range(max(1, args.warmup)):
         eng.square_mul(0, 1)
+    eng.set_digits(0, digits)   # the timed steps start from the seeded input, whatever the preheat did
     eng.sync(); torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         eng.square_mul(0, 1)
     eng.sync(); torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    _, kern = eng.time_square_mul(0, min(args.steps, 32))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng.words(0))
     ms = 1e3 * elapsed / args.steps
-    dom = max(kern, key=kern.get)
     bytes_iter = eng.algorithmic_bytes()
-    traffic = None
-    try:   # HBM bytes per squaring from the committed PMC passes of this command (tools/profile.sh, tools/make_traffic_json.py)
-        tj = json.load(open(os.path.join(ROOT, "profiles", "traffic_crt_latest.json")))
-        if tj.get("plan") == eng.describe():
-            traffic = tj.get("per_squaring")
-    except Exception:
-        traffic = None
     out = {"metric": "squaring throughput at p=%d over GF(M61^2) x GF(M31^2), PFA radix-%d axis" % (p, args.odd), "value": round(args.steps / elapsed, 3),
            "unit": "iter/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 5), "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "u64 + u32 (GF(M61^2) x GF(M31^2))", "data": "synthetic",
-           "config": {"workload": "square_mul x<-x^2 mod 2^p-1, p=%d, n=%d words (odd radix %d)" % (p, n, args.odd), "plan": eng.describe()},
-           "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(bytes_iter / (ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(bytes_iter / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic,
-                        "traffic_source": "profiles/traffic_crt_latest.json (rocprofv3 --pmc passes of this command)" if traffic else None,
-                        "algorithmic_bytes_per_iteration": bytes_iter, "stage_ms": {k: round(v, 5) for k, v in kern.items()},
-                        "note": "whole iteration; stage slots: front, forward columns, rows + pointwise + inverse rows, inverse columns, back + carry (one kernel), range edges; DESIGN.md section 7 N1"}}
+           "config": {"workload": "square_mul x<-x^2 mod 2^p-1, p=%d, n=%d words (odd radix %d)" % (p, n, args.odd), "plan": eng.describe()}}
+    if args.full:
+        _, kern = eng.time_square_mul(0, min(args.steps, 32))
+        dom = max(kern, key=kern.get)
+        traffic = None
+        try:   # HBM bytes per squaring from the committed PMC passes of this command (tools/profile.sh, tools/make_traffic_json.py)
+            tj = json.load(open(os.path.join(ROOT, "profiles", "traffic_crt_latest.json")))
+            if tj.get("plan") == eng.describe():
+                traffic = tj.get("per_squaring")
+        except Exception:
+            traffic = None
+        out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(bytes_iter / (ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(bytes_iter / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic,
+                           "traffic_source": "profiles/traffic_crt_latest.json (rocprofv3 --pmc passes of this command)" if traffic else None,
+                           "algorithmic_bytes_per_iteration": bytes_iter, "stage_ms": {k: round(v, 5) for k, v in kern.items()},
+                           "note": "whole iteration; stage slots: front, forward columns, rows + pointwise + inverse rows, inverse columns, back + carry (one kernel), range edges; DESIGN.md section 7 N1"}
     print(json.dumps(out))
     eng.close()
+
+
+def dump_outputs(out_dir, words):
+    """the residue after the last timed step, canonical 32-bit words, as float64 (exact) -> out_dir/residue_words.npy"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "residue_words.npy"), np.asarray(words, dtype=np.float64))
 
 
 def main():
@@ -185,7 +205,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--exponent", type=int, default=0, help="override the exponent (testing)")
     ap.add_argument("--plan", type=str, default=None, help="plan override, e.g. m2=4096,c=4")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: LL form, Gerbicz check, per-kernel roofline with the VALU "
+                         "model and shader clock, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the residue after the last timed step (rank 0) to DIR/residue_words.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--field", default="goldilocks", choices=["goldilocks", "crt"],
                     help="crt: the GF(M61^2) x GF(M31^2) engine with the prime-factor radix-3/9 axis (SURVEY.md 8f N1; one GPU, not the headline line)")
     ap.add_argument("--odd", type=int, default=9, help="--field crt: radix of the odd axis (1, 3, 9)")
@@ -237,7 +262,8 @@ def main():
 
     p = args.exponent or EXPONENTS[rank % len(EXPONENTS)]
     eng = Engine(p, 2, device=local_rank, plan=args.plan)
-    eng.set_digits(0, seeded_digits(p, eng.n, 1000 + rank))
+    digits = seeded_digits(p, eng.n, 1000 + rank)
+    eng.set_digits(0, digits)
 
     def barrier():
         if dist is not None:
@@ -256,6 +282,7 @@ def main():
                 break
             last = ms
     eng.time_square_mul(0, max(1, args.warmup))
+    eng.set_digits(0, digits)   # the timed steps start from the seeded input, whatever the preheat did
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
@@ -265,6 +292,8 @@ def main():
     barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng.words(0))
 
     status = torch.tensor([1, 0, args.steps], dtype=torch.int64, device=red_dev)   # ok, gerbicz errors, iterations
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -277,22 +306,48 @@ def main():
         per_rank = gathered
     elapsed = float(tmax.item())
 
-    # BASELINE configs[2] is the LL form of the same exponent (x^2 - 2): a short untimed-region measurement
-    # of that variant, reported beside the metric (the subtraction rides on the next front sweep)
-    ll_iters = min(args.steps, 500)
-    ll_ms, _ = eng.time_square_mul(0, ll_iters, sub=2)
-    # second, instrumented pass of the same loop: per-kernel durations from event pairs on the engine stream
-    _, kern = eng.time_square_mul(0, min(args.steps, 64), per_kernel=True)
-    # a Gerbicz-style check at this size: device-side canonical form + compare, and res64
-    check = None
-    if rank == 0:
-        eng.copy(1, 0)
-        eng.is_equal(0, 1); eng.res64(0)   # allocate the scratch, warm the kernels
-        tc0 = time.perf_counter(); same = eng.is_equal(0, 1); tc1 = time.perf_counter(); eng.res64(0); tc2 = time.perf_counter()
-        check = {"is_equal_ms": round(1e3 * (tc1 - tc0), 3), "res64_ms": round(1e3 * (tc2 - tc1), 3), "equal": bool(same),
-                 "pcie_bytes_per_check": 16, "note": "strong carry, compare and res64 on the device (canon.hip)"}
+    if args.full:
+        # BASELINE configs[2] is the LL form of the same exponent (x^2 - 2): a short untimed-region measurement
+        # of that variant, reported beside the metric (the subtraction rides on the next front sweep)
+        ll_iters = min(args.steps, 500)
+        ll_ms, _ = eng.time_square_mul(0, ll_iters, sub=2)
+        # second, instrumented pass of the same loop: per-kernel durations from event pairs on the engine stream
+        _, kern = eng.time_square_mul(0, min(args.steps, 64), per_kernel=True)
+        # a Gerbicz-style check at this size: device-side canonical form + compare, and res64
+        check = None
+        if rank == 0:
+            eng.copy(1, 0)
+            eng.is_equal(0, 1); eng.res64(0)   # allocate the scratch, warm the kernels
+            tc0 = time.perf_counter(); same = eng.is_equal(0, 1); tc1 = time.perf_counter(); eng.res64(0); tc2 = time.perf_counter()
+            check = {"is_equal_ms": round(1e3 * (tc1 - tc0), 3), "res64_ms": round(1e3 * (tc2 - tc1), 3), "equal": bool(same),
+                     "pcie_bytes_per_check": 16, "note": "strong carry, compare and res64 on the device (canon.hip)"}
     if rank == 0:
         n = eng.n
+        ms_per_step = 1e3 * elapsed / args.steps
+        out = {
+            "metric": "PRP squaring throughput at p~136M (Marin IBDWT, one exponent per GPU)",
+            "value": round(world * args.steps / elapsed, 3),
+            "unit": "iter/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 5),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u64 (GF(2^64-2^32+1))",
+            "data": "synthetic",
+            "config": {"workload": "square_mul x<-x^2 mod 2^p-1, p=%d, n=%d words" % (p, n),
+                       "plan": __import__("prmers_amd").resolve_plan(p, args.plan),
+                       "exponents": EXPONENTS[:world] if not args.exponent else [p],
+                       "per_rank": per_rank,
+                       "status_reduction_backend": args.dist_backend if world > 1 else None,
+                       "parallelism": "replicas: one exponent per GPU, no data-path collective" +
+                                      (" [REHEARSAL: all ranks on one device]" if rehearsal else "")},
+            "event_ms_per_step": round(ev_ms / args.steps, 5),
+            "preheat_iters": preheat_iters, "preheat_ms": round(preheat_ms, 1),
+        }
+    if rank == 0 and args.full:
         event_overhead = kern.pop("event_overhead", 0.0)
         kern = {k: v for k, v in kern.items() if v >= 0}   # slots this path does not launch are reported as -1
         chain = {k: v for k, v in kern.items() if k != "k_sub_small"}
@@ -300,7 +355,6 @@ def main():
         dom_ms = chain[dom]
         sweep_bytes = 16 * n
         achieved = sweep_bytes / (dom_ms * 1e-3) / 1e9
-        ms_per_step = 1e3 * elapsed / args.steps
         traffic = None
         try:   # HBM bytes per launch of the dominant kernel from the committed PMC passes (tools/profile.sh)
             tj = json.load(open(os.path.join(ROOT, "profiles", "traffic_latest.json")))
@@ -333,29 +387,8 @@ def main():
                         "source": "profiles/valu_model_latest.json (tools/valu_model.py) + this run's kernel times and clock"}
         except Exception as exc:
             valu = {"error": "valu model unavailable: %s" % exc}
-        out = {
-            "metric": "PRP squaring throughput at p~136M (Marin IBDWT, one exponent per GPU)",
-            "value": round(world * args.steps / elapsed, 3),
-            "unit": "iter/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 5),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u64 (GF(2^64-2^32+1))",
-            "data": "synthetic",
-            "config": {"workload": "square_mul x<-x^2 mod 2^p-1, p=%d, n=%d words" % (p, n),
-                       "plan": __import__("prmers_amd").resolve_plan(p, args.plan),
-                       "exponents": EXPONENTS[:world] if not args.exponent else [p],
-                       "per_rank": per_rank,
-                       "status_reduction_backend": args.dist_backend if world > 1 else None,
-                       "parallelism": "replicas: one exponent per GPU, no data-path collective" +
-                                      (" [REHEARSAL: all ranks on one device]" if rehearsal else "")},
-            "event_ms_per_step": round(ev_ms / args.steps, 5),
+        out.update({
             "ll_ms_per_step": round(ll_ms / ll_iters, 5),
-            "preheat_iters": preheat_iters, "preheat_ms": round(preheat_ms, 1),
             "gerbicz_check": check,
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
@@ -369,9 +402,10 @@ def main():
                          "iteration": {"algorithmic_bytes": 48 * n,
                                        "achieved": round(48 * n / (ms_per_step * 1e-3) / 1e9, 1),
                                        "frac": round(48 * n / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(p)
+    if rank == 0:
         print(json.dumps(out))
     eng.close()
     if dist is not None:

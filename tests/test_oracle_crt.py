@@ -1,10 +1,9 @@
 """Pins of the second oracle (oracle/oracle_crt.c: GF(M61^2) x GF(M31^2) with a prime-factor radix-3 / radix-9 axis, SURVEY.md 8f
-N1): Python big integers, the reference's own CPU prototype run here (oracle/_ref/ref_mixed_crt, built in place from
-docs/mersenne2_mixed_crt_2d_half_fast/*.cpp), and the libgmp pins at BASELINE configs[3] with the PFA sizes."""
+N1): Python big integers, the output of the reference's own CPU prototype (oracle/_ref/ref_mixed_crt, built in place from
+docs/mersenne2_mixed_crt_2d_half_fast/*.cpp; recorded in tests/golden/reference_outputs.json), and the libgmp pins at BASELINE configs[3] with the PFA sizes."""
 import hashlib
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,7 +11,7 @@ import pytest
 import orc_crt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "oracle", "_ref", "ref_mixed_crt")
+REF_OUT = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_outputs.json")))["mixed_crt_ll"]
 
 
 @pytest.mark.parametrize("p,odd", [(127, 1), (521, 1), (521, 3), (1279, 3), (1279, 9), (2203, 9), (4423, 3), (9941, 9), (11213, 9), (11213, 3), (19937, 1)])
@@ -35,18 +34,17 @@ def test_squarings_match_python_integers(p, odd):
 
 @pytest.mark.parametrize("p,odd,prime", [(1279, 9, True), (2203, 3, True), (2281, 9, True), (2293, 9, False), (4253, 3, True), (4423, 9, True), (9941, 9, True), (9949, 3, False)])
 def test_lucas_lehmer_verdicts_match_the_reference_prototype_run_here(p, odd, prime):
-    """complete LL tests at forced radix 3 / 9: the oracle, the known status of 2^p - 1, and -- when the reference tree is present --
-    the reference's own program (m2:1141-1190) on the same exponent and radix"""
+    """complete LL tests at forced radix 3 / 9: the oracle, the known status of 2^p - 1, and what the reference's own program
+    (m2:1141-1190) printed for the same exponent and radix"""
     o = orc_crt.OracleCrt(p, odd)
     o.set(4)
     for _ in range(p - 2):
         o.square_mul(); o.sub(2)
     v = o.value()
     assert (v == 0) == prime
-    if os.path.exists(REF):
-        out = subprocess.run([REF, str(p), str(odd), "--no-progress"], capture_output=True, text=True).stdout
-        assert ("transform=%d*2^" % odd) in out and ("= %d," % o.n) in out      # same transform size rule (m2:479-503)
-        assert ("%d is prime" % p in out) == prime and ("%d is composite" % p in out) == (not prime)
+    out = REF_OUT["%d,%d" % (p, odd)]
+    assert ("transform=%d*2^" % odd) in out and ("= %d," % o.n) in out      # same transform size rule (m2:479-503)
+    assert ("%d is prime" % p in out) == prime and ("%d is composite" % p in out) == (not prime)
 
 
 @pytest.mark.parametrize("n", [9 << 20, 3 << 21])

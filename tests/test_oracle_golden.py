@@ -1,9 +1,8 @@
-"""Pin the CPU oracle: reference known answers, the reference's own host headers (oracle/_ref) and
-plain big-integer arithmetic.  No GPU."""
+"""Pin the CPU oracle: reference known answers, the outputs of the reference's own host headers (oracle/_ref, recorded in
+tests/golden/reference_outputs.json by tests/golden/make_reference_outputs.py) and plain big-integer arithmetic.  No GPU."""
+import hashlib
 import json
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -11,7 +10,7 @@ import pytest
 import orc
 
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_known_answers.json")))
-HAVE_REF = os.path.exists(orc.REF_HOST)
+REF_OUT = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_outputs.json")))
 
 
 def prp_run(p, check_at=None):
@@ -48,35 +47,31 @@ def test_transform_size_survey_values(oracle_lib, p, n):
     assert oracle_lib.orc_transform_size(p) == n
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref not built (reference tree absent)")
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
 @pytest.mark.parametrize("p", [31, 89, 127, 521, 1279, 3001, 9941, 100003, 1000003, 2500007])
 def test_tables_match_reference_headers(p):
-    """widths / weights / inverse weights equal what the reference's ibdwt.h computes."""
+    """widths / weights / inverse weights equal what the reference's ibdwt.h computes (its tables as SHA-256 digests)."""
     o = orc.Oracle(p, 1)
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "t.bin")
-        subprocess.check_call([orc.REF_HOST, "tables", str(p), out])
-        raw = open(out, "rb").read()
-    n = int(np.frombuffer(raw[:8], dtype=np.uint64)[0])
-    assert n == o.n
-    width = np.frombuffer(raw[8:8 + n], dtype=np.uint8)
-    w = np.frombuffer(raw[8 + n:8 + n + 8 * n], dtype=np.uint64)
-    wi = np.frombuffer(raw[8 + n + 8 * n:], dtype=np.uint64)
+    ref = REF_OUT["tables"][str(p)]
+    assert ref["n"] == o.n
+    width = o.widths()
     ow, owi = o.weights()
-    assert np.array_equal(width, o.widths())
-    assert np.array_equal(w, ow)
-    assert np.array_equal(wi, owi)
+    assert _sha(width.astype(np.uint8)) == ref["sha256_width_u8"]
+    assert _sha(ow.astype(np.uint64)) == ref["sha256_w_u64"]
+    assert _sha(owi.astype(np.uint64)) == ref["sha256_winv_u64"]
     assert int(width.astype(np.int64).sum()) == p
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref not built (reference tree absent)")
 def test_transform_size_matches_reference_headers(oracle_lib):
     rng = np.random.default_rng(7)
     ps = [3, 5, 31, 61, 89, 127, 1279, 86243, 9815459, 57885161, 136279841, 205271257, 600000001, 2147483647] + \
         [int(x) for x in rng.integers(100, 2**31, 40)]
+    assert sorted(map(int, REF_OUT["transform_size"])) == sorted(ps)
     for p in ps:
-        ref = int(subprocess.check_output([orc.REF_HOST, "size", str(p)]).split()[0])
-        assert oracle_lib.orc_transform_size(p) == ref, p
+        assert oracle_lib.orc_transform_size(p) == REF_OUT["transform_size"][str(p)], p
 
 
 @pytest.mark.parametrize("p", [31, 61, 89, 107, 127, 521, 607, 1279])
@@ -208,45 +203,37 @@ def test_radix5_sizes(oracle_lib, p):
     assert o.value(0) == x
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref not built (reference tree absent)")
 @pytest.mark.parametrize("p", [127, 9941, 100003])
 def test_digit_formatting_matches_reference_headers(p):
-    """res64 / equal_to / get_mpz / pack_words / div9 / hex: oracle vs the reference's own inline code."""
+    """res64 / equal_to / get_mpz / pack_words / div9 / hex: oracle vs the reference's own inline code (its outputs for these digit
+    vectors, get_mpz as a SHA-256 digest of its hex)."""
     M = (1 << p) - 1
     rng = np.random.default_rng(p)
     o = orc.Oracle(p, 2)
     cases = [9, 0, M, 3, int.from_bytes(rng.bytes((p + 7) // 8), "little") % M]
-    for v in cases:
+    assert len(REF_OUT["digits"][str(p)]) == len(cases)
+    for v, ref in zip(cases, REF_OUT["digits"][str(p)]):
         if v == M:
             d = o.widths().astype(np.uint64)
             d = ((np.uint64(1) << d) - np.uint64(1)) | (d << np.uint64(32))
         else:
             o.set_value(0, v)
             d = o.digits(0)
-        with tempfile.TemporaryDirectory() as td:
-            f = os.path.join(td, "d.bin")
-            d.tofile(f)
-            out = subprocess.check_output([orc.REF_HOST, "digits", str(p), f]).decode().split()
-        res64, eq9, eqMp, zhex, r64d9, r2048d9, r64raw = out
         L = orc.lib()
-        assert int(res64, 16) == L.orc_digits_res64(d.ctypes.data, o.n)
-        assert int(eq9) == L.orc_digits_equal_to(d.ctypes.data, o.n, 9)
-        assert int(eqMp) == L.orc_digits_equal_to_Mp(d.ctypes.data, o.n)
-        assert int(zhex, 16) == (0 if v == M else v)
+        assert int(ref["res64"], 16) == L.orc_digits_res64(d.ctypes.data, o.n)
+        assert ref["equal9"] == L.orc_digits_equal_to(d.ctypes.data, o.n, 9)
+        assert ref["equalMp"] == L.orc_digits_equal_to_Mp(d.ctypes.data, o.n)
+        assert ref["mpz_sha256"] == hashlib.sha256(("%x" % (0 if v == M else v)).encode()).hexdigest()
         a64, a2048 = orc.prp_type1_hex(d, p)
-        assert (a64, a2048) == (r64d9, r2048d9)
+        assert (a64, a2048) == (ref["res64_div9"], ref["res2048_div9"])
         w = orc.pack_words(d, p)
-        assert "%016X" % (orc.words_to_int(w) & (2**64 - 1)) == r64raw
+        assert "%016X" % (orc.words_to_int(w) & (2**64 - 1)) == ref["res64_raw"]
         if v != M:
             # reference set_mpz -> digits equals the oracle's set_words
-            with tempfile.TemporaryDirectory() as td:
-                f = os.path.join(td, "o.bin")
-                subprocess.check_call([orc.REF_HOST, "setmpz", str(p), "%x" % (v + M), f])
-                dref = np.fromfile(f, dtype=np.uint64)
             # engine::set_mpz truncates bit-wise (no reduction); compare for v < Mp only via value
             o.set_value(1, v)
             assert orc.digits_to_int(o.digits(1)) == v
-            assert dref.size == o.n
+            assert ref["setmpz_digits"] == o.n
 
 
 PINS = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "big_p_pins.json")))

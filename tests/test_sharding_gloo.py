@@ -165,8 +165,8 @@ def _torchrun(tmp_path, *args, timeout=300):
 def test_launcher_refuses_to_start_without_a_gpu(tmp_path):
     """the launcher counts its devices without the HIP runtime (KFD topology) and fails with a clear message when none is
     visible, instead of creating engines on `local_rank % 0`."""
-    import torch
-    if torch.cuda.is_available():
+    from prmers_amd import launch
+    if launch.visible_gpu_count():
         pytest.skip("needs a box without a GPU")
     wt = tmp_path / "worktodo.txt"
     wt.write_text("PRP=1,2,127,-1\n")

@@ -5,7 +5,7 @@
 A=$1; B=$2; shift 2
 for rep in 1 2 3; do
   for L in "$A" "$B"; do
-    MI355_ENGINE_LIB=$L python bench.py --no-cpu-baseline --steps 1500 --warmup 150 "$@" | python -c "
+    MI355_ENGINE_LIB=$L python bench.py --full --no-cpu-baseline --steps 1500 --warmup 150 "$@" | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms']
 print('$L', d['ms_per_step'], {a:round(b*1e3,1) for a,b in k.items() if a in ('k_front','k_middle','k_back')})"
   done

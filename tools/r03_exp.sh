@@ -6,7 +6,7 @@ O=gpurun_out/r03; mkdir -p $O
 timeout -k 10 500 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "square or c3 or identit or edge or gmp" > $O/${TAG}_tests.log 2>&1
 tail -3 $O/${TAG}_tests.log
 for t in $TUNES; do
-  MI355_TUNE=$t python bench.py --no-cpu-baseline --steps 1500 --warmup 150 > $O/${TAG}_bench_tune$t.json 2> $O/${TAG}_bench_tune$t.err
+  MI355_TUNE=$t python bench.py --full --no-cpu-baseline --steps 1500 --warmup 150 > $O/${TAG}_bench_tune$t.json 2> $O/${TAG}_bench_tune$t.err
   python - <<PY
 import json
 try:

@@ -5,10 +5,10 @@ O=gpurun_out/r04
 mkdir -p $O
 python -m pytest tests -m gpu -x -q > $O/job1_tests.log 2>&1; echo "tests rc=$?" | tee $O/job1_tests.rc
 tail -3 $O/job1_tests.log
-python bench.py > $O/job1_bench_default.json 2> $O/job1_bench_default.err && tail -c 600 $O/job1_bench_default.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/job1_bench_driver.json 2>> $O/job1_bench_default.err
+python bench.py --full > $O/job1_bench_default.json 2> $O/job1_bench_default.err && tail -c 600 $O/job1_bench_default.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/job1_bench_driver.json 2>> $O/job1_bench_default.err
 for plan in "m2=2048,c=2" "m2=8192,c=8"; do
-  python bench.py --no-cpu-baseline --plan "$plan" > "$O/job1_bench_plan_${plan//[=,]/_}.json" 2>> $O/job1_bench_default.err
+  python bench.py --full --no-cpu-baseline --plan "$plan" > "$O/job1_bench_plan_${plan//[=,]/_}.json" 2>> $O/job1_bench_default.err
 done
 python - <<'PY'
 import json,glob

@@ -5,7 +5,7 @@ O=gpurun_out/r04
 mkdir -p $O
 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fused_ops.py -x -q -k "400063 or 800283 or 1600589 or 205271257 or c4 or radix4" > $O/job10_tests.log 2>&1; echo "tests rc=$?"; tail -3 $O/job10_tests.log
 for rep in 1 2 3; do for L in prmers_amd/libmi355_engine_ldsadd3.so prmers_amd/libmi355_engine.so; do for p in 205271257 332000003 100000007; do
-  MI355_ENGINE_LIB=$L python bench.py --exponent $p --no-cpu-baseline --steps 1000 --warmup 100 2>/dev/null | python -c "
+  MI355_ENGINE_LIB=$L python bench.py --full --exponent $p --no-cpu-baseline --steps 1000 --warmup 100 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms']
 print('$L'.split('/')[-1], $p, d['ms_per_step'], {a:round(b*1e3,1) for a,b in k.items() if a in ('k_front','k_middle','k_back')})"
 done; done; done > $O/job10_ab_v5_lds.txt 2>&1; cat $O/job10_ab_v5_lds.txt

@@ -9,7 +9,7 @@ python -m pytest tests/test_gpu_parity.py tests/test_gpu_runs.py tests/test_gpu_
 tools/ab_many.sh "136279841" prmers_amd/libmi355_engine_r3forms.so prmers_amd/libmi355_engine.so > $O/job2_ab_forms_c3.txt 2>&1; cat $O/job2_ab_forms_c3.txt
 PS="205271257 57885161 250000013 30402457"
 for L in prmers_amd/libmi355_engine_r3forms.so prmers_amd/libmi355_engine.so prmers_amd/libmi355_engine_r3forms.so prmers_amd/libmi355_engine.so; do for p in $PS; do
-  MI355_ENGINE_LIB=$L python bench.py --exponent $p --no-cpu-baseline --steps 1000 --warmup 100 | python -c "
+  MI355_ENGINE_LIB=$L python bench.py --full --exponent $p --no-cpu-baseline --steps 1000 --warmup 100 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms']
 print('$L'.split('/')[-1], $p, d['ms_per_step'], {a:round(b*1e3,1) for a,b in k.items() if a in ('k_front','k_middle','k_back')})"
 done; done > $O/job2_ab_forms_sizes.txt 2>&1; cat $O/job2_ab_forms_sizes.txt

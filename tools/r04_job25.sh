@@ -6,10 +6,10 @@ mkdir -p $O
 cd $GRAFT_REPO_ROOT
 timeout -k 10 900 python -m pytest tests -m gpu -x -q --durations=8 > $O/job25_pytest.log 2>&1; rc=$?; tail -14 $O/job25_pytest.log; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-python bench.py > $O/job25_bench_default.json 2> $O/job25_bench.err; echo "bench default rc=$?"
-python bench.py --steps 20 --warmup 5 > $O/job25_bench_driver.json 2>> $O/job25_bench.err; echo "bench driver rc=$?"
-python bench.py --exponent 9815459 --no-cpu-baseline > $O/job25_bench_c2.json 2>> $O/job25_bench.err
-python bench.py --exponent 205271257 --no-cpu-baseline > $O/job25_bench_c4.json 2>> $O/job25_bench.err
+python bench.py --full > $O/job25_bench_default.json 2> $O/job25_bench.err; echo "bench default rc=$?"
+python bench.py --full --steps 20 --warmup 5 > $O/job25_bench_driver.json 2>> $O/job25_bench.err; echo "bench driver rc=$?"
+python bench.py --full --exponent 9815459 --no-cpu-baseline > $O/job25_bench_c2.json 2>> $O/job25_bench.err
+python bench.py --full --exponent 205271257 --no-cpu-baseline > $O/job25_bench_c4.json 2>> $O/job25_bench.err
 bash tools/bench_sizes.sh 2976221 4800007 9815459 19000013 30402457 50000017 57885161 100000007 136279841 205271257 250000013 332000003 600000001 700000001 > $O/job25_bench_sizes.txt 2>&1; cat $O/job25_bench_sizes.txt
 python - <<'PY'
 import json

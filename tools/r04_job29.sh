@@ -6,9 +6,9 @@ mkdir -p $O
 cd $GRAFT_REPO_ROOT
 timeout -k 10 600 bash tools/profile.sh r04b_c4 --exponent 205271257 > $O/job29_profile_c4.log 2>&1; echo "profile c4 rc=$?"
 cd $GRAFT_REPO_ROOT
-python bench.py --exponent 205271257 --no-cpu-baseline > $O/job29_bench_c4.json 2>> $O/job29_bench.err
-python bench.py > $O/job29_bench_default.json 2>> $O/job29_bench.err
-python bench.py --steps 20 --warmup 5 > $O/job29_bench_driver.json 2>> $O/job29_bench.err
+python bench.py --full --exponent 205271257 --no-cpu-baseline > $O/job29_bench_c4.json 2>> $O/job29_bench.err
+python bench.py --full > $O/job29_bench_default.json 2>> $O/job29_bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/job29_bench_driver.json 2>> $O/job29_bench.err
 bash tools/bench_sizes.sh 50000017 100000007 205271257 332000003 700000001 > $O/job29_bench_sizes.txt 2>&1; cat $O/job29_bench_sizes.txt
 python - <<'PY'
 import json

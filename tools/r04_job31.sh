@@ -8,7 +8,7 @@ timeout -k 10 300 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fuzz_
 timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fused_ops.py tests/test_gpu_runs.py tests/test_gpu_switches.py tests/test_gpu_fuzz_plans.py tests/test_gpu_canon.py tests/test_prp_driver.py tests/test_host_logic.py -m gpu -x -q > $O/job31_pytest.log 2>&1; rc=$?; tail -5 $O/job31_pytest.log; [ $rc -ne 0 ] && exit $rc
 for rep in 1 2; do for L in prmers_amd/libmi355_engine_base.so prmers_amd/libmi355_engine.so; do for p in 13466917 25000009 1300000003; do
   steps=1500; [ $p -gt 700000000 ] && steps=60
-  MI355_ENGINE_LIB=$L python bench.py --exponent $p --no-cpu-baseline --steps $steps --warmup 20 --preheat-seconds 1 2>/dev/null | python -c "
+  MI355_ENGINE_LIB=$L python bench.py --full --exponent $p --no-cpu-baseline --steps $steps --warmup 20 --preheat-seconds 1 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms']
 print('$L'.split('/')[-1], $p, d['config']['plan'], d['ms_per_step'], {a:round(b*1e3,1) for a,b in k.items() if a in ('k_front','k_middle','k_back')})"
 done; done; done > $O/job31_ab.txt 2>&1

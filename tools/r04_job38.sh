@@ -5,8 +5,8 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r04b
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-python bench.py > $O/job38_bench_default.json 2> $O/job38_bench.err; echo "bench default rc=$?"
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/job38_bench_driver.json 2>> $O/job38_bench.err; echo "bench driver rc=$?"
+python bench.py --full > $O/job38_bench_default.json 2> $O/job38_bench.err; echo "bench default rc=$?"
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/job38_bench_driver.json 2>> $O/job38_bench.err; echo "bench driver rc=$?"
 python - <<'PY'
 import json
 for f in ("job38_bench_default.json","job38_bench_driver.json"):

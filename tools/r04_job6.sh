@@ -7,7 +7,7 @@ mkdir -p $O
 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fused_ops.py -x -q > $O/job6_tests.log 2>&1; echo "tests rc=$?"; tail -2 $O/job6_tests.log
 tools/ab_many.sh "136279841" prmers_amd/libmi355_engine_ldsadd3.so prmers_amd/libmi355_engine.so 2>&1 | grep -v amdgpu.ids > $O/job6_ab_lds_c3.txt; cat $O/job6_ab_lds_c3.txt
 for L in prmers_amd/libmi355_engine_ldsadd3.so prmers_amd/libmi355_engine.so prmers_amd/libmi355_engine_ldsadd3.so prmers_amd/libmi355_engine.so; do for p in 205271257 57885161 250000013 30402457 600000001; do
-  MI355_ENGINE_LIB=$L python bench.py --exponent $p --no-cpu-baseline --steps 1000 --warmup 100 2>/dev/null | python -c "
+  MI355_ENGINE_LIB=$L python bench.py --full --exponent $p --no-cpu-baseline --steps 1000 --warmup 100 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms']
 print('$L'.split('/')[-1], $p, d['ms_per_step'], {a:round(b*1e3,1) for a,b in k.items() if a in ('k_front','k_middle','k_back')})"
 done; done > $O/job6_ab_lds_sizes.txt 2>&1; cat $O/job6_ab_lds_sizes.txt

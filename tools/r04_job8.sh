@@ -3,7 +3,7 @@
 set -o pipefail
 O=gpurun_out/r04
 mkdir -p $O
-run() { MI355_TUNE=$1 python bench.py --exponent $2 --no-cpu-baseline --steps 3000 --warmup 300 ${3:+--plan $3} 2>/dev/null | python -c "
+run() { MI355_TUNE=$1 python bench.py --full --exponent $2 --no-cpu-baseline --steps 3000 --warmup 300 ${3:+--plan $3} 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms']
 print('tune=$1', $2, d['config']['plan'], d['ms_per_step'], {a:round(b*1e3,1) for a,b in k.items() if a in ('k_front','k_middle','k_back')})"; }
 for rep in 1 2; do
