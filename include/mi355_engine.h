@@ -53,6 +53,10 @@ MI355_ENGINE_API int mi355_engine_set_words(mi355_engine_handle handle, size_t d
 MI355_ENGINE_API int mi355_engine_get_words(mi355_engine_handle handle, size_t src, uint32_t* words, size_t count);       /* get_mpz, engine.h:173 */
 MI355_ENGINE_API int mi355_engine_copy(mi355_engine_handle handle, size_t dst, size_t src);          /* engine::copy, engine.h:49 */
 MI355_ENGINE_API int mi355_engine_prepare(mi355_engine_handle handle, size_t dst, size_t src);       /* set_multiplicand, engine.h:53 */
+/* Every factor in [1, 2^32) is exact.  Up to a bound of the plan the back sweep multiplies it into its carry chain (64-bit terms:
+   the bound is 33537975 at p = 9815459, 7254967 at p = 136279841, 838834 at p = 205271257, and at least 15 everywhere; runs of two
+   digits: 15; plan.hpp fused_factor_limit); above it the operation runs with factor 1 and a run-wise x factor pass follows.  The one
+   exception: mul_add with add_src == dst needs the fused form and refuses a factor above the bound. */
 MI355_ENGINE_API int mi355_engine_square_mul(mi355_engine_handle handle, size_t reg, uint32_t factor);      /* engine.h:51 */
 MI355_ENGINE_API int mi355_engine_mul(mi355_engine_handle handle, size_t dst, size_t src, uint32_t factor); /* engine.h:60 */
 MI355_ENGINE_API int mi355_engine_add(mi355_engine_handle handle, size_t dst, size_t src);           /* engine.h:64 */
@@ -75,7 +79,7 @@ MI355_ENGINE_API int mi355_engine_mul_copy(mi355_engine_handle handle, size_t ds
 /* count x { reg = reg^2 * factor; reg -= sub } -- the run of squarings a PRP (sub = 0) or Lucas-Lehmer (sub = 2) loop issues between two
    checks (src/modes/RunPrpOrLlMarin.cpp:338-409: one square_mul, and for LL one sub, per iteration).  Same result as the loop of
    mi355_engine_square_mul / mi355_engine_sub_u32 calls, issued by the library in one call (no per-iteration trip through the FFI; an LL
-   subtraction rides on the next front sweep).  (A one-cooperative-launch form for transforms of at most 2^20 words was built and measured
+   subtraction borrows through the digits).  (A one-cooperative-launch form for transforms of at most 2^20 words was built and measured
    slower than three launches per squaring; it is not in this library: DESIGN.md 5.2c.) */
 MI355_ENGINE_API int mi355_engine_square_mul_n(mi355_engine_handle handle, size_t reg, uint32_t factor, size_t count, uint32_t sub);
 

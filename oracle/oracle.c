@@ -61,6 +61,10 @@ static inline uint32_t adc(uint64_t lhs, uint8_t width, uint64_t* carry) {
   *carry = (s >> width) + (c << (64 - width));
   return (uint32_t)s & ((1u << width) - 1);
 }
+/* x a in 64 bits, as the reference has it: exact while (lhs >> width) a + the carry stays below 2^64, i.e. for factors up to the
+   engine's fused bound (prmers_amd/csrc/plan.hpp fused_factor_limit: about 2^25 at n = 2^19, 2^22.8 at n = 2^23, 2^19.7 at
+   n = 5 2^21 for the worst-case input).  Beyond it the oracle overflows (x = 2^p - 2 at p = 9815459: a = 2^28 + 1 is wrong), so the
+   tests check large factors against Python integers instead. */
 static inline uint32_t adc_mul(uint64_t lhs, uint32_t a, uint8_t width, uint64_t* carry) {
   uint64_t c = 0;
   const uint32_t d = adc(lhs, width, &c);

@@ -285,11 +285,11 @@ void Engine::normalize(size_t r) {
 // convolution sums of unsigned digits are ~ n 2^(2w-2)); its first digit absorbs w of them and the rest lands on the
 // run's second digit, log2(n) - 2 (+ log2 a) bits above its width -- too much for the next squaring once that exceeds w.
 // Local carry passes (canon.hip k_relax) take w bits off per pass; as many as it takes to get below the width follow.
-void Engine::carry_fix_now(size_t r) {
+void Engine::carry_fix_now(size_t r, int excess) {
   HIPCHK(launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
   pending_carry_[r] = 0;
   if (pl_.C >= 2) return;
-  int excess = ilog2(pl_.n) + 1 + 4 - 2;   // log2(n) rounded up, factor a up to 15
+  if (excess < 0) excess = ilog2(pl_.n) + 1 + 4 - 2;   // log2(n) rounded up, factor a up to 15 (plan.hpp a_fast)
   const int w = int(pl_.q);                 // the narrower digit width
   while (excess > w - 2) {
     HIPCHK(canon_relax(dp_, pl_.p, digits(r), reinterpret_cast<uint32_t*>(work()), stream_));
@@ -565,6 +565,7 @@ void Engine::copy(size_t dst, size_t src) {
 }
 
 void Engine::square_chain(size_t r, uint32_t a, hipEvent_t* ev) {
+  if (a > pl_.a_fast) { square_chain(r, 1, ev); scale(r, a); return; }   // beyond the fused carry's bound (plan.hpp fused_factor_limit)
   if (ev) HIPCHK(hipEventRecord(ev[0], stream_));
 #if defined(MI355_EXPERIMENTAL)
   if (coop_groups_ && pending_sub_[r] < (1u << 30)) {   // one launch: the whole squaring sits in slot 0
@@ -608,6 +609,7 @@ void Engine::square_mul_n(size_t r, uint32_t a, size_t count, uint32_t sub) {
   if (a == 0) throw std::runtime_error("square_mul_n: factor must be >= 1");
   if (count == 0) return;
   HIPCHK(hipSetDevice(device_));
+  if (a > pl_.a_fast) { for (size_t i = 0; i < count; ++i) { square_chain(r, a, nullptr); if (sub) sub_u32(r, sub); } return; }
 #if defined(MI355_EXPERIMENTAL)
   if (coop_groups_ && pending_sub_[r] < (1u << 30) && sub < (1u << 30)) { coop_launch(r, a, count, sub); return; }
 #endif
@@ -668,7 +670,19 @@ void Engine::mul(size_t dst, size_t src, uint32_t a) {
   HIPCHK(hipSetDevice(device_));
   run_front(dst);
   run_middle(work(), image(src), work(), 1, 0);
-  run_back(dst, a);
+  run_back(dst, a > pl_.a_fast ? 1u : a);
+  if (a > pl_.a_fast) scale(dst, a);
+}
+
+// r = r x a, run-wise (kernels.hip k_scale): the factors above the plan's fused bound follow the operation with factor 1
+void Engine::scale(size_t r, uint32_t a) {
+  digits_ready(r);
+  uint64_t* fresh = take_spare_cbuf();
+  HIPCHK(launch_scale(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, digits(r), fresh, a, stream_));
+  adopt_cbuf(r, fresh);
+  pending_carry_[r] = 1;
+  // runs of two digits: the carry words (below 2^34: digit < 2^(q+2) after the passes, times a < 2^32) go in at once
+  if (pl_.C < 2) carry_fix_now(r, 34 - int(pl_.q));
 }
 
 uint64_t* Engine::take_spare_cbuf() {
@@ -756,7 +770,7 @@ void Engine::square_mul_copy(size_t src, size_t dst_copy, uint32_t a) {
   need_digits(src, "square_mul_copy"); check_reg(dst_copy);
   if (a == 0) throw std::runtime_error("square_mul_copy: factor must be >= 1");
   HIPCHK(hipSetDevice(device_));
-  if (dst_copy == src || pl_.split5) { square_mul(src, a); copy(dst_copy, src); return; }
+  if (dst_copy == src || pl_.split5 || a > pl_.a_fast) { square_mul(src, a); copy(dst_copy, src); return; }
   run_front(src);
   run_middle(work(), nullptr, work(), 0, 0);
   back_ext(src, a, long(dst_copy), -1);
@@ -768,7 +782,7 @@ void Engine::mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t a) {
   if (dst == src || dst_copy == src) throw std::runtime_error("mul_copy: the multiplicand must differ from the outputs");
   if (a == 0) throw std::runtime_error("mul_copy: factor must be >= 1");
   HIPCHK(hipSetDevice(device_));
-  if (dst_copy == dst || pl_.split5) { mul(dst, src, a); copy(dst_copy, dst); return; }
+  if (dst_copy == dst || pl_.split5 || a > pl_.a_fast) { mul(dst, src, a); copy(dst_copy, dst); return; }
   run_front(dst);
   run_middle(work(), image(src), work(), 1, 0);
   back_ext(dst, a, long(dst_copy), -1);
@@ -780,8 +794,10 @@ void Engine::mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t a) {
   if (dst == mul_src) throw std::runtime_error("mul_add: dst and mul_src must differ");
   if (a == 0) throw std::runtime_error("mul_add: factor must be >= 1");
   HIPCHK(hipSetDevice(device_));
-  if (pl_.split5) {   // the split sweeps have no fused variants: the base-class composition (engine.h:65-70)
-    if (add_src == dst) throw std::runtime_error("mul_add: add_src == dst needs the fused sweep, which this transform size does not have");
+  if (pl_.split5 || a > pl_.a_fast) {   // no fused sweep (split sweeps; factors above the fused bound): the base-class composition (engine.h:65-70)
+    if (add_src == dst)
+      throw std::runtime_error(pl_.split5 ? "mul_add: add_src == dst needs the fused sweep, which this transform size does not have"
+                                          : "mul_add: add_src == dst needs the fused sweep, which takes factors up to the plan's fused bound only (mi355_engine.h)");
     mul(dst, mul_src, a); add(dst, add_src); return;
   }
   if (add_src != dst) digits_ready(add_src);
@@ -795,7 +811,8 @@ void Engine::sub_u32(size_t r, uint32_t v) {
   need_digits(r, "sub");
   if (v == 0) return;
   HIPCHK(hipSetDevice(device_));
-  if ((v2cols_ || coop_on()) && uint64_t(pending_sub_[r]) + v < (1u << 30)) { pending_sub_[r] += v; return; }  // folded into the next front / middle sweep
+  // (not deferred into the next front sweep as a field element: digit 0 plus its carry may be below v, and the sums of a sparse register
+  // then go negative, which the unsigned back sweep reads as values near the field prime; the borrow below is exact for every register)
   // the small subtraction only touches the digit vector (cyclic borrow), so run carries that are still pending
   // for the next front sweep can stay pending: value = digits + carries - v either way
   if (!(kind_[r] == kDigits && pl_.C >= 2 && !pending_sub_[r])) normalize(r);
@@ -927,7 +944,7 @@ void Engine::time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, d
     // which of the five slots hold a kernel on this path
     const bool fix_now = !v2cols_ && pl_.C < 2;                        // k_carry_fix right after the back sweep
     const bool coop = coop_on();                                       // (experimental build) one launch (slot 0) for the whole squaring
-    const bool sub_kernel = sub != 0 && !((v2cols_ || coop) && sub < (1u << 30));          // k_sub_small (else folded into the next front sweep)
+    const bool sub_kernel = sub != 0;                                  // k_sub_small
     const bool launched[5] = {true, !coop, !coop, fix_now && !coop, sub_kernel};
     for (size_t k = 0; k < 5 && k < kcount; ++k) kernel_ms[k] = launched[k] ? std::max(0.0, kernel_ms[k] - overhead) : -1.0;
     if (kcount > 5) kernel_ms[5] = overhead;

@@ -741,6 +741,34 @@ __global__ void __launch_bounds__(256) k_linear(DevPlan pl, LinArgs la) {
 }
 
 
+// x a for the factors above the plan's fused bound (plan.hpp fused_factor_limit; Engine::scale): one thread per run, the run's digits with
+// their pending carry-in taken as k_linear takes them (three masked digits, the rest on the fourth; all of it on the second when C = 1),
+// times a with a carry through the run, whose carry-out word is left pending.  Digit outputs may alias the input, cout must not alias cin.
+// Bounds: a digit after the carry-in is below 2^31 (fused_factor_ok), so digit a + carry < 2^63 + 2^(64 - q).
+__global__ void __launch_bounds__(256) k_scale(DevPlan pl, const uint32_t* __restrict__ in, const uint64_t* __restrict__ cin,
+                                               uint32_t* __restrict__ out, uint64_t* __restrict__ cout, uint32_t a) {
+  const uint32_t run = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t M1 = pl.M1, C = pl.C, NT = pl.M2 / C;
+  if (run >= M1 * NT) return;
+  const uint32_t T = run / M1, i1 = run - T * M1;
+  const size_t off = (size_t(T) * M1 + i1) * C * 2;
+  const uint32_t sa = pl.SA[i1];
+  uint64_t ci = cin ? carry_in_of(pl, cin, T, i1) : 0, c = 0;
+  for (uint32_t k = 0; k < 2 * C; ++k) {
+    uint32_t width; bool wrap;
+    digit_info(pl, sa, pl.SB[2 * (T * C) + k], width, wrap);
+    const uint64_t mask = (uint64_t(1) << width) - 1;
+    uint64_t xv = in[off + k];
+    if (k < 3 && k + 1 < 2 * C) { xv += ci; ci = xv >> width; xv &= mask; }
+    else if (k == 3 || k + 1 == 2 * C) { xv += ci; ci = 0; }
+    const uint64_t v = xv * a + c;
+    out[off + k] = uint32_t(v & mask);
+    c = v >> width;
+  }
+  cout[size_t(T) * M1 + i1] = c;
+}
+
+
 // carry fix: one thread per run; weak carry (the remainder, if any, stays on the run's last digit:
 // same contract as adc4, marin.cl:203-212)
 __global__ void __launch_bounds__(256) k_carry_fix(DevPlan pl, uint32_t* __restrict__ digits, const uint64_t* __restrict__ cbuf) {
@@ -914,6 +942,11 @@ hipError_t launch_coop(const DevPlan& pl, uint32_t groups, uint32_t* digits, uin
 hipError_t launch_linear(const DevPlan& pl, const LinArgs& la, hipStream_t s) {
   const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
   hipLaunchKernelGGL(k_linear, dim3((runs + 255) / 256), dim3(256), 0, s, pl, la);
+  return hipGetLastError();
+}
+hipError_t launch_scale(const DevPlan& pl, const uint32_t* in, const uint64_t* cin, uint32_t* out, uint64_t* cout, uint32_t a, hipStream_t s) {
+  const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
+  hipLaunchKernelGGL(k_scale, dim3((runs + 255) / 256), dim3(256), 0, s, pl, in, cin, out, cout, a);
   return hipGetLastError();
 }
 hipError_t launch_carry_fix(const DevPlan& pl, uint32_t* digits, const uint64_t* cbuf, hipStream_t s) {

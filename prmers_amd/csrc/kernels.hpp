@@ -64,6 +64,8 @@ struct LinArgs {
   uint32_t* d1 = nullptr; uint64_t* cd1 = nullptr; uint32_t* d2 = nullptr; uint64_t* cd2 = nullptr;
 };
 hipError_t launch_linear(const DevPlan& pl, const LinArgs& la, hipStream_t s);
+// out = (in + its pending carries cin, nullable) x a, run-wise, carry-out words to cout (kernels.hip k_scale)
+hipError_t launch_scale(const DevPlan& pl, const uint32_t* in, const uint64_t* cin, uint32_t* out, uint64_t* cout, uint32_t a, hipStream_t s);
 hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
 hipError_t v2_launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
 

@@ -14,6 +14,7 @@
 //   * registers hold UNWEIGHTED digits as u32 in a tile-major order chosen so that both the front
 //     and the back sweep touch them fully coalesced.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
@@ -56,6 +57,7 @@ struct Plan {
   bool split5 = false;      // columns of 5 L1 pairs beyond LDS: the radix-5 stage runs through memory (kernels.hip k_front_split_*), C = 1
   uint32_t q = 0, t = 0;    // p = q*n + t
   uint32_t twh = 0;         // omega_m^e = TWlo[e & (2^twh-1)] * TWhi[e >> twh]
+  uint32_t a_fast = 1;      // largest factor the back sweeps multiply in themselves (fused_factor_ok); above it: factor 1 + k_scale
   size_t lds_front = 0, lds_mid = 0;
 
   // host tables (uploaded as-is)
@@ -96,6 +98,52 @@ struct Plan {
     return buf;
   }
 };
+
+// Whether the back sweeps' fused x a (adc_mul, marin.cl:194-201: carry = (r >> w) + (u >> w) a in 64 bits) is exact for factor a on a
+// plan with digit widths q / q + 1, n digits and runs of 2C digits, at the worst input: every digit at 2^(q+1) - 1 except the one per run
+// that takes the remainder of the carry-in (apply_carry_in / run_carry_in: three digits absorb it, the fourth keeps the rest: digit E).
+//   convolution sum  u <= sum x_i^2 (Cauchy-Schwarz) = (n - n/2C) D^2 + (n/2C) E^2, which must stay below the field prime;
+//   back sweep       r = dlo a + carry + addend (< 2^32) and carry' = (r >> q) + (u >> q) a below 2^64 at the carry's fixed point;
+//   next sweep       E = D + (carry >> 3q) + 3, the digit the carry word leaves behind (below 2^31, so that x a fits k_scale too).
+// Runs of two digits (C = 1) take their carries at once and the local carry passes restore the digits (Engine::carry_fix_now, sized for
+// a <= 15): only the 64-bit terms are checked there, and a_fast is capped at 15.
+inline bool fused_factor_ok(uint32_t q, size_t n, uint32_t C, uint64_t a) {
+  typedef unsigned __int128 u128;
+  const u128 field = (u128(1) << 64) - (u128(1) << 32) + 1, lim = u128(1) << 64;
+  const u128 D = (u128(1) << (q + 1)) - 1;
+  const size_t runs = n / (2 * size_t(C));
+  u128 E = D;
+  for (int it = 0; it < 64; ++it) {
+    const u128 U = (C >= 2) ? u128(n - runs) * D * D + u128(runs) * E * E : u128(n) * D * D;
+    if (U >= field) return false;
+    const u128 chi = U >> q;
+    u128 c = 0;
+    for (int k = 0; k < 4096; ++k) {   // carry_{k+1} = f(carry_k) rises to its fixed point, which bounds every run
+      const u128 r = D * a + c + (u128(1) << 32);
+      if (r >= lim) return false;
+      const u128 c2 = (r >> q) + chi * a;
+      if (c2 >= lim) return false;
+      if (c2 == c) break;
+      c = c2;
+    }
+    if (C < 2) return true;
+    const u128 E2 = D + (c >> (3 * q)) + 3;
+    if (E2 >= (u128(1) << 31)) return false;
+    if (E2 <= E) return true;
+    E = E2;
+  }
+  return false;
+}
+
+inline uint32_t fused_factor_limit(uint32_t q, size_t n, uint32_t C) {
+  uint64_t lo = 1, hi = 0xffffffffu;
+  if (!fused_factor_ok(q, n, C, 1)) return 1;   // (never for a plan of the size rule; factor 1 is the plain squaring either way)
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi + 1) / 2;
+    if (fused_factor_ok(q, n, C, mid)) lo = mid; else hi = mid - 1;
+  }
+  return uint32_t(C >= 2 ? lo : std::min<uint64_t>(lo, 15));
+}
 
 // spec: "" (auto) or comma/colon separated "m2=<pow2>", "c=<pow2>"
 inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables = true) {
@@ -176,6 +224,7 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
   pl.lds_mid = size_t(pl.M2) * 16;
   pl.q = uint32_t(p / pl.n);
   pl.t = uint32_t(p % pl.n);
+  pl.a_fast = fused_factor_limit(pl.q, pl.n, pl.C);
   if (!build_tables) return pl;
 
   const size_t n = pl.n, m = pl.m;

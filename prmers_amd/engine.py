@@ -7,6 +7,7 @@ as EngineError where the reference throws std::runtime_error.  There is no CPU f
 built HIP library or without a GPU, construction fails.
 """
 import ctypes as C
+import operator
 import os
 
 import numpy as np
@@ -116,6 +117,18 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def u32_arg(name, v):
+    """v as a uint32_t argument of the C ABI: ctypes would silently keep the low 32 bits of anything else
+    (2**32 + 3 -> 3, -1 -> 2**32 - 1), so values outside [0, 2**32) are refused here, before any C call."""
+    try:
+        iv = operator.index(v)
+    except TypeError:
+        raise TypeError("%s must be an integer, not %s" % (name, type(v).__name__)) from None
+    if not 0 <= iv <= 0xFFFFFFFF:
+        raise ValueError("%s = %d is outside the 32-bit range [0, 2**32) of the engine's C ABI" % (name, iv))
+    return iv
+
+
 class Engine:
     """engine::create_gpu(p, reg_count, device, verbose) on an MI355X (include/marin/engine.h:301)."""
 
@@ -152,24 +165,24 @@ class Engine:
     # --- engine.h surface ---
     def get_size(self): return self.n
     def sync(self): self._ok(self.L.mi355_engine_sync(self.h))
-    def set(self, dst, a): self._ok(self.L.mi355_engine_set_u32(self.h, dst, a))
+    def set(self, dst, a): self._ok(self.L.mi355_engine_set_u32(self.h, dst, u32_arg("value", a)))
     def copy(self, dst, src): self._ok(self.L.mi355_engine_copy(self.h, dst, src))
-    def square_mul(self, src, a=1): self._ok(self.L.mi355_engine_square_mul(self.h, src, a))
+    def square_mul(self, src, a=1): self._ok(self.L.mi355_engine_square_mul(self.h, src, u32_arg("factor", a)))
     def set_multiplicand(self, dst, src): self._ok(self.L.mi355_engine_prepare(self.h, dst, src))
-    def mul(self, dst, src, a=1): self._ok(self.L.mi355_engine_mul(self.h, dst, src, a))
-    def sub(self, src, a): self._ok(self.L.mi355_engine_sub_u32(self.h, src, a))
+    def mul(self, dst, src, a=1): self._ok(self.L.mi355_engine_mul(self.h, dst, src, u32_arg("factor", a)))
+    def sub(self, src, a): self._ok(self.L.mi355_engine_sub_u32(self.h, src, u32_arg("value", a)))
     def add(self, dst, src): self._ok(self.L.mi355_engine_add(self.h, dst, src))
     def sub_reg(self, dst, src): self._ok(self.L.mi355_engine_sub_reg(self.h, dst, src))
 
     # fused variants (engine.h:65-131): one sweep each
     def addsub(self, sum_out, diff_out, a, b): self._ok(self.L.mi355_engine_addsub(self.h, sum_out, diff_out, a, b))
     def addsub_copy(self, s, d, s_copy, d_copy, a, b): self._ok(self.L.mi355_engine_addsub_copy(self.h, s, d, s_copy, d_copy, a, b))
-    def mul_add(self, dst, mul_src, add_src, a=1): self._ok(self.L.mi355_engine_mul_add(self.h, dst, mul_src, add_src, a))
-    def square_mul_copy(self, src, dst_copy, a=1): self._ok(self.L.mi355_engine_square_mul_copy(self.h, src, dst_copy, a))
+    def mul_add(self, dst, mul_src, add_src, a=1): self._ok(self.L.mi355_engine_mul_add(self.h, dst, mul_src, add_src, u32_arg("factor", a)))
+    def square_mul_copy(self, src, dst_copy, a=1): self._ok(self.L.mi355_engine_square_mul_copy(self.h, src, dst_copy, u32_arg("factor", a)))
     def square_mul_n(self, src, count, a=1, sub=0):
         """count x { src = src^2 * a; src -= sub }: one cooperative launch on the small transforms."""
-        self._ok(self.L.mi355_engine_square_mul_n(self.h, src, a, count, sub))
-    def mul_copy(self, dst, src, dst_copy, a=1): self._ok(self.L.mi355_engine_mul_copy(self.h, dst, src, dst_copy, a))
+        self._ok(self.L.mi355_engine_square_mul_n(self.h, src, u32_arg("factor", a), count, u32_arg("sub", sub)))
+    def mul_copy(self, dst, src, dst_copy, a=1): self._ok(self.L.mi355_engine_mul_copy(self.h, dst, src, dst_copy, u32_arg("factor", a)))
 
     def is_equal(self, lhs, rhs):
         out = C.c_int(0)
@@ -251,6 +264,7 @@ class Engine:
 
     def time_square_mul(self, reg, iters, a=1, sub=0, per_kernel=False):
         """(total_ms, {kernel: avg_ms}) for `iters` back-to-back squarings, HIP events on the engine stream."""
+        a, sub = u32_arg("factor", a), u32_arg("sub", sub)
         total = C.c_double(0)
         k = self.L.mi355_engine_kernel_count(self.h)
         ks = (C.c_double * k)()
