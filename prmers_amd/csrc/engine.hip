@@ -135,42 +135,7 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
       HIPCHK(hipStreamSynchronize(stream_));
       dp_.F0f = f0_; dp_.F0i = f0_ + nt; dp_.FBf = f0_ + 2 * nt; dp_.FBi = f0_ + 2 * nt + pl_.M2;
     }
-#if defined(MI355_EXPERIMENTAL)
-    {
-      // back sweep + next front sweep in one launch for runs of squarings (kernels_v2.hip k31_cols): opt-in, MI355_CHAIN=1
-      const char* ch = std::getenv("MI355_CHAIN");
-      if (v2cols_ && ch && ch[0] == '1' && v2_chain_supported(dp_)) {
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&xchain_), pl_.runs() * 8 + 64));
-        HIPCHK(hipMemsetAsync(xchain_, 0, pl_.runs() * 8 + 64, stream_));
-      }
-    }
-    if (v2rows_ && v2cols_) chain_tiles_ = v3_chain_tiles(dp_, device_);
-    if (chain_tiles_) {
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&chain_x_), size_t(chain_tiles_) * 256 * 8));
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&chain_flags_), (size_t(chain_tiles_) + 1) * 4));
-      HIPCHK(hipMemsetAsync(chain_flags_, 0, (size_t(chain_tiles_) + 1) * 4, stream_));
-    }
-#endif
   }
-
-#if defined(MI355_EXPERIMENTAL)
-  {
-    // transforms whose tiles are all resident at once: one cooperative launch per run of squarings instead of three launches per
-    // squaring (kernels.hip k_coop).  Opt-in (MI355_COOP=1): measured slower on MI355X -- 0.044 ms per squaring at C2 inside one launch
-    // against 0.031 ms for three launches; a grid barrier costs what a kernel boundary costs (2.9 vs 2.8 us, tools/microbench_gridsync.hip),
-    // the hand-over data has to bypass the XCD's L2, and a cooperative launch itself takes 21.6 us.
-    const char* co = std::getenv("MI355_COOP");
-    if (!v2rows_ && !v2cols_ && !pl_.split5 && co && co[0] == '1') coop_groups_ = coop_groups(dp_, device_);
-    if (coop_groups_) {
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&coop_flags_), (size_t(coop_groups_) + 64) * 4));
-      HIPCHK(hipMemsetAsync(coop_flags_, 0, (size_t(coop_groups_) + 64) * 4, stream_));
-      const char* cf = std::getenv("MI355_COOP_FAULT");   // test hook: work-group 0 skips its barriers (tests/test_gpu_coop.py)
-      coop_fault_ = (cf && cf[0] == '1') ? 1u : 0u;
-      const char* cb = std::getenv("MI355_COOP_BATCH");
-      if (cb && std::atoi(cb) > 1) coop_batch_ = size_t(std::atoi(cb));
-    }
-  }
-#endif
 
   // digit widths in natural order (ibdwt.h:127-132), s_j = p*j mod n kept incrementally
   width_.resize(pl_.n);
@@ -194,14 +159,6 @@ Engine::~Engine() {
   if (f0_) (void)hipFree(f0_);
   if (split_) (void)hipFree(split_);
   if (canon_) (void)hipFree(canon_);
-#if defined(MI355_EXPERIMENTAL)
-  if (xchain_) (void)hipFree(xchain_);
-  if (chain_x_) (void)hipFree(chain_x_);
-  if (chain_flags_) (void)hipFree(chain_flags_);
-#endif
-#if defined(MI355_EXPERIMENTAL)
-  if (coop_flags_) (void)hipFree(coop_flags_);
-#endif
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -216,58 +173,7 @@ void Engine::need_digits(size_t r, const char* op) const {
 void Engine::sync() {
   HIPCHK(hipSetDevice(device_));
   HIPCHK(hipStreamSynchronize(stream_));
-  coop_check();
-  chain_check();
 }
-
-#if defined(MI355_EXPERIMENTAL)
-// The fused back + front launches of square_mul_n hand carry words from tile to tile inside the launch; a wait that timed out raised the
-// error word and left garbage behind: nothing is read out of the engine after that.
-void Engine::chain_check() {
-  if (xchain_failed_) throw std::runtime_error("chained squaring kernel: a carry hand-over timed out earlier; the engine's registers are not valid");
-  if (xchain_used_) {
-    uint32_t err = 0;
-    HIPCHK(hipMemcpyAsync(&err, xchain_err(), 4, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    xchain_used_ = false;
-    if (err) { xchain_failed_ = true; throw std::runtime_error("chained squaring kernel: carry hand-over timed out"); }
-  }
-  if (chain_failed_) throw std::runtime_error("chained squaring kernel: a carry hand-over timed out earlier; the engine's registers are not valid");
-  if (!chain_used_) return;
-  uint32_t err = 0;
-  HIPCHK(hipMemcpyAsync(&err, chain_flags_ + chain_tiles_, 4, hipMemcpyDeviceToHost, stream_));
-  HIPCHK(hipStreamSynchronize(stream_));
-  chain_used_ = false;
-  if (err) { chain_failed_ = true; throw std::runtime_error("chained squaring kernel: carry hand-over timed out (tiles not co-resident?)"); }
-}
-#endif
-
-#if defined(MI355_EXPERIMENTAL)
-// The grid barrier of k_coop gives up after 0.2 s and raises the error word; the results of that launch are garbage.
-void Engine::coop_check() {
-  if (coop_failed_) throw std::runtime_error("cooperative squaring kernel: a grid barrier timed out earlier; the engine's registers are not valid");
-  if (!coop_used_) return;
-  uint32_t err = 0;
-  HIPCHK(hipMemcpyAsync(&err, coop_flags_ + coop_groups_, 4, hipMemcpyDeviceToHost, stream_));
-  HIPCHK(hipStreamSynchronize(stream_));
-  coop_used_ = false;
-  if (err) { coop_failed_ = true; throw std::runtime_error("cooperative squaring kernel: grid barrier timed out (work-groups not co-resident?)"); }
-}
-
-void Engine::coop_launch(size_t r, uint32_t a, size_t count, uint32_t sub_next) {
-  if (coop_failed_) coop_check();
-  while (count) {
-    const uint32_t c = uint32_t(std::min<size_t>(count, 1u << 20));
-    HIPCHK(launch_coop(dp_, coop_groups_, digits(r), cbuf(r), pending_carry_[r] != 0, work(), a, pending_sub_[r], sub_next, c, coop_flags_,
-                       coop_flags_ + coop_groups_, coop_epoch_, coop_fault_, stream_));
-    coop_epoch_ += 3 * c - 1;
-    pending_carry_[r] = 1;
-    pending_sub_[r] = sub_next;
-    coop_used_ = true;
-    count -= c;
-  }
-}
-#endif
 
 void Engine::normalize(size_t r) {
   if (kind_[r] != kDigits) return;
@@ -357,8 +263,6 @@ void Engine::write_values(size_t dst, const std::vector<uint32_t>& natural) {
 uint32_t* Engine::canon_digits(size_t r, int slot) {
   need_digits(r, "get");
   HIPCHK(hipSetDevice(device_));
-  coop_check();   // nothing is read out of an engine whose one-launch kernel gave up at a grid barrier
-  chain_check();
   const size_t sw = canon_scratch_words(dp_);
   if (!canon_) {
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&canon_), (sw + 2 * pl_.n) * 4));
@@ -398,8 +302,6 @@ void Engine::read_values_host(size_t src, std::vector<uint64_t>& v) {
   need_digits(src, "get");
   stage_.resize(pl_.n);
   HIPCHK(hipSetDevice(device_));
-  coop_check();
-  chain_check();
   normalize(src);
   HIPCHK(hipStreamSynchronize(stream_));
   HIPCHK(hipMemcpy(stage_.data(), digits(src), pl_.n * 4, hipMemcpyDeviceToHost));
@@ -567,13 +469,6 @@ void Engine::copy(size_t dst, size_t src) {
 void Engine::square_chain(size_t r, uint32_t a, hipEvent_t* ev) {
   if (a > pl_.a_fast) { square_chain(r, 1, ev); scale(r, a); return; }   // beyond the fused carry's bound (plan.hpp fused_factor_limit)
   if (ev) HIPCHK(hipEventRecord(ev[0], stream_));
-#if defined(MI355_EXPERIMENTAL)
-  if (coop_groups_ && pending_sub_[r] < (1u << 30)) {   // one launch: the whole squaring sits in slot 0
-    coop_launch(r, a, 1, 0);
-    if (ev) for (int k = 1; k <= 4; ++k) HIPCHK(hipEventRecord(ev[k], stream_));
-    return;
-  }
-#endif
   run_front(r);
   if (ev) HIPCHK(hipEventRecord(ev[1], stream_));
   run_middle(work(), nullptr, work(), 0, 0);
@@ -609,45 +504,6 @@ void Engine::square_mul_n(size_t r, uint32_t a, size_t count, uint32_t sub) {
   if (a == 0) throw std::runtime_error("square_mul_n: factor must be >= 1");
   if (count == 0) return;
   HIPCHK(hipSetDevice(device_));
-  if (a > pl_.a_fast) { for (size_t i = 0; i < count; ++i) { square_chain(r, a, nullptr); if (sub) sub_u32(r, sub); } return; }
-#if defined(MI355_EXPERIMENTAL)
-  if (coop_groups_ && pending_sub_[r] < (1u << 30) && sub < (1u << 30)) { coop_launch(r, a, count, sub); return; }
-#endif
-#if defined(MI355_EXPERIMENTAL)
-  if (xchain_ && a == 1 && count >= 2 && sub < (1u << 30) && !xchain_failed_) {
-    // front | rows | [back + front | rows] x (count - 1) | back: the back sweep of a squaring and the front sweep of the next one are ONE
-    // launch (kernels_v2.hip k31_cols); same digits as the loop below
-    run_front(r);                                      // consumes pending carries / subtraction
-    for (size_t i = 0; i + 1 < count; ++i) {
-      run_middle(work(), nullptr, work(), 0, 0);
-      HIPCHK(v2_launch_backfront(dp_, work(), sub, xchain_, xchain_err(), xchain_tag_, stream_));
-      xchain_tag_ = xchain_tag_ % 4095u + 1u;          // 1 .. 4095: never the tag of the launch before, never the zero of a fresh buffer
-      xchain_used_ = true;
-    }
-    run_middle(work(), nullptr, work(), 0, 0);
-    run_back(r, a);
-    if (sub) sub_u32(r, sub);
-    return;
-  }
-  if (chain_tiles_ && count >= 2 && sub < (1u << 30) && !chain_failed_) {
-    // front | rows | [back + front | rows] x (count - 1) | back: the back sweep of a squaring and the front sweep of the next one are ONE
-    // launch on the small shapes (kernels_v3.hip k31_cols256_planes); same digits as the loop below
-    run_front(r);                                      // consumes pending carries / subtraction
-    for (size_t i = 0; i + 1 < count; ++i) {
-      run_middle(work(), nullptr, work(), 0, 0);
-      HIPCHK(v3_launch_backfront(dp_, work(), a, sub, chain_x_, chain_flags_, ++chain_epoch_, stream_));
-      chain_used_ = true;
-      if (chain_epoch_ >= 0x7fff0000u) {               // the flags compare epochs in 31 bits: start over
-        HIPCHK(hipMemsetAsync(chain_flags_, 0, size_t(chain_tiles_) * 4, stream_));
-        chain_epoch_ = 0;
-      }
-    }
-    run_middle(work(), nullptr, work(), 0, 0);
-    run_back(r, a);
-    if (sub) sub_u32(r, sub);
-    return;
-  }
-#endif
   for (size_t i = 0; i < count; ++i) { square_chain(r, a, nullptr); if (sub) sub_u32(r, sub); }
 }
 
@@ -825,8 +681,6 @@ void Engine::get_data(size_t src, void* data, size_t size) {
   check_reg(src);
   if (size != register_data_size()) throw std::runtime_error("get_data: size mismatch");
   HIPCHK(hipSetDevice(device_));
-  coop_check();
-  chain_check();
   normalize(src);
   HIPCHK(hipStreamSynchronize(stream_));
   HIPCHK(hipMemcpy(data, slot_[src], reg_bytes_, hipMemcpyDeviceToHost));
@@ -889,22 +743,7 @@ void Engine::time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, d
   const hipEvent_t e0 = pool.make(), e1 = pool.make();
   HIPCHK(hipStreamSynchronize(stream_));
   HIPCHK(hipEventRecord(e0, stream_));
-#if defined(MI355_EXPERIMENTAL)
-  if (coop_groups_ && coop_batch_ > 1) {   // MI355_COOP_BATCH squarings per launch (what a PRP / LL loop between two checks does)
-    for (size_t done = 0; done < iters;) { const size_t c = std::min(coop_batch_, iters - done); square_mul_n(r, a, c, sub); done += c; }
-  } else
-#endif
-  {
-    bool as_run = false;   // the run of squarings as the callers issue it (experimental build: back + front in one launch where that is on)
-#if defined(MI355_EXPERIMENTAL)
-    as_run = xchain_ != nullptr || chain_tiles_ != 0;
-#endif
-    if (as_run) square_mul_n(r, a, iters, sub);
-    else for (size_t i = 0; i < iters; ++i) {
-      square_chain(r, a, nullptr);
-      if (sub) sub_u32(r, sub);
-    }
-  }
+  square_mul_n(r, a, iters, sub);
   HIPCHK(hipEventRecord(e1, stream_));
   HIPCHK(hipEventSynchronize(e1));
   float ms = 0;
@@ -943,9 +782,8 @@ void Engine::time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, d
       }
     // which of the five slots hold a kernel on this path
     const bool fix_now = !v2cols_ && pl_.C < 2;                        // k_carry_fix right after the back sweep
-    const bool coop = coop_on();                                       // (experimental build) one launch (slot 0) for the whole squaring
     const bool sub_kernel = sub != 0;                                  // k_sub_small
-    const bool launched[5] = {true, !coop, !coop, fix_now && !coop, sub_kernel};
+    const bool launched[5] = {true, true, true, fix_now, sub_kernel};
     for (size_t k = 0; k < 5 && k < kcount; ++k) kernel_ms[k] = launched[k] ? std::max(0.0, kernel_ms[k] - overhead) : -1.0;
     if (kcount > 5) kernel_ms[5] = overhead;
   }

@@ -19,14 +19,11 @@ constexpr unsigned shift64(unsigned e) { return (LOG2_W64 * e) % 192; }   // ome
 //     sub a canonical subtrahend, and e0 only ever meets the canonical e1); outputs 0, 2's partner 6, 4 and 7 stay canonical;
 //   2 every output but 7 may be un-folded (round 4: a0, c0 and e0 are lazy sums as well; each of them meets a canonical partner in the
 //     next level: a0 with a2, c0 with c1, e0 with e1).
-// Three instructions fewer per transform at LAZY = 2, one at LAZY = 1 (GF_R3_FORMS restores the round-3 network for A/B builds).
+// Three instructions fewer per transform at LAZY = 2, one at LAZY = 1; the round-3 network without the a0 / e0 lazy sums was 0.6 % slower at
+// C3 (profiles/r04_ab_field_forms.md).
 template <bool INV, int LAZY = 0>
 GF_HD void dft8(uint64_t (&x)[8]) {
-#if defined(GF_R3_FORMS)
-  constexpr bool LZ_A0 = false, LZ_E0 = false;
-#else
   constexpr bool LZ_A0 = (LAZY >= 2), LZ_E0 = (LAZY >= 1);
-#endif
   const uint64_t a0 = LZ_A0 ? add_lazy(x[0], x[4]) : add(x[0], x[4]);
   const uint64_t a1 = add(x[1], x[5]), a2 = add(x[2], x[6]), a3 = add(x[3], x[7]);
   uint64_t b0 = sub(x[0], x[4]), b1, b2, b3;

@@ -75,14 +75,6 @@ hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_
 hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, uint32_t sub, hipStream_t s);
 hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s);
 hipError_t launch_carry_fix(const DevPlan& pl, uint32_t* digits, const uint64_t* cbuf, hipStream_t s);
-#if defined(MI355_EXPERIMENTAL)   // libmi355_engine_exp.so only (make exp): measured slower than three launches, DESIGN.md 5.2c
-// `count` squarings in ONE cooperative launch (kernels.hip k_coop): grid size for this plan, or 0 when the plan is not served
-uint32_t coop_groups(const DevPlan& pl, int device);
-// flags: `groups` barrier words, err: error word (both device-visible, zero at first use); epoch0: barriers passed so far on these flags
-// (each squaring passes 3, the last one of a launch 2); sub: subtracted before the first squaring, sub_next before each later one
-hipError_t launch_coop(const DevPlan& pl, uint32_t groups, uint32_t* digits, uint64_t* cbuf, bool carry_in, uint64_t* W, uint32_t a, uint32_t sub, uint32_t sub_next,
-                       uint32_t count, uint32_t* flags, uint32_t* err, uint32_t epoch0, uint32_t fault, hipStream_t s);   // fault: test hook, see CoopArgs
-#endif
 // columns of 5 L1 pairs that do not fit LDS (n = 5 * 2^26): the radix-5 stage through a second work buffer U (8 n bytes), C = 1
 hipError_t configure_split(const DevPlan& pl);
 hipError_t launch_front_split(const DevPlan& pl, const uint32_t* digits, uint64_t* U, uint64_t* W, hipStream_t s);
@@ -106,18 +98,6 @@ hipError_t v2_build_fourstep(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, ui
 hipError_t v2_launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, uint32_t sub, hipStream_t s);
 hipError_t v2_launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint32_t sub, uint64_t* W, hipStream_t s);
 hipError_t v2_launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, uint64_t scale, hipStream_t s);
-#if defined(MI355_EXPERIMENTAL)
-// runs of squarings on the radix-8 column shapes (kernels_v2.hip k31_cols): the back sweep of one squaring and the front sweep of the next in one
-// launch (a = 1).  xbuf: one hand-over word per run (tiles x M1), err: the error word a timed-out wait raises, tag: 1 .. 4095, different from
-// the previous launch's on the same xbuf
-bool v2_chain_supported(const DevPlan& pl);
-hipError_t v2_launch_backfront(const DevPlan& pl, uint64_t* W, uint32_t sub, uint64_t* xbuf, uint32_t* err, uint32_t tag, hipStream_t s);
-// runs of squarings on the small shapes (kernels_v3.hip): the back sweep of one squaring and the front sweep of the next in one launch.
-// v3_chain_tiles: tiles of such a launch (all resident at once on `device`), 0 where the plan is not served.  xbuf: tiles x 256 carry
-// words, flags: tiles + 1 words (the last one is the error word a timed-out wait raises), epoch: larger than any used before on these flags
-uint32_t v3_chain_tiles(const DevPlan& pl, int device);
-hipError_t v3_launch_backfront(const DevPlan& pl, uint64_t* W, uint32_t a, uint32_t sub, uint64_t* xbuf, uint32_t* flags, uint32_t epoch, hipStream_t s);
-#endif
 #if defined(MI355_PROBE)
 size_t v2_lds_bytes();
 // one launch of sweep `kind` (0 front, 1 rows, 2 back) over grid_mult x the normal grid with extra_lds bytes of padding LDS

@@ -20,35 +20,15 @@ struct alignas(16) P2 { uint64_t a, b; };
 // ({0-3, 12-15, 20-27}, ...) on 64 banks (MI355X_MICROARCH.md, LDS).  Round 4: i ^ ((i >> 3) & 15) is conflict-free for every one of the
 // row kernel's six orders (census: tools/lds_census.py; the round-1 skew i + i / 8 left the consecutive-lane loads 2-way conflicted -- the 18 %
 // of SQ_LDS_BANK_CONFLICT over SQ_LDS_IDX_ACTIVE that VERDICT r03 lists) and needs no padding: 64 KiB instead of 72 per group.
-// -DMI355_LDS_ADD3 restores the old skew for A/B builds.
-#if defined(MI355_LDS_ADD3)
-__device__ __forceinline__ uint32_t phys(uint32_t i) { return i + (i >> 3); }
-constexpr uint32_t kLdsSlots = 4096 + 512;
-#else
+// The old skew lost to this map in a same-box A/B at C3, C4 and five other sizes (profiles/r04_ab_lds_map.txt).
 __device__ __forceinline__ uint32_t phys(uint32_t i) { return i ^ ((i >> 3) & 15u); }
 constexpr uint32_t kLdsSlots = 4096;
-#endif
 constexpr uint32_t kLdsBytes = kLdsSlots * 16;
 
-// Work-buffer accesses of the sweeps.  -DMI355_NT=<bits> (A/B builds only): bit 0 stores, bit 1 loads with the non-temporal hint (streamed
-// through L2: a sweep never re-reads what it wrote and the next launch reads it from the memory side anyway).
-typedef uint64_t u64x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void w_store(P2* p, P2 v) {
-#if defined(MI355_NT) && (MI355_NT & 1)
-  u64x2_t q; q.x = v.a; q.y = v.b;
-  __builtin_nontemporal_store(q, reinterpret_cast<u64x2_t*>(p));
-#else
-  *p = v;
-#endif
-}
-__device__ __forceinline__ P2 w_load(const P2* p) {
-#if defined(MI355_NT) && (MI355_NT & 2)
-  const u64x2_t q = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t*>(p));
-  return {q.x, q.y};
-#else
-  return *p;
-#endif
-}
+// Work-buffer accesses of the sweeps: plain loads and stores.  The non-temporal hint on them was 3.5-4.5 % slower at C3 and up to 60 %
+// at n = 2^24, where non-temporal stores keep the L2 from merging the tiles' pieces of a line (profiles/r04_ab_nontemporal.txt).
+__device__ __forceinline__ void w_store(P2* p, P2 v) { *p = v; }
+__device__ __forceinline__ P2 w_load(const P2* p) { return *p; }
 
 __device__ __forceinline__ P2 p2_mul(P2 x, uint64_t w) { return {gf::mul(x.a, w), gf::mul(x.b, w)}; }
 
@@ -230,10 +210,5 @@ hipError_t v3_launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64
 hipError_t v3_launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint32_t sub, uint64_t* W, hipStream_t s);
 hipError_t v3_launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, uint64_t scale, hipStream_t s);
 hipError_t v3_launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
-#if defined(MI355_EXPERIMENTAL)
-// back sweep of one squaring + front sweep of the next in one launch (kernels_v3.hip k31_cols256_planes): tiles served (0: not), launch
-uint32_t v3_chain_tiles(const DevPlan& pl, int device);
-hipError_t v3_launch_backfront(const DevPlan& pl, uint64_t* W, uint32_t a, uint32_t sub, uint64_t* xbuf, uint32_t* flags, uint32_t epoch, hipStream_t s);
-#endif
 
 }  // namespace mi355

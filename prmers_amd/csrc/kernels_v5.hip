@@ -45,11 +45,7 @@ static_assert((Shape<1>::PU % 5) == 1 && (Shape<1>::PU % 512) == 0 && (Shape<1>:
 // (3 + 3 + 2 + 2) is not placed next to a resident one for up to 17 us after a slot has become free (profiles/r03_probe_c4.md: 44 % of
 // the dispatches of a launch, a CU then runs one group for half of its time); twelve are placed within 2 us like the 512-thread groups.
 constexpr uint32_t kLaunchThreads = 768;
-#if defined(MI355_LDS_ADD3)
-constexpr uint32_t kPlaneWords = kTile + kTile / 32 + 8;
-#else
 constexpr uint32_t kPlaneWords = kTile;
-#endif
 // the exchange plane, then a copy of the omega_1280 table (10 KiB): the seams of this shape are table multiplications and their roots
 // come out of LDS (~100 cycles) instead of L2 (several hundred, exposed at every stage)
 constexpr uint32_t lds_bytes(uint32_t m1) { return (kPlaneWords + m1) * 8; }
@@ -57,15 +53,11 @@ constexpr uint32_t lds_bytes(uint32_t m1) { return (kPlaneWords + m1) * 8; }
 // the lane groups of 64-bit accesses (stores: four groups of 16 lanes on 32 banks, loads: two groups of 32 lanes on 64 banks;
 // MI355X_MICROARCH.md, LDS) in both directions of that exchange.  The single skew i + i / 32 of rounds 2-3 left 44 % of the LDS cycles of
 // these kernels to bank conflicts (SQ_LDS_BANK_CONFLICT 4.03 M of SQ_LDS_IDX_ACTIVE 9.07 M per launch at C4: the last exchange of the front
-// and the first of the back were 4-way conflicted).  -DMI355_LDS_ADD3 restores it for A/B builds.
+// and the first of the back were 4-way conflicted; same-box A/B of the two: profiles/r04_ab_lds_map.txt).
 template <int S>
 __device__ __forceinline__ uint32_t ph(uint32_t i) {   // S < 0: identity
-#if defined(MI355_LDS_ADD3)
-  return i + (i >> 5);
-#else
   if constexpr (S < 0) return i;
   else return i ^ ((i >> S) & 31u);
-#endif
 }
 template <uint32_t M1>
 __device__ __forceinline__ const uint64_t* stage_roots(const DevPlan& pl, uint64_t* X) {

@@ -180,7 +180,7 @@ class Engine:
     def mul_add(self, dst, mul_src, add_src, a=1): self._ok(self.L.mi355_engine_mul_add(self.h, dst, mul_src, add_src, u32_arg("factor", a)))
     def square_mul_copy(self, src, dst_copy, a=1): self._ok(self.L.mi355_engine_square_mul_copy(self.h, src, dst_copy, u32_arg("factor", a)))
     def square_mul_n(self, src, count, a=1, sub=0):
-        """count x { src = src^2 * a; src -= sub }: one cooperative launch on the small transforms."""
+        """count x { src = src^2 * a; src -= sub } in one engine call."""
         self._ok(self.L.mi355_engine_square_mul_n(self.h, src, u32_arg("factor", a), count, u32_arg("sub", sub)))
     def mul_copy(self, dst, src, dst_copy, a=1): self._ok(self.L.mi355_engine_mul_copy(self.h, dst, src, dst_copy, u32_arg("factor", a)))
 

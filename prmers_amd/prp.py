@@ -304,7 +304,7 @@ def run_prp_or_ll(eng, p, mode="prp", gerbicz=True, erroriter=0, checklevel=0, m
             log("Interrupted, state saved at iteration %d j=%d" % (it, j))
             break
         # the run of plain iterations up to the next event (Gerbicz-Li boundary, injected error, checkpoint, stop poll) goes to the
-        # engine as ONE call where it offers square_mul_n (one cooperative launch on the small transforms); `it` / `j` then name the
+        # engine as ONE call where it offers square_mul_n (no per-iteration trip through the FFI); `it` / `j` then name the
         # last iteration of the run, as they would after that many turns of the reference's loop (RunPrpOrLlMarin.cpp:338-409)
         r = 1
         if batched:

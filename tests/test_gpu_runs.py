@@ -1,8 +1,7 @@
 """Runs of squarings in one engine call (Engine::square_mul_n / mi355_engine_square_mul_n: what a PRP or Lucas-Lehmer loop issues between
 two checks, RunPrpOrLlMarin.cpp:338-409) on the product library: the same digits as the loop of square_mul / sub calls, against the oracle,
 the reference-held residues and Python integers, on the small generic plans, the register-resident kernels and the split sweeps.
-(The one-cooperative-launch form of the small transforms is not in the product library: it was measured slower; its own
-checks are tools/exp_coop_check.py, run against libmi355_engine_exp.so.)  Needs a real MI355X."""
+Needs a real MI355X."""
 import json
 import os
 
@@ -25,7 +24,7 @@ def Engine(*a, **k):
 RUN_CASES = [(127, "m2=2,c=2"), (521, "m2=4,c=2"), (1801, "m2=8,c=4"), (3997, "m2=16,c=4"), (9941, "m2=64,c=8"), (9941, "m2=4,c=4"),
              (13967, None), (44497, None), (102701, None), (400063, "m2=64,c=4"), (1001, "m2=2,c=2"), (2976221, None), (9815459, None),
              (19000013, None),
-             # columns of 256 x 4 on the radix-4 set, 2 .. 16 tiles (the experimental library runs these as back + front in one launch)
+             # columns of 256 x 4 on the radix-4 set, 2 .. 16 tiles
              (86243, "m2=8,c=4"), (132049, "m2=16,c=4"), (756839, "m2=64,c=4")]
 
 

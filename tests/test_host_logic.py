@@ -100,10 +100,19 @@ def test_plan_weight_tables_and_digit_info_words():
     assert "m1=1280:m2=8:c=4 digits=20480 di_checked=20480" in out and "m1=2560:m2=8:c=2 digits=40960 di_checked=40960" in out   # radix-5 columns
 
 
-def test_product_library_has_no_experimental_code_and_the_experiments_still_build():
-    """The experiments that did not make the product (cooperative one-launch squaring, back + front in one launch) live behind
-    -DMI355_EXPERIMENTAL: the product library exports and contains nothing of them, and their sources still compile for gfx950 (host and device passes, -fsyntax-only; `make -C prmers_amd/csrc exp` builds the library)
-    (their parity checks run on a GPU box: tools/exp_coop_check.py)."""
+def test_product_library_and_sources_hold_no_rejected_experiments():
+    """The experiments that were measured and did not make the product (cooperative one-launch squaring, back + front in one launch;
+    DESIGN.md section 8) and the A/B build macros of rejected variants are gone: the library exports and contains nothing of them, and no
+    source of the library or header names their macros."""
+    for d in (CSRC, os.path.join(ROOT, "include")):
+        for dirpath, _, files in os.walk(d):
+            for f in files:
+                if not (f == "Makefile" or f.endswith((".hip", ".hpp", ".cpp", ".h"))):
+                    continue
+                path = os.path.join(dirpath, f)
+                text = open(path).read()
+                for macro in ("MI355_EXPERIMENTAL", "MI355_LDS_ADD3", "MI355_NT", "GF_R3_FORMS"):
+                    assert not re.search(r"\b%s\b" % macro, text), (path, macro)
     from prmers_amd import engine as E
     if not os.path.exists(E.LIB_PATH):
         pytest.skip("libmi355_engine.so not built")
@@ -112,13 +121,6 @@ def test_product_library_has_no_experimental_code_and_the_experiments_still_buil
     blob = open(E.LIB_PATH, "rb").read()
     for name in (b"k_coop", b"k31_cols", b"MI355_COOP", b"MI355_CHAIN"):
         assert name not in blob, name
-    csrc = os.path.join(ROOT, "prmers_amd", "csrc")
-    procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-DMI355_EXPERIMENTAL", "-fsyntax-only", "-Wno-unused-command-line-argument",
-                               os.path.join(csrc, f)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-             for f in ("kernels.hip", "kernels_v2.hip", "kernels_v3.hip", "engine.hip")]
-    for pr in procs:
-        out, _ = pr.communicate()
-        assert pr.returncode == 0, out[-2000:]
 
 
 def test_c_abi_exports_and_no_gpu_behaviour():
