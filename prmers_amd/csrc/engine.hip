@@ -14,6 +14,32 @@ namespace mi355 {
       throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " in " #expr); \
   } while (0)
 
+// launchers of the chosen column variant (the split sweeps are launched by run_front / run_back: they need the second buffer)
+static ColSweeps col_sweeps(ColKernels k) {
+  switch (k) {
+    case ColKernels::kRadix8R1: return v2_cols(1);
+    case ColKernels::kRadix8R2: return v2_cols(2);
+    case ColKernels::kRadix8R4: return v2_cols(4);
+    case ColKernels::kRadix4Pairs: return v3_cols(false);
+    case ColKernels::kRadix4Planes: return v3_cols(true);
+    case ColKernels::kRadix5: return v5_cols(false);
+    case ColKernels::kRadix5J1: return v5_cols(true);
+    case ColKernels::kSplit: return ColSweeps{};
+    default: return ColSweeps{launch_front, launch_back, launch_back_ext, nullptr};
+  }
+}
+static RowsFn row_sweep(RowKernels k) {
+  switch (k) {
+    case RowKernels::kRadix4Pairs: return v3_rows1024_pairs;
+    case RowKernels::kRadix4Planes: return v3_rows1024_planes;
+    case RowKernels::kRadix8: return v2_rows4096;
+    case RowKernels::kRadix8Wide: return v2_rows8192;
+    case RowKernels::kRows2048One: return v2_rows2048_one;
+    case RowKernels::kRows2048Two: return v2_rows2048_two;
+    default: return launch_middle;
+  }
+}
+
 template <class T>
 static const T* upload(unsigned char*& cursor, unsigned char* base, const std::vector<T>& v, std::vector<unsigned char>& host) {
   const size_t off = size_t(cursor - base);
@@ -46,7 +72,6 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
   for (size_t r = nregs_; r < nregs_ + 4; ++r) cb_spare_.push_back(cbuf_ + r * pl_.runs());
   kind_.assign(nregs_, kDigits);
   pending_carry_.assign(nregs_, 0);
-  pending_sub_.assign(nregs_, 0);
 
   // one allocation for all tables
   auto padded = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
@@ -97,9 +122,7 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device_));
     const uint32_t slots = 2u * uint32_t(prop.multiProcessorCount);
-    const char* bf = std::getenv("MI355_BOOST");           // boosted part of the last round in percent (default 50)
-    const uint32_t pct = bf ? uint32_t(std::atoi(bf)) : 50u;
-    auto from = [&](size_t grid) { return (!(dp_.tune & 4) && grid > slots) ? uint32_t(grid - size_t(slots) * pct / 100) : ~0u; };
+    auto from = [&](size_t grid) { return grid > slots ? uint32_t(grid - size_t(slots) * 50 / 100) : ~0u; };
     dp_.boost_rows = from(pl_.M2 == 2048 ? pl_.M1 / 2 : pl_.M1);   // (rows of 2048 go two to a tile on the register-resident row kernel)
     dp_.boost_tiles = from(pl_.tiles());
   }
@@ -108,33 +131,30 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
     HIPCHK(configure_split(dp_));
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&split_), reg_bytes_));
   }
-  {
-    // kernel set: the register-resident radix-8 kernels where the shape is served, else the generic
-    // set.  MI355_KERNELS=generic|v2rows|v2cols narrows it (A/B tests, debugging).
-    const char* ks = std::getenv("MI355_KERNELS");
-    const std::string sel = ks ? ks : "v2";
-    v2rows_ = (sel == "v2" || sel == "v2rows") && v2_rows_supported(dp_);
-    v2cols_ = (sel == "v2" || sel == "v2cols") && v2_cols_supported(dp_);
-    dp_.lab_u = 1; dp_.lab_v = pl_.r5; dp_.lab_red = 0;
-    if (v2cols_ && v5_cols_shape(dp_)) v5_pfa(dp_, &dp_.lab_u, &dp_.lab_v);   // radix-5 columns in prime-factor form: their own frequency labels
-    else if (!v2cols_ && pl_.r5 == 5 && !pl_.split5 && pl_.L1 > 1) {   // the generic radix-5 stage in prime-factor form (kernels.hip lds_radix5)
-      uint32_t u = 1; while ((pl_.L1 * u) % 5 != 1) ++u;
-      dp_.lab_u = pl_.L1 * u;   // L1 (L1^-1 mod 5); lab_v stays 5
-      dp_.lab_red = pl_.M1;     // lab_u blk + 5 rq <= 16 L1 + 5 (L1 - 1) < 5 M1: four conditional subtractions
-    }
-    {   // every exponent label + M1 k, k < M2, that a row kernel looks up lies inside the two-level root table (plan.hpp TWhi)
-      const uint64_t max_label = dp_.lab_red ? uint64_t(pl_.M1) - 1 : uint64_t(dp_.lab_u) * (pl_.r5 - 1) + uint64_t(dp_.lab_v) * (pl_.L1 - 1);
-      if (max_label + uint64_t(pl_.M1) * (pl_.M2 - 1) >= (uint64_t(pl_.TWhi.size()) << pl_.twh))
-        throw std::runtime_error("internal: column frequency labels beyond the root table");
-    }
-    if (v2rows_ || v2cols_) HIPCHK(v2_configure());
-    if (v2cols_) {   // four-step chain starts and ratios: built once on the device (2 x tiles x 512 + 2 x M2 words)
-      const size_t nt = pl_.tiles() * v2_threads_per_tile(dp_);
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&f0_), (2 * nt + 2 * size_t(pl_.M2)) * 8));
-      HIPCHK(v2_build_fourstep(dp_, f0_, f0_ + nt, f0_ + 2 * nt, f0_ + 2 * nt + pl_.M2, stream_));
-      HIPCHK(hipStreamSynchronize(stream_));
-      dp_.F0f = f0_; dp_.F0i = f0_ + nt; dp_.FBf = f0_ + 2 * nt; dp_.FBi = f0_ + 2 * nt + pl_.M2;
-    }
+  // kernel variants: those that serve the shape (plan.hpp), narrowed by MI355_KERNELS=generic|v2rows|v2cols (A/B tests, debugging)
+  kc_ = choose_kernels(pl_, std::getenv("MI355_KERNELS"));
+  cols_ = col_sweeps(kc_.cols);
+  rows_ = row_sweep(kc_.rows);
+  dp_.lab_u = 1; dp_.lab_v = pl_.r5; dp_.lab_red = 0;
+  if (kc_.cols == ColKernels::kRadix5 || kc_.cols == ColKernels::kRadix5J1) {   // radix-5 columns in prime-factor form: their own frequency labels
+    v5_pfa(kc_.cols == ColKernels::kRadix5J1, &dp_.lab_u, &dp_.lab_v);
+  } else if (kc_.cols == ColKernels::kGeneric && pl_.r5 == 5 && pl_.L1 > 1) {   // the generic radix-5 stage in prime-factor form (kernels.hip lds_radix5)
+    uint32_t u = 1; while ((pl_.L1 * u) % 5 != 1) ++u;
+    dp_.lab_u = pl_.L1 * u;   // L1 (L1^-1 mod 5); lab_v stays 5
+    dp_.lab_red = pl_.M1;     // lab_u blk + 5 rq <= 16 L1 + 5 (L1 - 1) < 5 M1: four conditional subtractions
+  }
+  {   // every exponent label + M1 k, k < M2, that a row kernel looks up lies inside the two-level root table (plan.hpp TWhi)
+    const uint64_t max_label = dp_.lab_red ? uint64_t(pl_.M1) - 1 : uint64_t(dp_.lab_u) * (pl_.r5 - 1) + uint64_t(dp_.lab_v) * (pl_.L1 - 1);
+    if (max_label + uint64_t(pl_.M1) * (pl_.M2 - 1) >= (uint64_t(pl_.TWhi.size()) << pl_.twh))
+      throw std::runtime_error("internal: column frequency labels beyond the root table");
+  }
+  if (kc_.resident_cols() || kc_.rows != RowKernels::kGeneric) HIPCHK(v2_configure());
+  if (kc_.resident_cols()) {   // four-step chain starts and ratios: built once on the device (2 x tiles x threads + 2 x M2 words)
+    const size_t nt = pl_.tiles() * threads_per_tile(kc_.cols);
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&f0_), (2 * nt + 2 * size_t(pl_.M2)) * 8));
+    HIPCHK(cols_.build_fourstep(dp_, f0_, f0_ + nt, f0_ + 2 * nt, f0_ + 2 * nt + pl_.M2, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    dp_.F0f = f0_; dp_.F0i = f0_ + nt; dp_.FBf = f0_ + 2 * nt; dp_.FBi = f0_ + 2 * nt + pl_.M2;
   }
 
   // digit widths in natural order (ibdwt.h:127-132), s_j = p*j mod n kept incrementally
@@ -181,10 +201,6 @@ void Engine::normalize(size_t r) {
     HIPCHK(launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
     pending_carry_[r] = 0;
   }
-  if (pending_sub_[r]) {
-    HIPCHK(launch_sub_small(dp_, digits(r), pending_sub_[r], stream_));
-    pending_sub_[r] = 0;
-  }
 }
 
 // Runs of two digits (C = 1): the run carries go into the digits at once.  A carry word has about w + log2(n) bits (the
@@ -204,45 +220,26 @@ void Engine::carry_fix_now(size_t r, int excess) {
   }
 }
 
+// digits(r) (+ its pending run carries) -> work(); digits(r) stay as they are.  (Runs of two digits never leave carries pending:
+// every operation that writes run carries on a plan with C < 2 takes them in at once, carry_fix_now.)
 void Engine::run_front(size_t r) {
-  if (pl_.split5) {   // columns beyond LDS (n = 5 2^26): radix-5 stage through the second work buffer
-    normalize(r);
-    HIPCHK(launch_front_split(dp_, digits(r), split_, work(), stream_));
-    return;
-  }
-  if (v2cols_) {
-    HIPCHK(v2_launch_front(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, pending_sub_[r], work(), stream_));
-  } else if (pl_.C >= 2 && kind_[r] == kDigits && !pending_sub_[r]) {
-    HIPCHK(launch_front(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, work(), stream_));   // does not modify digits(r)
-  } else {
-    normalize(r);
-    HIPCHK(launch_front(dp_, digits(r), nullptr, work(), stream_));
-  }
+  if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_front_split(dp_, digits(r), split_, work(), stream_));
+  else HIPCHK(cols_.front(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, work(), stream_));
 }
 
-void Engine::run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, uint32_t sub) {
-  if (v2rows_) HIPCHK(v2_launch_middle(dp_, in, y, out, mode, sub, stream_));
-  else HIPCHK(launch_middle(dp_, in, y, out, mode, sub, stream_));
+void Engine::run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode) {
+  HIPCHK(rows_(dp_, in, y, out, mode, stream_));
 }
 
-// work() -> digits(r) (+ run carries in cbuf(r)); the carry fix is deferred to the next front sweep
-// when that kernel can fold it in, otherwise applied right away
-void Engine::run_back(size_t r, uint32_t a) {
-  if (pl_.split5) {
-    HIPCHK(launch_back_split(dp_, work(), split_, digits(r), cbuf(r), a, stream_));
-    carry_fix_now(r);
-    pending_sub_[r] = 0;
-    return;
-  }
-  if (v2cols_) {
-    HIPCHK(v2_launch_back(dp_, work(), digits(r), cbuf(r), a, 1, stream_));
-    pending_carry_[r] = 1;
-  } else {
-    HIPCHK(launch_back(dp_, work(), digits(r), cbuf(r), a, stream_));
-    if (pl_.C >= 2) pending_carry_[r] = 1;   // the generic front folds the run carries in as well
-    else carry_fix_now(r);
-  }
-  pending_sub_[r] = 0;
+// work() -> digits(r) + run carries in cbuf(r): runs of 2C >= 4 digits leave them to the next sweep, which folds them in, runs of two
+// digits take them at once.  ev (nullable): two events recorded around that carry fix (time_square_mul)
+void Engine::run_back(size_t r, uint32_t a, hipEvent_t* ev) {
+  if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_back_split(dp_, work(), split_, digits(r), cbuf(r), a, stream_));
+  else HIPCHK(cols_.back(dp_, work(), digits(r), cbuf(r), a, stream_));
+  if (ev) HIPCHK(hipEventRecord(ev[0], stream_));
+  if (pl_.C >= 2) pending_carry_[r] = 1;
+  else carry_fix_now(r);
+  if (ev) HIPCHK(hipEventRecord(ev[1], stream_));
 }
 
 // ---- host digit I/O -------------------------------------------------------------------------
@@ -256,7 +253,7 @@ void Engine::write_values(size_t dst, const std::vector<uint32_t>& natural) {
   HIPCHK(canon_scatter(dp_, pl_.p, nat, digits(dst), stream_));
   HIPCHK(hipStreamSynchronize(stream_));
   kind_[dst] = kDigits;
-  pending_carry_[dst] = 0; pending_sub_[dst] = 0;
+  pending_carry_[dst] = 0;
 }
 
 // canonical digits of register r (strong carry with wrap-around, 2^p - 1 -> 0) in natural order, on the device
@@ -338,7 +335,7 @@ void Engine::set_u32(size_t dst, uint32_t value) {
   // engine_gpu.h:1444-1449; same value, but never an over-wide digit)
   if (value) HIPCHK(canon_set_small(dp_, pl_.p, digits(dst), value, stream_));
   kind_[dst] = kDigits;
-  pending_carry_[dst] = 0; pending_sub_[dst] = 0;
+  pending_carry_[dst] = 0;
 }
 
 void Engine::set_digits(size_t dst, const uint64_t* d, size_t count) {
@@ -455,14 +452,13 @@ void Engine::copy(size_t dst, size_t src) {
   check_reg(dst); check_reg(src);
   if (dst == src) return;
   HIPCHK(hipSetDevice(device_));
-  // the register is copied as it stands: digits with their pending run carries and small subtraction (no carry sweep),
+  // the register is copied as it stands: digits with their pending run carries (no carry sweep),
   // a multiplicand image whole
   const size_t bytes = (kind_[src] == kDigits) ? pl_.n * 4 : reg_bytes_;
   HIPCHK(hipMemcpyAsync(slot_[dst], slot_[src], bytes, hipMemcpyDeviceToDevice, stream_));
   if (kind_[src] == kDigits && pending_carry_[src])
     HIPCHK(hipMemcpyAsync(cbuf(dst), cbuf(src), pl_.runs() * 8, hipMemcpyDeviceToDevice, stream_));
   pending_carry_[dst] = (kind_[src] == kDigits) ? pending_carry_[src] : 0;
-  pending_sub_[dst] = (kind_[src] != kImage) ? pending_sub_[src] : 0;
   kind_[dst] = kind_[src];
 }
 
@@ -471,25 +467,9 @@ void Engine::square_chain(size_t r, uint32_t a, hipEvent_t* ev) {
   if (ev) HIPCHK(hipEventRecord(ev[0], stream_));
   run_front(r);
   if (ev) HIPCHK(hipEventRecord(ev[1], stream_));
-  run_middle(work(), nullptr, work(), 0, 0);
+  run_middle(work(), nullptr, work(), 0);
   if (ev) HIPCHK(hipEventRecord(ev[2], stream_));
-  if (v2cols_) {
-    HIPCHK(v2_launch_back(dp_, work(), digits(r), cbuf(r), a, 1, stream_));
-    if (ev) { HIPCHK(hipEventRecord(ev[3], stream_)); HIPCHK(hipEventRecord(ev[4], stream_)); }
-    pending_carry_[r] = 1;
-  } else if (pl_.split5) {
-    HIPCHK(launch_back_split(dp_, work(), split_, digits(r), cbuf(r), a, stream_));
-    if (ev) HIPCHK(hipEventRecord(ev[3], stream_));
-    carry_fix_now(r);
-    if (ev) HIPCHK(hipEventRecord(ev[4], stream_));
-  } else {
-    HIPCHK(launch_back(dp_, work(), digits(r), cbuf(r), a, stream_));
-    if (ev) HIPCHK(hipEventRecord(ev[3], stream_));
-    if (pl_.C >= 2) pending_carry_[r] = 1;
-    else carry_fix_now(r);
-    if (ev) HIPCHK(hipEventRecord(ev[4], stream_));
-  }
-  pending_sub_[r] = 0;
+  run_back(r, a, ev ? ev + 3 : nullptr);
 }
 
 void Engine::square_mul(size_t r, uint32_t a) {
@@ -512,9 +492,9 @@ void Engine::prepare(size_t dst, size_t src) {
   check_reg(dst);
   HIPCHK(hipSetDevice(device_));
   run_front(src);
-  run_middle(work(), nullptr, image(dst), 2, 0);
+  run_middle(work(), nullptr, image(dst), 2);
   kind_[dst] = kImage;
-  pending_carry_[dst] = 0; pending_sub_[dst] = 0;
+  pending_carry_[dst] = 0;
 }
 
 void Engine::mul(size_t dst, size_t src, uint32_t a) {
@@ -525,14 +505,14 @@ void Engine::mul(size_t dst, size_t src, uint32_t a) {
   if (a == 0) throw std::runtime_error("mul: factor must be >= 1");
   HIPCHK(hipSetDevice(device_));
   run_front(dst);
-  run_middle(work(), image(src), work(), 1, 0);
+  run_middle(work(), image(src), work(), 1);
   run_back(dst, a > pl_.a_fast ? 1u : a);
   if (a > pl_.a_fast) scale(dst, a);
 }
 
 // r = r x a, run-wise (kernels.hip k_scale): the factors above the plan's fused bound follow the operation with factor 1
 void Engine::scale(size_t r, uint32_t a) {
-  digits_ready(r);
+  need_digits(r, "scale");
   uint64_t* fresh = take_spare_cbuf();
   HIPCHK(launch_scale(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, digits(r), fresh, a, stream_));
   adopt_cbuf(r, fresh);
@@ -552,16 +532,11 @@ void Engine::adopt_cbuf(size_t r, uint64_t* fresh) {
   cb_[r] = fresh;
 }
 
-void Engine::digits_ready(size_t r) {
-  need_digits(r, "add/sub");
-  if (pending_sub_[r]) normalize(r);   // rare: a small subtraction not yet folded into a sweep
-}
-
 // sum -> s1 (and s2), difference -> d1 (and d2); -1: not wanted.  One run-wise sweep on pending-carry digits
 // (kernels.hip k_linear); the results leave their run carries pending for the next front sweep.
 void Engine::linear(long s1, long s2, long d1, long d2, size_t a, size_t b) {
   HIPCHK(hipSetDevice(device_));
-  digits_ready(a); digits_ready(b);
+  need_digits(a, "add/sub"); need_digits(b, "add/sub");
   const long outs[4] = {s1, s2, d1, d2};
   for (int i = 0; i < 4; ++i)
     if (outs[i] >= 0) { check_reg(size_t(outs[i])); for (int j = 0; j < i; ++j) if (outs[j] == outs[i]) throw std::runtime_error("addsub: output registers must differ"); }
@@ -580,7 +555,7 @@ void Engine::linear(long s1, long s2, long d1, long d2, size_t a, size_t b) {
     if (outs[i] >= 0) {
       const size_t r = size_t(outs[i]);
       adopt_cbuf(r, fresh[i]);
-      kind_[r] = kDigits; pending_carry_[r] = 1; pending_sub_[r] = 0;
+      kind_[r] = kDigits; pending_carry_[r] = 1;
       if (pl_.C < 2) carry_fix_now(r);   // runs of two digits: no deferred fold
     }
 }
@@ -611,14 +586,13 @@ void Engine::back_ext(size_t dst, uint32_t a, long copy_to, long add_src) {
   if (copy_to >= 0 && size_t(copy_to) != dst) { check_reg(size_t(copy_to)); x.digits2 = digits(size_t(copy_to)); x.cbuf2 = cbuf(size_t(copy_to)); }
   if (add_src >= 0) { x.add_digits = digits(size_t(add_src)); x.add_cbuf = pending_carry_[size_t(add_src)] ? cbuf(size_t(add_src)) : nullptr; }
   uint64_t* fresh = take_spare_cbuf();   // the addend may be dst itself: its pending carries are read while the new ones are written
-  if (v2cols_) HIPCHK(v2_launch_back_ext(dp_, work(), digits(dst), fresh, a, x, stream_));
-  else HIPCHK(launch_back_ext(dp_, work(), digits(dst), fresh, a, x, stream_));
+  HIPCHK(cols_.back_ext(dp_, work(), digits(dst), fresh, a, x, stream_));
   adopt_cbuf(dst, fresh);
   const size_t outs[2] = {dst, x.digits2 ? size_t(copy_to) : dst};
   for (int i = 0; i < (x.digits2 ? 2 : 1); ++i) {
     const size_t r = outs[i];
-    kind_[r] = kDigits; pending_sub_[r] = 0; pending_carry_[r] = 1;
-    if (!v2cols_ && pl_.C < 2) carry_fix_now(r);
+    kind_[r] = kDigits; pending_carry_[r] = 1;
+    if (pl_.C < 2) carry_fix_now(r);
   }
 }
 
@@ -626,9 +600,9 @@ void Engine::square_mul_copy(size_t src, size_t dst_copy, uint32_t a) {
   need_digits(src, "square_mul_copy"); check_reg(dst_copy);
   if (a == 0) throw std::runtime_error("square_mul_copy: factor must be >= 1");
   HIPCHK(hipSetDevice(device_));
-  if (dst_copy == src || pl_.split5 || a > pl_.a_fast) { square_mul(src, a); copy(dst_copy, src); return; }
+  if (dst_copy == src || !kc_.fused_back() || a > pl_.a_fast) { square_mul(src, a); copy(dst_copy, src); return; }
   run_front(src);
-  run_middle(work(), nullptr, work(), 0, 0);
+  run_middle(work(), nullptr, work(), 0);
   back_ext(src, a, long(dst_copy), -1);
 }
 
@@ -638,9 +612,9 @@ void Engine::mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t a) {
   if (dst == src || dst_copy == src) throw std::runtime_error("mul_copy: the multiplicand must differ from the outputs");
   if (a == 0) throw std::runtime_error("mul_copy: factor must be >= 1");
   HIPCHK(hipSetDevice(device_));
-  if (dst_copy == dst || pl_.split5 || a > pl_.a_fast) { mul(dst, src, a); copy(dst_copy, dst); return; }
+  if (dst_copy == dst || !kc_.fused_back() || a > pl_.a_fast) { mul(dst, src, a); copy(dst_copy, dst); return; }
   run_front(dst);
-  run_middle(work(), image(src), work(), 1, 0);
+  run_middle(work(), image(src), work(), 1);
   back_ext(dst, a, long(dst_copy), -1);
 }
 
@@ -650,16 +624,14 @@ void Engine::mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t a) {
   if (dst == mul_src) throw std::runtime_error("mul_add: dst and mul_src must differ");
   if (a == 0) throw std::runtime_error("mul_add: factor must be >= 1");
   HIPCHK(hipSetDevice(device_));
-  if (pl_.split5 || a > pl_.a_fast) {   // no fused sweep (split sweeps; factors above the fused bound): the base-class composition (engine.h:65-70)
+  if (!kc_.fused_back() || a > pl_.a_fast) {   // no fused sweep (split sweeps; factors above the fused bound): the base-class composition (engine.h:65-70)
     if (add_src == dst)
-      throw std::runtime_error(pl_.split5 ? "mul_add: add_src == dst needs the fused sweep, which this transform size does not have"
+      throw std::runtime_error(!kc_.fused_back() ? "mul_add: add_src == dst needs the fused sweep, which this transform size does not have"
                                           : "mul_add: add_src == dst needs the fused sweep, which takes factors up to the plan's fused bound only (mi355_engine.h)");
     mul(dst, mul_src, a); add(dst, add_src); return;
   }
-  if (add_src != dst) digits_ready(add_src);
-  else if (kind_[dst] != kDigits || pending_sub_[dst]) normalize(dst);
   run_front(dst);   // reads digits(dst) (+ pending carries) and leaves them in place
-  run_middle(work(), image(mul_src), work(), 1, 0);
+  run_middle(work(), image(mul_src), work(), 1);
   back_ext(dst, a, -1, long(add_src));
 }
 
@@ -671,7 +643,6 @@ void Engine::sub_u32(size_t r, uint32_t v) {
   // then go negative, which the unsigned back sweep reads as values near the field prime; the borrow below is exact for every register)
   // the small subtraction only touches the digit vector (cyclic borrow), so run carries that are still pending
   // for the next front sweep can stay pending: value = digits + carries - v either way
-  if (!(kind_[r] == kDigits && pl_.C >= 2 && !pending_sub_[r])) normalize(r);
   HIPCHK(launch_sub_small(dp_, digits(r), v, stream_));
 }
 
@@ -698,7 +669,7 @@ void Engine::set_data(size_t dst, const void* data, size_t size) {
   HIPCHK(hipStreamSynchronize(stream_));
   HIPCHK(hipMemcpy(slot_[dst], data, reg_bytes_, hipMemcpyHostToDevice));
   kind_[dst] = uint8_t(tag);
-  pending_carry_[dst] = 0; pending_sub_[dst] = 0;
+  pending_carry_[dst] = 0;
 }
 
 void Engine::get_checkpoint(void* data, size_t size) {
@@ -781,7 +752,7 @@ void Engine::time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, d
         kernel_ms[k] += double(t) / double(reps);
       }
     // which of the five slots hold a kernel on this path
-    const bool fix_now = !v2cols_ && pl_.C < 2;                        // k_carry_fix right after the back sweep
+    const bool fix_now = pl_.C < 2;                                    // k_carry_fix right after the back sweep
     const bool sub_kernel = sub != 0;                                  // k_sub_small
     const bool launched[5] = {true, true, true, fix_now, sub_kernel};
     for (size_t k = 0; k < 5 && k < kcount; ++k) kernel_ms[k] = launched[k] ? std::max(0.0, kernel_ms[k] - overhead) : -1.0;
@@ -792,8 +763,11 @@ void Engine::time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, d
 #if defined(MI355_PROBE)
 void Engine::probe(int kind, int grid_mult, int extra_lds, int boost_pct, size_t iters, double* avg_ms, uint64_t* tl, size_t tl_words) {
   HIPCHK(hipSetDevice(device_));
-  if (!v2cols_ || !v2rows_) throw std::runtime_error("probe: needs the register-resident kernels");
+  if (!kc_.resident_cols() || kc_.rows == RowKernels::kGeneric) throw std::runtime_error("probe: needs the register-resident kernels");
   if (grid_mult < 1 || kind < 0 || kind > 2) throw std::runtime_error("probe: bad arguments");
+  // probe launches: the rows of 4096, the columns of 1024 x 4 (v2) and of 1280 x 4 (v5)
+  const bool v5 = kind != 1 && kc_.cols == ColKernels::kRadix5;
+  if (kind == 1 ? kc_.rows != RowKernels::kRadix8 : !(v5 || kc_.cols == ColKernels::kRadix8R2)) HIPCHK(hipErrorNotSupported);
   const size_t base = (kind == 1) ? pl_.M1 : pl_.tiles(), grid = base * size_t(grid_mult);
   if (tl && tl_words < grid * 8) throw std::runtime_error("probe: timeline buffer too small");
   DevPlan d = dp_;
@@ -811,7 +785,9 @@ void Engine::probe(int kind, int grid_mult, int extra_lds, int boost_pct, size_t
   HIPCHK(hipMalloc(reinterpret_cast<void**>(&dtl), grid * 64));
   HIPCHK(hipMemset(dtl, 0, grid * 64));
   uint32_t* dout = reinterpret_cast<uint32_t*>(slot_[0]);   // register 0 is scratch here
-  auto launch = [&](const DevPlan& dd) { HIPCHK(v2_probe_launch(dd, kind, grid_mult, extra_lds, digits(1 % nregs_), kind == 2 ? cbuf(0) : nullptr, work(), dout, stream_)); };
+  auto launch = [&](const DevPlan& dd) {
+    HIPCHK((v5 ? v5_probe_launch : v2_probe_launch)(dd, kind, grid_mult, extra_lds, digits(1 % nregs_), kind == 2 ? cbuf(0) : nullptr, work(), dout, stream_));
+  };
   for (int w = 0; w < 3; ++w) launch(d);
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
@@ -827,7 +803,7 @@ void Engine::probe(int kind, int grid_mult, int extra_lds, int boost_pct, size_t
   if (tl) {
     d.probe = dtl;
     // (boost_pct < 0: the instrumented launch follows a launch of ANOTHER kernel, as in a squaring, instead of a launch of itself)
-    if (boost_pct < 0) { if (kind == 1) HIPCHK(v2_launch_back(dp_, work(), dout, cbuf(0), 1, 1, stream_)); else run_middle(work(), nullptr, work(), 0, 0); }
+    if (boost_pct < 0) { if (kind == 1) HIPCHK(cols_.back(dp_, work(), dout, cbuf(0), 1, stream_)); else run_middle(work(), nullptr, work(), 0); }
     launch(d);
     HIPCHK(hipStreamSynchronize(stream_));
     HIPCHK(hipMemcpy(tl, dtl, grid * 64, hipMemcpyDeviceToHost));

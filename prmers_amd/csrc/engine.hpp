@@ -72,7 +72,7 @@ class Engine {
 #endif
 
  private:
-  // kDigits: unweighted u32 digits (+ deferred run carries / subtraction); kImage: multiplicand
+  // kDigits: unweighted u32 digits (+ deferred run carries); kImage: multiplicand
   enum Kind : uint8_t { kDigits = 0, kImage = 1 };
   void check_reg(size_t r) const;
   void need_digits(size_t r, const char* op) const;
@@ -89,16 +89,15 @@ class Engine {
   uint64_t* cbuf(size_t r) { return cb_[r]; }
   uint64_t* take_spare_cbuf();                      // carry-word buffers are handed around like the register slots
   void adopt_cbuf(size_t r, uint64_t* fresh);       // r's pending carries are now in `fresh`; its old buffer becomes spare
-  void digits_ready(size_t r);                      // r as a digit register for a run-wise kernel (small subtraction applied)
   void linear(long s1, long s2, long d1, long d2, size_t a, size_t b);
   void back_ext(size_t dst, uint32_t a, long copy_to, long add_src);
-  void normalize(size_t r);          // apply deferred run carries / small subtraction
+  void normalize(size_t r);          // apply deferred run carries
   void carry_fix_now(size_t r, int excess = -1);   // run carries into the digits right away (plans with runs of two digits cannot defer
                                                    // them); excess: bits of a carry word above the first digit's width (-1: a <= 15)
   void scale(size_t r, uint32_t a);   // r x a, run-wise (k_scale): factors above pl_.a_fast
-  void run_front(size_t r);          // digits(r) -> work_, consuming pending state when the kernel can
-  void run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, uint32_t sub);
-  void run_back(size_t r, uint32_t a);
+  void run_front(size_t r);          // digits(r) (+ pending run carries) -> work_
+  void run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode);
+  void run_back(size_t r, uint32_t a, hipEvent_t* ev = nullptr);
 
   Plan pl_;
   DevPlan dp_{};
@@ -115,9 +114,10 @@ class Engine {
   uint64_t* f0_ = nullptr;   // four-step chain starts / ratios of the register-resident column kernels
   uint32_t* di_ = nullptr;   // digit-info words of the register-resident column kernels (plan.hpp DI)
   std::vector<uint8_t> kind_;
-  std::vector<uint8_t> pending_carry_;   // cbuf(r) not yet folded into the digits
-  std::vector<uint32_t> pending_sub_;    // small constant still to subtract (LL's -2)
-  bool v2rows_ = false, v2cols_ = false;
+  std::vector<uint8_t> pending_carry_;   // cbuf(r) not yet folded into the digits (never on plans with C < 2)
+  KernelChoice kc_;          // kernel variants of the sweeps (plan.hpp choose_kernels)
+  ColSweeps cols_{};         // launchers of kc_.cols (none for the split sweeps)
+  RowsFn rows_ = nullptr;    // launcher of kc_.rows
   std::vector<uint8_t> width_;   // natural order
   std::vector<uint32_t> stage_;  // host staging (one register of digits)
   uint32_t* canon_ = nullptr;    // device scratch of the canonicalisation: work arrays + two outputs of n digits (lazy)

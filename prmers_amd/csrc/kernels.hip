@@ -677,30 +677,6 @@ __global__ void __launch_bounds__(256) k_carry_fix(DevPlan pl, uint32_t* __restr
   }
 }
 
-// dst <- dst + src   (negate = 0)   or   dst <- dst - src + 2*Mp  (negate = 1; neg2_mp4, marin.cl:246-256)
-__global__ void __launch_bounds__(256) k_addsub(DevPlan pl, uint32_t* __restrict__ dst, const uint32_t* __restrict__ src,
-                                                uint64_t* __restrict__ cbuf, int negate) {
-  const uint32_t run = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t M1 = pl.M1, C = pl.C, NT = pl.M2 / C;
-  if (run >= M1 * NT) return;
-  const uint32_t T = run / M1, i1 = run - T * M1;
-  uint32_t* d = dst + (size_t(T) * M1 + i1) * C * 2;
-  const uint32_t* s = src + (size_t(T) * M1 + i1) * C * 2;
-  const uint32_t sa = pl.SA[i1];
-  uint64_t carry = 0;
-  for (uint32_t k = 0; k < 2 * C; ++k) {
-    uint32_t width; bool wrap;
-    digit_info(pl, sa, pl.SB[2 * (T * C) + k], width, wrap);
-    const uint64_t mask = (uint64_t(1) << width) - 1;
-    uint64_t sv = s[k];
-    if (negate) sv = 2 * mask - sv;   // src digits are < 2^width + small: keep it non-negative
-    const uint64_t v = uint64_t(d[k]) + sv + carry;
-    d[k] = uint32_t(v & mask);
-    carry = v >> width;
-  }
-  cbuf[size_t(T) * M1 + i1] = carry;
-}
-
 // digit j -> memory slot (Plan::pos)
 __device__ __forceinline__ size_t slot_of(const DevPlan& pl, uint32_t j) {
   const uint32_t i = j >> 1, b = j & 1;
@@ -735,9 +711,8 @@ __global__ void k_sub_small(DevPlan pl, uint32_t* __restrict__ digits, uint32_t 
 // ------------------------------- launch wrappers ---------------------------------------------
 
 static inline uint32_t block_for(size_t work) {
-  static const size_t cap = [] { const char* e = getenv("MI355_THREADS"); size_t v = e ? size_t(atoi(e)) : 512; return v < 64 ? 64 : (v > 1024 ? 1024 : v); }();
   size_t b = 64;
-  while (b < cap && b < work) b <<= 1;
+  while (b < 512 && b < work) b <<= 1;
   return uint32_t(b);
 }
 
@@ -745,12 +720,11 @@ static inline uint32_t block_for(size_t work) {
 // launch has no more work-groups than the chip has CUs (latency-bound: one plane per thread, lds_pow2_dft_planes)
 static inline uint32_t block_for_small(const DevPlan& pl, size_t pairs) {
   const size_t groups = size_t(pl.M1) * pl.M2 / (pairs ? pairs : 1);
-  const bool small = groups <= 256 && !(pl.tune & 8);   // at most one work-group per CU (with two per CU the classic form wins: n = 2^21, 0.066 vs 0.073 ms)
-  if (!small) return block_for(pairs / 4 ? pairs / 4 : 1);
+  // at most one work-group per CU (with two per CU the classic form wins: n = 2^21, 0.066 vs 0.073 ms; profiles/r02_ab_small_tiles.txt)
+  if (groups > 256) return block_for(pairs / 4 ? pairs / 4 : 1);
   // one pair per thread in the element-wise loops where the tile allows (C2: 0.0331 -> 0.0318 ms), else one plane per thread
-  const size_t want = (pl.tune & 16) ? pairs / 2 : pairs;
   size_t b = 64;
-  while (b < 1024 && b < want) b <<= 1;
+  while (b < 1024 && b < pairs) b <<= 1;
   return uint32_t(b);
 }
 
@@ -759,8 +733,8 @@ hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_
   hipLaunchKernelGGL(k_front, dim3(pl.M2 / pl.C), dim3(block_for_small(pl, tile)), tile * 16, s, pl, digits, cbuf_in, W);
   return hipGetLastError();
 }
-hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, uint32_t sub, hipStream_t s) {
-  hipLaunchKernelGGL(k_middle, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Y, Wout, mode, sub);
+hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s) {
+  hipLaunchKernelGGL(k_middle, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Y, Wout, mode, 0u);
   return hipGetLastError();
 }
 hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s) {
@@ -811,11 +785,6 @@ hipError_t launch_scale(const DevPlan& pl, const uint32_t* in, const uint64_t* c
 hipError_t launch_carry_fix(const DevPlan& pl, uint32_t* digits, const uint64_t* cbuf, hipStream_t s) {
   const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
   hipLaunchKernelGGL(k_carry_fix, dim3((runs + 255) / 256), dim3(256), 0, s, pl, digits, cbuf);
-  return hipGetLastError();
-}
-hipError_t launch_addsub(const DevPlan& pl, uint32_t* dst, const uint32_t* src, uint64_t* cbuf, int negate, hipStream_t s) {
-  const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
-  hipLaunchKernelGGL(k_addsub, dim3((runs + 255) / 256), dim3(256), 0, s, pl, dst, src, cbuf, negate);
   return hipGetLastError();
 }
 hipError_t launch_sub_small(const DevPlan& pl, uint32_t* digits, uint32_t a, hipStream_t s) {

@@ -26,7 +26,7 @@ struct DevPlan {
   uint64_t* probe;        // timeline probe (tools/probe.py, libmi355_engine_probe.so only): 8 words per work-group, or null
   uint32_t probe_mod;     // blockIdx.x is taken modulo this (launches of several rounds over the same tiles)
 #endif
-  uint32_t tune;   // MI355_TUNE bit 0: plain (not XCD-contiguous) tile order in the back sweep, for A/B runs; bit 2: no issue-priority boost of the last half round
+  uint32_t tune;   // MI355_TUNE (A/B runs), read by the kernels only: bit 0 plain (not XCD-contiguous) tile order in the back sweeps; bit 5 the other tile order in the front sweeps
 };
 
 #if defined(__HIPCC__)
@@ -66,42 +66,50 @@ struct LinArgs {
 hipError_t launch_linear(const DevPlan& pl, const LinArgs& la, hipStream_t s);
 // out = (in + its pending carries cin, nullable) x a, run-wise, carry-out words to cout (kernels.hip k_scale)
 hipError_t launch_scale(const DevPlan& pl, const uint32_t* in, const uint64_t* cin, uint32_t* out, uint64_t* cout, uint32_t a, hipStream_t s);
-hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
-hipError_t v2_launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
-
-hipError_t configure_kernels(size_t lds_front, size_t lds_mid);
-// cbuf_in (nullable, needs C >= 2): run carries left by the last back sweep, folded into the load
-hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s);
-hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, uint32_t sub, hipStream_t s);
-hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s);
 hipError_t launch_carry_fix(const DevPlan& pl, uint32_t* digits, const uint64_t* cbuf, hipStream_t s);
+hipError_t launch_sub_small(const DevPlan& pl, uint32_t* digits, uint32_t a, hipStream_t s);
+
+// Launchers of the sweeps, one per kernel variant (plan.hpp ColKernels / RowKernels).  The engine takes those of its plan's variants once
+// and calls them as they are: none of them tests the shape.
+//   front: digits (+ the run carries cbuf_in left by the last back sweep, nullable; needs C >= 2) -> work buffer W
+//   back: W -> digits x a + one carry word per run; back_ext: with the extras of BackExt
+//   build_fourstep (register-resident columns): the chain starts and ratios of their four-step twiddles (tiles x threads x 2 + M2 x 2 words)
+//   rows: Win -> Wout (mode 0: squaring, 1: times the multiplicand image Y, 2: forward only, Wout a multiplicand image)
+typedef hipError_t (*FrontFn)(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s);
+typedef hipError_t (*BackFn)(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s);
+typedef hipError_t (*BackExtFn)(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
+typedef hipError_t (*FourStepFn)(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, uint64_t* fbf, uint64_t* fbi, hipStream_t s);
+typedef hipError_t (*RowsFn)(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s);
+struct ColSweeps { FrontFn front; BackFn back; BackExtFn back_ext; FourStepFn build_fourstep; };
+
+// generic set (kernels.hip): tiles in LDS, any shape
+hipError_t configure_kernels(size_t lds_front, size_t lds_mid);
+hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s);
+hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s);
+hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
 // columns of 5 L1 pairs that do not fit LDS (n = 5 * 2^26): the radix-5 stage through a second work buffer U (8 n bytes), C = 1
 hipError_t configure_split(const DevPlan& pl);
 hipError_t launch_front_split(const DevPlan& pl, const uint32_t* digits, uint64_t* U, uint64_t* W, hipStream_t s);
 hipError_t launch_back_split(const DevPlan& pl, const uint64_t* W, uint64_t* U, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s);
-hipError_t launch_addsub(const DevPlan& pl, uint32_t* dst, const uint32_t* src, uint64_t* cbuf, int negate, hipStream_t s);
-hipError_t launch_sub_small(const DevPlan& pl, uint32_t* digits, uint32_t a, hipStream_t s);
 
-
-// radix-5 column shapes of kernels_v5.hip (M1 = 1280 = 5 x 256 with C = 4, M1 = 2560 = 5 x 512 with C = 2) and the frequency map of their
-// prime-factor form (DevPlan.lab_u / lab_v)
-inline bool v5_cols_shape(const DevPlan& pl) { return pl.r5 == 5 && ((pl.M1 == 1280 && pl.C == 4) || (pl.M1 == 2560 && pl.C == 2)) && pl.M2 >= 8; }
-void v5_pfa(const DevPlan& pl, uint32_t* u, uint32_t* v);
-
-// register-resident radix-8 set (kernels_v2.hip); shapes: rows M2 = 4096, columns M1 = 1024 x C = 4
-bool v2_rows_supported(const DevPlan& pl);
-bool v2_cols_supported(const DevPlan& pl);
-size_t v2_threads_per_tile(const DevPlan& pl);   // 512 (columns of 512 R) or 640 (columns of 1280 = 5 x 256)
+// register-resident sets; v2_configure sets the LDS size of the radix-8 and radix-5 kernels
 hipError_t v2_configure();
-// fills the chain-start / ratio tables of the column kernels' four-step twiddles (tiles*512, tiles*512, M2, M2 words)
-hipError_t v2_build_fourstep(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, uint64_t* fbf, uint64_t* fbi, hipStream_t s);
-hipError_t v2_launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, uint32_t sub, hipStream_t s);
-hipError_t v2_launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint32_t sub, uint64_t* W, hipStream_t s);
-hipError_t v2_launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, uint64_t scale, hipStream_t s);
+ColSweeps v2_cols(uint32_t R);    // radix-8 columns of 512 R, R = 1, 2, 4 (kernels_v2.hip)
+ColSweeps v3_cols(bool planes);   // radix-4 columns of 256 x 4, a pair or a plane per thread (kernels_v3.hip)
+ColSweeps v5_cols(bool j1);       // radix-5 columns of 1280 x 4 or (j1) 2560 x 2 (kernels_v5.hip)
+void v5_pfa(bool j1, uint32_t* u, uint32_t* v);   // the frequency map of their prime-factor form (DevPlan.lab_u / lab_v)
+hipError_t v2_rows4096(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t v2_rows8192(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t v2_rows2048_one(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t v2_rows2048_two(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t v3_rows1024_pairs(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t v3_rows1024_planes(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s);
 #if defined(MI355_PROBE)
-size_t v2_lds_bytes();
-// one launch of sweep `kind` (0 front, 1 rows, 2 back) over grid_mult x the normal grid with extra_lds bytes of padding LDS
+// one launch of sweep `kind` (0 front, 1 rows, 2 back) over grid_mult x the normal grid with extra_lds bytes of padding LDS:
+// the rows of 4096 and the columns of 1024 x 4 (v2), the columns of 1280 x 4 (v5)
 hipError_t v2_probe_launch(const DevPlan& pl, int kind, int grid_mult, int extra_lds, const uint32_t* digits, uint64_t* cbuf, uint64_t* W, uint32_t* dout, hipStream_t s);
+hipError_t v5_probe_launch(const DevPlan& pl, int kind, int grid_mult, int extra_lds, const uint32_t* digits, uint64_t* cbuf, uint64_t* W, uint32_t* dout, hipStream_t s);
 #endif
 
 // device-side canonical form (canon.hip): strong carry with wrap-around into natural order, compare, scatter

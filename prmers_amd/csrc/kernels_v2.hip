@@ -49,7 +49,7 @@ namespace v2 {
 // omega_32^(k1' d2), still uniform per wave), the table seam reads omega_2048^((k1' + 4 k2)(8 d3 + d4)) (plan.hpp builds S2r for this shape)
 // and everything after it is the 4096-point code with the row carried in the top bit of the k1 field: X[k], k = k1' + 4 k2 + 32 k3 + 256 k4
 // of row 2 tile + (k1 >> 2).  n = 2^21: 0.0645 -> 0.0577 ms, n = 5 2^20 (p ~ 100 M): 0.130 -> 0.120 ms (same-box A/B against the generic rows,
-// MI355_TUNE bit 6).  (Four rows of 1024 to a tile -- RL = 2, a radix-2 first stage -- were built and measured too: n = 5 2^19 has only
+// profiles/r03_summary.md).  (Four rows of 1024 to a tile -- RL = 2, a radix-2 first stage -- were built and measured too: n = 5 2^19 has only
 // 320 such tiles for 256 CUs and lost 2.4 % against the generic rows; not kept.)
 template <int RL, int W, bool INV>
 __device__ __forceinline__ void seam_rows_const(P2 (&x)[8]) {   // x[(8 >> RL) r + k1'] *= omega_(64 >> RL)^(+-k1' W) = 2^(+-39 2^RL k1' W)
@@ -783,44 +783,56 @@ __global__ void __launch_bounds__(512) k_build_f0(DevPlan pl, uint64_t* __restri
 }
 }  // namespace v2
 
-size_t v2_threads_per_tile(const DevPlan& pl) { return v5_cols_shape(pl) ? v5_threads_per_tile() : v3_cols_shape(pl) ? v3_threads_per_tile() : 512; }
+// ------------------------------- launchers ---------------------------------------------------
 
-hipError_t v2_build_fourstep(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, uint64_t* fbf, uint64_t* fbi, hipStream_t s) {
-  const dim3 grid(pl.M2 / pl.C), block(512);
-  if (v5_cols_shape(pl)) return v5_build_fourstep(pl, f0f, f0i, fbf, fbi, s);
-  if (v3_cols_shape(pl)) return v3_build_fourstep(pl, f0f, f0i, fbf, fbi, s);
-  switch (pl.M1) {
-    case 512: hipLaunchKernelGGL(v2::k_build_f0<1>, grid, block, 0, s, pl, f0f, f0i, fbf, fbi); break;
-    case 1024: hipLaunchKernelGGL(v2::k_build_f0<2>, grid, block, 0, s, pl, f0f, f0i, fbf, fbi); break;
-    default: hipLaunchKernelGGL(v2::k_build_f0<4>, grid, block, 0, s, pl, f0f, f0i, fbf, fbi); break;
+// columns of 512 R: one 4096-pair tile per work-group of 512 threads
+template <int R>
+static hipError_t cols_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s) {
+  hipLaunchKernelGGL(v2::k1_cols<R>, dim3(pl.M2 / pl.C), dim3(512), v2::kLdsBytes, s, pl, digits, cbuf_in, 0u, W);
+  return hipGetLastError();
+}
+template <int R>
+static hipError_t cols_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s) {
+  hipLaunchKernelGGL(v2::k3_cols<R>, dim3(pl.M2 / pl.C), dim3(512), v2::kLdsBytes, s, pl, W, digits, cbuf, a, uint64_t(1));
+  return hipGetLastError();
+}
+template <int R>
+static hipError_t cols_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s) {
+  hipLaunchKernelGGL(v2::k3_cols_ext<R>, dim3(pl.M2 / pl.C), dim3(512), v2::kLdsBytes, s, pl, W, digits, cbuf, a, x);
+  return hipGetLastError();
+}
+template <int R>
+static hipError_t cols_fourstep(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, uint64_t* fbf, uint64_t* fbi, hipStream_t s) {
+  hipLaunchKernelGGL(v2::k_build_f0<R>, dim3(pl.M2 / pl.C), dim3(512), 0, s, pl, f0f, f0i, fbf, fbi);
+  return hipGetLastError();
+}
+template <int R>
+static ColSweeps cols() { return {cols_front<R>, cols_back<R>, cols_back_ext<R>, cols_fourstep<R>}; }
+ColSweeps v2_cols(uint32_t R) { return R == 1 ? cols<1>() : R == 2 ? cols<2>() : cols<4>(); }
+
+// rows: one instantiation per mode (the squaring kernel carries no multiply / image code); H = 2: rows of 8192 (1024 threads),
+// RL = 1: rows of 2048 two to a tile
+template <int H, int RL>
+static hipError_t rows(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s) {
+  const dim3 grid(RL ? pl.M1 / 2 : pl.M1), block(512 * H);
+  switch (mode) {
+    case 0: hipLaunchKernelGGL((v2::k2_rows4096<0, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Wout, 0u); break;
+    case 1: hipLaunchKernelGGL((v2::k2_rows4096<1, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Wout, 0u); break;
+    default: hipLaunchKernelGGL((v2::k2_rows4096<2, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Wout, 0u); break;
   }
   return hipGetLastError();
 }
-
-// ------------------------------- launch wrappers ---------------------------------------------
-
-// rows of 2048 go two to a tile: only where that still gives at least one work-group per CU (n = 2^21, 5 2^20); below that the generic
-// rows win.  MI355_TUNE bit 6 switches them off (A/B runs)
-// Below 512 rows (n = 2^20) and at 1280 rows (n = 5 2^20: 640 two-row tiles are 1.25 rounds of the chip) a row is a tile of its own with
-// one plane per thread (k2_rows2048_planes): same-box A/B 0.0428 -> 0.0378 ms at n = 2^20, 0.1182 -> 0.1137 at 5 2^20, but 0.0571 -> 0.0586
-// at n = 2^21 (512 rows: two to a tile stay), profiles/r04_ab_rows2048_planes.txt.  MI355_TUNE bit 13 switches the plane form off, bit 14
-// forces it for every row count (A/B runs)
-static bool rows2048_planes(const DevPlan& pl) {
-  return pl.M2 == 2048 && (((pl.M1 < 512 || pl.M1 == 1280) && !(pl.tune & 8192)) || (pl.tune & 16384));
-}
-bool v2_rows_supported(const DevPlan& pl) {
-  if (v3_rows_shape(pl)) return true;   // rows of 1024: the radix-4 set (kernels_v3.hip)
-  if (pl.S2r == nullptr) return false;
-  if (pl.M2 == 4096 || pl.M2 == 8192) return true;
-  if (rows2048_planes(pl)) return true;
-  return pl.M2 == 2048 && pl.M1 % 2 == 0 && pl.M1 >= 512 && !(pl.tune & 64);
-}
-// columns: M1 = 512 R, R in {1, 2, 4}, with C = 8 / R pairs per run (one 4096-pair tile per work-group)
-bool v2_cols_supported(const DevPlan& pl) {
-  if (v5_cols_shape(pl)) return pl.DI != nullptr;
-  if (v3_cols_shape(pl)) return true;   // columns of 256 x 4: the radix-4 set
-  return pl.r5 == 1 && (pl.M1 == 512 || pl.M1 == 1024 || pl.M1 == 2048) && pl.M1 * pl.C == 4096 && pl.M2 >= pl.C * 2 && pl.S1r != nullptr &&
-         pl.DI != nullptr;
+hipError_t v2_rows4096(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s) { return rows<1, 0>(pl, Win, Y, Wout, mode, s); }
+hipError_t v2_rows8192(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s) { return rows<2, 0>(pl, Win, Y, Wout, mode, s); }
+hipError_t v2_rows2048_two(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s) { return rows<1, 1>(pl, Win, Y, Wout, mode, s); }
+// rows of 2048, one row per tile with one plane per thread
+hipError_t v2_rows2048_one(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s) {
+  switch (mode) {
+    case 0: hipLaunchKernelGGL((v2::k2_rows2048_planes<0>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Wout, 0u); break;
+    case 1: hipLaunchKernelGGL((v2::k2_rows2048_planes<1>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Wout, 0u); break;
+    default: hipLaunchKernelGGL((v2::k2_rows2048_planes<2>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Wout, 0u); break;
+  }
+  return hipGetLastError();
 }
 
 #define MI355_SET_LDS(KERNEL, BYTES)                                                                                          \
@@ -837,72 +849,16 @@ hipError_t v2_configure() {
   return hipSuccess;
 }
 #undef MI355_SET_LDS
-hipError_t v2_launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, uint32_t sub, hipStream_t s) {
-  if (v3_rows_shape(pl)) return v3_launch_middle(pl, Win, Y, Wout, mode, sub, s);
-#define MI355_ROWS(MODE, HH) hipLaunchKernelGGL((v2::k2_rows4096<MODE, HH>), dim3(pl.M1), dim3(512 * HH), HH * v2::kLdsBytes, s, pl, Win, Y, Wout, sub)
-  if (rows2048_planes(pl)) {
-#define MI355_ROWS_PL(MODE) hipLaunchKernelGGL((v2::k2_rows2048_planes<MODE>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Wout, sub)
-    switch (mode) { case 0: MI355_ROWS_PL(0); break; case 1: MI355_ROWS_PL(1); break; default: MI355_ROWS_PL(2); break; }
-#undef MI355_ROWS_PL
-  } else if (pl.M2 == 2048) {   // two rows to a tile
-#define MI355_ROWS_TWO(MODE) hipLaunchKernelGGL((v2::k2_rows4096<MODE, 1, 1>), dim3(pl.M1 / 2), dim3(512), v2::kLdsBytes, s, pl, Win, Y, Wout, sub)
-    switch (mode) { case 0: MI355_ROWS_TWO(0); break; case 1: MI355_ROWS_TWO(1); break; default: MI355_ROWS_TWO(2); break; }
-#undef MI355_ROWS_TWO
-  } else if (pl.M2 == 4096) {   // one instantiation per mode: the squaring kernel carries no multiply / image code
-    switch (mode) { case 0: MI355_ROWS(0, 1); break; case 1: MI355_ROWS(1, 1); break; default: MI355_ROWS(2, 1); break; }
-  } else {
-    switch (mode) { case 0: MI355_ROWS(0, 2); break; case 1: MI355_ROWS(1, 2); break; default: MI355_ROWS(2, 2); break; }
-  }
-#undef MI355_ROWS
-  return hipGetLastError();
-}
-hipError_t v2_launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint32_t sub, uint64_t* W, hipStream_t s) {
-  const dim3 grid(pl.M2 / pl.C), block(512);
-  if (v5_cols_shape(pl)) return v5_launch_front(pl, digits, cbuf_in, sub, W, s);
-  if (v3_cols_shape(pl)) return v3_launch_front(pl, digits, cbuf_in, sub, W, s);
-  switch (pl.M1) {
-    case 512: hipLaunchKernelGGL(v2::k1_cols<1>, grid, block, v2::kLdsBytes, s, pl, digits, cbuf_in, sub, W); break;
-    case 1024: hipLaunchKernelGGL(v2::k1_cols<2>, grid, block, v2::kLdsBytes, s, pl, digits, cbuf_in, sub, W); break;
-    default: hipLaunchKernelGGL(v2::k1_cols<4>, grid, block, v2::kLdsBytes, s, pl, digits, cbuf_in, sub, W); break;
-  }
-  return hipGetLastError();
-}
-hipError_t v2_launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, uint64_t scale, hipStream_t s) {
-  const dim3 grid(pl.M2 / pl.C), block(512);
-  if (v5_cols_shape(pl)) return v5_launch_back(pl, W, digits, cbuf, a, scale, s);
-  if (v3_cols_shape(pl)) return v3_launch_back(pl, W, digits, cbuf, a, scale, s);
-  switch (pl.M1) {
-    case 512: hipLaunchKernelGGL(v2::k3_cols<1>, grid, block, v2::kLdsBytes, s, pl, W, digits, cbuf, a, scale); break;
-    case 1024: hipLaunchKernelGGL(v2::k3_cols<2>, grid, block, v2::kLdsBytes, s, pl, W, digits, cbuf, a, scale); break;
-    default: hipLaunchKernelGGL(v2::k3_cols<4>, grid, block, v2::kLdsBytes, s, pl, W, digits, cbuf, a, scale); break;
-  }
-  return hipGetLastError();
-}
-hipError_t v2_launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s) {
-  const dim3 grid(pl.M2 / pl.C), block(512);
-  if (v5_cols_shape(pl)) return v5_launch_back_ext(pl, W, digits, cbuf, a, x, s);
-  if (v3_cols_shape(pl)) return v3_launch_back_ext(pl, W, digits, cbuf, a, x, s);
-  switch (pl.M1) {
-    case 512: hipLaunchKernelGGL(v2::k3_cols_ext<1>, grid, block, v2::kLdsBytes, s, pl, W, digits, cbuf, a, x); break;
-    case 1024: hipLaunchKernelGGL(v2::k3_cols_ext<2>, grid, block, v2::kLdsBytes, s, pl, W, digits, cbuf, a, x); break;
-    default: hipLaunchKernelGGL(v2::k3_cols_ext<4>, grid, block, v2::kLdsBytes, s, pl, W, digits, cbuf, a, x); break;
-  }
-  return hipGetLastError();
-}
 
 #if defined(MI355_PROBE)
-size_t v2_lds_bytes() { return v2::kLdsBytes; }
 hipError_t v2_probe_launch(const DevPlan& pl, int kind, int grid_mult, int extra_lds, const uint32_t* digits, uint64_t* cbuf, uint64_t* W, uint32_t* dout, hipStream_t s) {
   const size_t lds = v2::kLdsBytes + size_t(extra_lds);
   if (kind == 1) {
-    if (pl.M2 != 4096) return hipErrorNotSupported;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(v2::k2_rows4096<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((v2::k2_rows4096<0, 1>), dim3(pl.M1 * grid_mult), dim3(512), lds, s, pl, W, nullptr, W, 0u);
     return hipGetLastError();
   }
-  if (v5_cols_shape(pl)) return v5_probe_launch(pl, kind, grid_mult, extra_lds, digits, cbuf, W, dout, s);
-  if (pl.M1 != 1024) return hipErrorNotSupported;
   const dim3 grid((pl.M2 / pl.C) * grid_mult), block(512);
   if (kind == 0) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(v2::k1_cols<2>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));

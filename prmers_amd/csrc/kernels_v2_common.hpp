@@ -190,25 +190,6 @@ __device__ __forceinline__ void apply_carry_in(const DevPlan& pl, uint32_t di, i
 
 }  // namespace v2
 
-// launch entry points of the radix-5 column shapes (kernels_v5.hip; v5_cols_shape, v5_pfa: kernels.hpp)
-size_t v5_threads_per_tile();
-hipError_t v5_configure();
-hipError_t v5_build_fourstep(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, uint64_t* fbf, uint64_t* fbi, hipStream_t s);
-hipError_t v5_launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint32_t sub, uint64_t* W, hipStream_t s);
-hipError_t v5_launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, uint64_t scale, hipStream_t s);
-hipError_t v5_launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
-#if defined(MI355_PROBE)
-hipError_t v5_probe_launch(const DevPlan& pl, int kind, int grid_mult, int extra_lds, const uint32_t* digits, uint64_t* cbuf, uint64_t* W, uint32_t* dout, hipStream_t s);
-#endif
-
-// radix-4 set for the small transforms (kernels_v3.hip): rows of 1024, columns of 256 with runs of four pairs (1024-pair tiles, 256 threads)
-bool v3_rows_shape(const DevPlan& pl);
-bool v3_cols_shape(const DevPlan& pl);
-size_t v3_threads_per_tile();
-hipError_t v3_build_fourstep(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, uint64_t* fbf, uint64_t* fbi, hipStream_t s);
-hipError_t v3_launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, uint32_t sub, hipStream_t s);
-hipError_t v3_launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint32_t sub, uint64_t* W, hipStream_t s);
-hipError_t v3_launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, uint64_t scale, hipStream_t s);
-hipError_t v3_launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
+hipError_t v5_configure();   // (kernels_v5.hip; called by v2_configure)
 
 }  // namespace mi355

@@ -684,57 +684,50 @@ __global__ void __launch_bounds__(kThreads) k_build_f0(DevPlan pl, uint64_t* __r
 
 }  // namespace v3
 
-// ------------------------------- shapes and launch wrappers -----------------------------------
-// MI355_TUNE bit 7 switches the set off (A/B runs against the generic kernels).
-// Rows: with one row per CU the launch lasts as long as one wave's dependent stream: the pair-per-thread kernel (one wave per SIMD) takes
-// 12.8 us at C2 against 10.6 us for the generic rows (eight waves per row, one plane of a butterfly per thread); the plane-per-thread form
-// below serves those sizes; with five rows per CU (n = 5 2^19) the pair form's lower instruction count wins, 26.0 against 30.1 us
-// (same-box A/B, profiles/r04_ab_radix4_set.txt).
-bool v3_rows_shape(const DevPlan& pl) { return pl.M2 == 1024 && !(pl.tune & 128); }
-bool v3_cols_shape(const DevPlan& pl) { return pl.r5 == 1 && pl.M1 == 256 && pl.C == 4 && pl.M2 >= 8 && pl.DI != nullptr && !(pl.tune & 128); }
-size_t v3_threads_per_tile() { return v3::kThreads; }
+// ------------------------------- launchers ---------------------------------------------------
+// Two forms of every kernel (plan.hpp served_kernels picks one): a pair per thread (256 threads, the fewest instructions per word) and one
+// plane per thread (512 threads, twice the waves with half the stream each: where a CU gets one tile or fewer).
+template <int mode>
+static void launch_rows(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, bool planes, hipStream_t s) {
+  if (planes) hipLaunchKernelGGL(v3::k2_rows1024_planes<mode>, dim3(pl.M1), dim3(2 * v3::kThreads), v3::kLdsBytes, s, pl, Win, Y, Wout, 0u);
+  else hipLaunchKernelGGL(v3::k2_rows1024<mode>, dim3(pl.M1), dim3(v3::kThreads), v3::kLdsBytes, s, pl, Win, Y, Wout, 0u);
+}
+static hipError_t rows1024(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, bool planes, hipStream_t s) {
+  switch (mode) {
+    case 0: launch_rows<0>(pl, Win, Y, Wout, planes, s); break;
+    case 1: launch_rows<1>(pl, Win, Y, Wout, planes, s); break;
+    default: launch_rows<2>(pl, Win, Y, Wout, planes, s); break;
+  }
+  return hipGetLastError();
+}
+hipError_t v3_rows1024_pairs(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s) { return rows1024(pl, Win, Y, Wout, mode, false, s); }
+hipError_t v3_rows1024_planes(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s) { return rows1024(pl, Win, Y, Wout, mode, true, s); }
 
-hipError_t v3_build_fourstep(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, uint64_t* fbf, uint64_t* fbi, hipStream_t s) {
+template <bool PLANES>
+static hipError_t cols_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s) {
+  if (PLANES) hipLaunchKernelGGL(v3::k1_cols256_planes, dim3(pl.M2 / 4), dim3(2 * v3::kThreads), v3::kLdsBytes, s, pl, digits, cbuf_in, 0u, W);
+  else hipLaunchKernelGGL(v3::k1_cols256, dim3(pl.M2 / 4), dim3(v3::kThreads), v3::kLdsBytes, s, pl, digits, cbuf_in, 0u, W);
+  return hipGetLastError();
+}
+template <bool PLANES>
+static hipError_t cols_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s) {
+  if (PLANES) hipLaunchKernelGGL(v3::k3_cols256_planes<false>, dim3(pl.M2 / 4), dim3(2 * v3::kThreads), v3::kLdsBytes, s, pl, W, digits, cbuf, a, uint64_t(1), BackExt());
+  else hipLaunchKernelGGL(v3::k3_cols256<false>, dim3(pl.M2 / 4), dim3(v3::kThreads), v3::kLdsBytes, s, pl, W, digits, cbuf, a, uint64_t(1), BackExt());
+  return hipGetLastError();
+}
+template <bool PLANES>
+static hipError_t cols_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s) {
+  if (PLANES) hipLaunchKernelGGL(v3::k3_cols256_planes<true>, dim3(pl.M2 / 4), dim3(2 * v3::kThreads), v3::kLdsBytes, s, pl, W, digits, cbuf, a, uint64_t(1), x);
+  else hipLaunchKernelGGL(v3::k3_cols256<true>, dim3(pl.M2 / 4), dim3(v3::kThreads), v3::kLdsBytes, s, pl, W, digits, cbuf, a, uint64_t(1), x);
+  return hipGetLastError();
+}
+static hipError_t cols_fourstep(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, uint64_t* fbf, uint64_t* fbi, hipStream_t s) {
   hipLaunchKernelGGL(v3::k_build_f0, dim3(pl.M2 / 4), dim3(v3::kThreads), 0, s, pl, f0f, f0i, fbf, fbi);
   return hipGetLastError();
 }
-hipError_t v3_launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, uint32_t sub, hipStream_t s) {
-  const dim3 grid(pl.M1), block(v3::kThreads);
-  // one row per CU or fewer: one plane per thread (twice the waves, half the stream each); more rows: a pair per thread (fewer
-  // instructions per word).  MI355_TUNE bit 8 forces the pair form, bit 9 the plane form (A/B runs).
-  const bool planes = ((pl.M1 < 512) && !(pl.tune & 256)) || (pl.tune & 512);
-  if (planes) {
-    const dim3 block2(2 * v3::kThreads);
-    switch (mode) {
-      case 0: hipLaunchKernelGGL(v3::k2_rows1024_planes<0>, grid, block2, v3::kLdsBytes, s, pl, Win, Y, Wout, sub); break;
-      case 1: hipLaunchKernelGGL(v3::k2_rows1024_planes<1>, grid, block2, v3::kLdsBytes, s, pl, Win, Y, Wout, sub); break;
-      default: hipLaunchKernelGGL(v3::k2_rows1024_planes<2>, grid, block2, v3::kLdsBytes, s, pl, Win, Y, Wout, sub); break;
-    }
-    return hipGetLastError();
-  }
-  switch (mode) {
-    case 0: hipLaunchKernelGGL(v3::k2_rows1024<0>, grid, block, v3::kLdsBytes, s, pl, Win, Y, Wout, sub); break;
-    case 1: hipLaunchKernelGGL(v3::k2_rows1024<1>, grid, block, v3::kLdsBytes, s, pl, Win, Y, Wout, sub); break;
-    default: hipLaunchKernelGGL(v3::k2_rows1024<2>, grid, block, v3::kLdsBytes, s, pl, Win, Y, Wout, sub); break;
-  }
-  return hipGetLastError();
-}
-// columns: one plane per thread where the tiles make a single round (at most two per CU; MI355_TUNE bit 10 forces the pair form, bit 11 the plane form)
-static bool cols_planes(const DevPlan& pl) { return ((pl.M2 / 4 <= 512) && !(pl.tune & 1024)) || (pl.tune & 2048); }
-hipError_t v3_launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint32_t sub, uint64_t* W, hipStream_t s) {
-  if (cols_planes(pl)) hipLaunchKernelGGL(v3::k1_cols256_planes, dim3(pl.M2 / 4), dim3(2 * v3::kThreads), v3::kLdsBytes, s, pl, digits, cbuf_in, sub, W);
-  else hipLaunchKernelGGL(v3::k1_cols256, dim3(pl.M2 / 4), dim3(v3::kThreads), v3::kLdsBytes, s, pl, digits, cbuf_in, sub, W);
-  return hipGetLastError();
-}
-hipError_t v3_launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, uint64_t scale, hipStream_t s) {
-  if (cols_planes(pl)) hipLaunchKernelGGL(v3::k3_cols256_planes<false>, dim3(pl.M2 / 4), dim3(2 * v3::kThreads), v3::kLdsBytes, s, pl, W, digits, cbuf, a, scale, BackExt());
-  else hipLaunchKernelGGL(v3::k3_cols256<false>, dim3(pl.M2 / 4), dim3(v3::kThreads), v3::kLdsBytes, s, pl, W, digits, cbuf, a, scale, BackExt());
-  return hipGetLastError();
-}
-hipError_t v3_launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s) {
-  if (cols_planes(pl)) hipLaunchKernelGGL(v3::k3_cols256_planes<true>, dim3(pl.M2 / 4), dim3(2 * v3::kThreads), v3::kLdsBytes, s, pl, W, digits, cbuf, a, uint64_t(1), x);
-  else hipLaunchKernelGGL(v3::k3_cols256<true>, dim3(pl.M2 / 4), dim3(v3::kThreads), v3::kLdsBytes, s, pl, W, digits, cbuf, a, uint64_t(1), x);
-  return hipGetLastError();
+ColSweeps v3_cols(bool planes) {
+  return planes ? ColSweeps{cols_front<true>, cols_back<true>, cols_back_ext<true>, cols_fourstep}
+                : ColSweeps{cols_front<false>, cols_back<false>, cols_back_ext<false>, cols_fourstep};
 }
 
 }  // namespace mi355

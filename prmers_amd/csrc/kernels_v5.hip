@@ -349,9 +349,7 @@ __global__ void __launch_bounds__(640) k_build_f0(DevPlan pl, uint64_t* __restri
 }
 }  // namespace v5
 
-static bool v5_j1(const DevPlan& pl) { return pl.M1 == 2560; }
-void v5_pfa(const DevPlan& pl, uint32_t* u, uint32_t* v) { *u = v5_j1(pl) ? v5::Shape<1>::PU : v5::Shape<0>::PU; *v = v5::Shape<0>::PV; }
-size_t v5_threads_per_tile() { return v5::kThreads; }
+void v5_pfa(bool j1, uint32_t* u, uint32_t* v) { *u = j1 ? v5::Shape<1>::PU : v5::Shape<0>::PU; *v = v5::Shape<0>::PV; }
 hipError_t v5_configure() {
   for (const void* f : {reinterpret_cast<const void*>(v5::k1_cols5<0>), reinterpret_cast<const void*>(v5::k3_cols5<0, false>), reinterpret_cast<const void*>(v5::k3_cols5<0, true>)}) {
     hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(v5::lds_bytes(1280)));
@@ -363,29 +361,33 @@ hipError_t v5_configure() {
   }
   return hipSuccess;
 }
-hipError_t v5_build_fourstep(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, uint64_t* fbf, uint64_t* fbi, hipStream_t s) {
-  if (v5_j1(pl)) hipLaunchKernelGGL(v5::k_build_f0<1>, dim3(pl.M2 / pl.C), dim3(v5::kThreads), 0, s, pl, f0f, f0i, fbf, fbi);
-  else hipLaunchKernelGGL(v5::k_build_f0<0>, dim3(pl.M2 / pl.C), dim3(v5::kThreads), 0, s, pl, f0f, f0i, fbf, fbi);
+// columns of 1280 x 4 (J = 0) and 2560 x 2 (J = 1): 640 threads per tile launched as 768
+template <int J>
+static hipError_t cols_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s) {
+  hipLaunchKernelGGL(v5::k1_cols5<J>, dim3(pl.M2 / pl.C), dim3(v5::kLaunchThreads), v5::lds_bytes(J ? 2560 : 1280), s, pl, digits, cbuf_in, 0u, W);
   return hipGetLastError();
 }
-hipError_t v5_launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint32_t sub, uint64_t* W, hipStream_t s) {
-  if (v5_j1(pl)) hipLaunchKernelGGL(v5::k1_cols5<1>, dim3(pl.M2 / pl.C), dim3(v5::kLaunchThreads), v5::lds_bytes(2560), s, pl, digits, cbuf_in, sub, W);
-  else hipLaunchKernelGGL(v5::k1_cols5<0>, dim3(pl.M2 / pl.C), dim3(v5::kLaunchThreads), v5::lds_bytes(1280), s, pl, digits, cbuf_in, sub, W);
+template <int J>
+static hipError_t cols_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s) {
+  hipLaunchKernelGGL((v5::k3_cols5<J, false>), dim3(pl.M2 / pl.C), dim3(v5::kLaunchThreads), v5::lds_bytes(J ? 2560 : 1280), s, pl, W, digits, cbuf, a, uint64_t(1), BackExt());
   return hipGetLastError();
 }
-hipError_t v5_launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, uint64_t scale, hipStream_t s) {
-  if (v5_j1(pl)) hipLaunchKernelGGL((v5::k3_cols5<1, false>), dim3(pl.M2 / pl.C), dim3(v5::kLaunchThreads), v5::lds_bytes(2560), s, pl, W, digits, cbuf, a, scale, BackExt());
-  else hipLaunchKernelGGL((v5::k3_cols5<0, false>), dim3(pl.M2 / pl.C), dim3(v5::kLaunchThreads), v5::lds_bytes(1280), s, pl, W, digits, cbuf, a, scale, BackExt());
+template <int J>
+static hipError_t cols_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s) {
+  hipLaunchKernelGGL((v5::k3_cols5<J, true>), dim3(pl.M2 / pl.C), dim3(v5::kLaunchThreads), v5::lds_bytes(J ? 2560 : 1280), s, pl, W, digits, cbuf, a, uint64_t(1), x);
   return hipGetLastError();
 }
-hipError_t v5_launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s) {
-  if (v5_j1(pl)) hipLaunchKernelGGL((v5::k3_cols5<1, true>), dim3(pl.M2 / pl.C), dim3(v5::kLaunchThreads), v5::lds_bytes(2560), s, pl, W, digits, cbuf, a, uint64_t(1), x);
-  else hipLaunchKernelGGL((v5::k3_cols5<0, true>), dim3(pl.M2 / pl.C), dim3(v5::kLaunchThreads), v5::lds_bytes(1280), s, pl, W, digits, cbuf, a, uint64_t(1), x);
+template <int J>
+static hipError_t cols_fourstep(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, uint64_t* fbf, uint64_t* fbi, hipStream_t s) {
+  hipLaunchKernelGGL(v5::k_build_f0<J>, dim3(pl.M2 / pl.C), dim3(v5::kThreads), 0, s, pl, f0f, f0i, fbf, fbi);
   return hipGetLastError();
+}
+ColSweeps v5_cols(bool j1) {
+  return j1 ? ColSweeps{cols_front<1>, cols_back<1>, cols_back_ext<1>, cols_fourstep<1>}
+            : ColSweeps{cols_front<0>, cols_back<0>, cols_back_ext<0>, cols_fourstep<0>};
 }
 #if defined(MI355_PROBE)
 hipError_t v5_probe_launch(const DevPlan& pl, int kind, int grid_mult, int extra_lds, const uint32_t* digits, uint64_t* cbuf, uint64_t* W, uint32_t* dout, hipStream_t s) {
-  if (v5_j1(pl)) return hipErrorNotSupported;
   const dim3 g5((pl.M2 / pl.C) * grid_mult), b5(v5::kLaunchThreads);
   const size_t l5 = v5::lds_bytes(1280) + size_t(extra_lds);
   const void* f = kind == 0 ? reinterpret_cast<const void*>(v5::k1_cols5<0>) : reinterpret_cast<const void*>(v5::k3_cols5<0, false>);

@@ -135,6 +135,64 @@ inline bool fused_factor_ok(uint32_t q, size_t n, uint32_t C, uint64_t a) {
   return false;
 }
 
+// Kernel variants of the column sweeps (front and back) and of the row sweep.
+enum class ColKernels : uint8_t {
+  kGeneric,                      // kernels.hip k_front, k_back<EXT>: every shape whose columns fit LDS
+  kSplit,                        // kernels.hip k_front_split_a/b, k_back_split_a/b: columns of 5 L1 pairs beyond LDS (split5)
+  kRadix8R1, kRadix8R2, kRadix8R4,   // kernels_v2.hip k1_cols<R>, k3_cols<R>, k3_cols_ext<R>: M1 = 512 R, M1 C = 4096
+  kRadix4Pairs, kRadix4Planes,   // kernels_v3.hip k1_cols256[_planes], k3_cols256[_planes]<EXT>: 256 x 4
+  kRadix5, kRadix5J1,            // kernels_v5.hip k1_cols5<J>, k3_cols5<J, EXT>: 1280 x 4 (J = 0), 2560 x 2 (J = 1)
+};
+enum class RowKernels : uint8_t {
+  kGeneric,                      // kernels.hip k_middle
+  kRadix4Pairs, kRadix4Planes,   // kernels_v3.hip k2_rows1024[_planes]<mode>: rows of 1024
+  kRadix8,                       // kernels_v2.hip k2_rows4096<mode, 1>: rows of 4096
+  kRadix8Wide,                   // k2_rows4096<mode, 2>: rows of 8192 as two 4096-point halves, 1024 threads
+  kRows2048One, kRows2048Two,    // k2_rows2048_planes<mode> (one row per tile), k2_rows4096<mode, 1, 1> (two rows per tile)
+};
+
+struct KernelChoice {
+  ColKernels cols = ColKernels::kGeneric;
+  RowKernels rows = RowKernels::kGeneric;
+  bool resident_cols() const { return cols != ColKernels::kGeneric && cols != ColKernels::kSplit; }   // register-resident column kernels
+  bool fused_back() const { return cols != ColKernels::kSplit; }   // a back sweep with extras (kernels.hpp BackExt)
+};
+
+// The kernels that serve a shape (r5, M1, M2, C, split5); the first matching rule wins.  make_plan builds the seam and digit-info tables
+// of exactly these, choose_kernels narrows them.
+//   radix-4 columns: one plane per thread where the tiles make a single round (at most two per CU), else a pair per thread;
+//   radix-4 rows: one plane per thread with one row per CU or fewer (the pair form takes 12.8 us at C2 against 10.6 us for the generic
+//     rows), a pair per thread above (n = 5 2^19: 26.0 against 30.1 us); profiles/r04_ab_radix4_set.txt has the same-box A/B of both;
+//   rows of 2048: two to a tile (n = 2^21: 0.0645 -> 0.0577 ms, n = 5 2^20: 0.130 -> 0.120 ms against the generic rows,
+//     profiles/r03_summary.md), but one row per tile below 512 rows and at 1280 rows, where 640 two-row tiles are 1.25 rounds of the chip
+//     (0.0428 -> 0.0378 ms at n = 2^20, 0.1182 -> 0.1137 at 5 2^20, 0.0571 -> 0.0586 at n = 2^21: profiles/r04_ab_rows2048_planes.txt).
+inline KernelChoice served_kernels(uint32_t r5, uint32_t M1, uint32_t M2, uint32_t C, bool split5) {
+  KernelChoice k;
+  if (split5) k.cols = ColKernels::kSplit;
+  else if (r5 == 5 && ((M1 == 1280 && C == 4) || (M1 == 2560 && C == 2)) && M2 >= 8)
+    k.cols = M1 == 2560 ? ColKernels::kRadix5J1 : ColKernels::kRadix5;
+  else if (r5 == 1 && M1 == 256 && C == 4 && M2 >= 8)
+    k.cols = M2 / 4 <= 512 ? ColKernels::kRadix4Planes : ColKernels::kRadix4Pairs;
+  else if (r5 == 1 && (M1 == 512 || M1 == 1024 || M1 == 2048) && M1 * C == 4096 && M2 >= 2 * C)
+    k.cols = M1 == 512 ? ColKernels::kRadix8R1 : M1 == 1024 ? ColKernels::kRadix8R2 : ColKernels::kRadix8R4;
+  if (M2 == 1024) k.rows = M1 < 512 ? RowKernels::kRadix4Planes : RowKernels::kRadix4Pairs;
+  else if (M2 == 4096) k.rows = RowKernels::kRadix8;
+  else if (M2 == 8192) k.rows = RowKernels::kRadix8Wide;
+  else if (M2 == 2048 && (M1 < 512 || M1 == 1280)) k.rows = RowKernels::kRows2048One;
+  else if (M2 == 2048 && M1 % 2 == 0 && M1 >= 512) k.rows = RowKernels::kRows2048Two;
+  return k;
+}
+
+// threads per tile of the register-resident column kernels (the digit-info words and four-step tables are [tile][thread]); 0: none
+inline uint32_t threads_per_tile(ColKernels c) {
+  switch (c) {
+    case ColKernels::kRadix8R1: case ColKernels::kRadix8R2: case ColKernels::kRadix8R4: return 512;
+    case ColKernels::kRadix4Pairs: case ColKernels::kRadix4Planes: return 256;
+    case ColKernels::kRadix5: case ColKernels::kRadix5J1: return 640;
+    default: return 0;
+  }
+}
+
 inline uint32_t fused_factor_limit(uint32_t q, size_t n, uint32_t C) {
   uint64_t lo = 1, hi = 0xffffffffu;
   if (!fused_factor_ok(q, n, C, 1)) return 1;   // (never for a plan of the size rule; factor 1 is the plain squaring either way)
@@ -261,7 +319,8 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
   const uint64_t om1 = gf::pow(om, pl.M2), om2 = gf::pow(om, pl.M1);
   pl.UT1.resize(pl.M1); pl.UT1[0] = 1; for (uint32_t i = 1; i < pl.M1; ++i) pl.UT1[i] = gf::mul(pl.UT1[i - 1], om1);
   pl.UT2.resize(pl.M2); pl.UT2[0] = 1; for (uint32_t i = 1; i < pl.M2; ++i) pl.UT2[i] = gf::mul(pl.UT2[i - 1], om2);
-  if (pl.M2 == 4096 || pl.M2 == 8192) {   // rows of 8192 = one radix-2 level over two 4096-point transforms
+  const KernelChoice kc = served_kernels(pl.r5, pl.M1, pl.M2, pl.C, pl.split5);
+  if (kc.rows == RowKernels::kRadix8 || kc.rows == RowKernels::kRadix8Wide) {   // rows of 8192 = one radix-2 level over two 4096-point transforms
     const uint32_t st = pl.M2 / 4096;       // omega_4096 = omega_M2^st
     pl.S2r.resize(4096); pl.S2ri.resize(4096);
     for (uint32_t b = 0; b < 64; ++b) for (uint32_t ka = 0; ka < 64; ++ka) {
@@ -270,14 +329,16 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
       pl.S2r[idx] = pl.UT2[st * e]; pl.S2ri[idx] = pl.UT2[st * ((4096 - e) & 4095)];
     }
   }
-  if (pl.M2 == 2048) {   // rows of 2048 two to a tile (kernels_v2.hip, RL = 1): [b][k1][k2] with k1 = 4 row + k1', omega_2048^((k1' + 4 k2) b)
+  if (kc.rows == RowKernels::kRows2048One || kc.rows == RowKernels::kRows2048Two) {
+    // rows of 2048 (kernels_v2.hip, RL = 1 and the one-row form): [b][k1][k2] with k1 = 4 row + k1', omega_2048^((k1' + 4 k2) b)
     pl.S2r.resize(4096); pl.S2ri.resize(4096);
     for (uint32_t b = 0; b < 64; ++b) for (uint32_t k1 = 0; k1 < 8; ++k1) for (uint32_t k2 = 0; k2 < 8; ++k2) {
       const uint32_t e = (((k1 & 3) + 4 * k2) * b) & 2047;
       pl.S2r[b * 64 + k1 * 8 + k2] = pl.UT2[e]; pl.S2ri[b * 64 + k1 * 8 + k2] = pl.UT2[(2048 - e) & 2047];
     }
   }
-  if (pl.r5 == 1 && (pl.M1 == 512 || pl.M1 == 1024 || pl.M1 == 2048)) {   // M1 = 512 R = (8R) x 64
+  const uint32_t tpt = threads_per_tile(kc.cols);
+  if (tpt == 512) {   // radix-8 columns, M1 = 512 R = (8R) x 64
     const uint32_t ka_n = pl.M1 / 64;
     pl.S1r.resize(pl.M1); pl.S1ri.resize(pl.M1);
     for (uint32_t b = 0; b < 64; ++b) for (uint32_t ka = 0; ka < ka_n; ++ka) {
@@ -288,56 +349,23 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
   }
   if (m % 4 == 0) { pl.I4 = gf::pow(om, m / 4); pl.I4inv = gf::inv(pl.I4); }
   else { pl.I4 = gf::root_of_unity(4); pl.I4inv = gf::inv(pl.I4); }
-  if (!pl.S1r.empty() && size_t(pl.M1) * pl.C == 4096) {
-    const uint32_t R = pl.M1 / 512, ND = 2 * pl.C;
-    pl.DI.assign(pl.tiles() * 512, 0u);
+  if (tpt) {
+    // digit-info words of the register-resident column kernels: thread t of tile T owns the runs i1 = t + tpt d1 (M1 / tpt runs of 2C digits;
+    // radix-8: R runs of 16 / R digits, radix-4: one of eight, radix-5: two of eight or four of four), 2 bits per digit at 2 (d1 2C + k)
+    const uint32_t NR = pl.M1 / tpt, ND = 2 * pl.C;
+    pl.DI.assign(pl.tiles() * tpt, 0u);
     for (size_t T = 0; T < pl.tiles(); ++T)
-      for (uint32_t t = 0; t < 512; ++t) {
+      for (uint32_t t = 0; t < tpt; ++t) {
         uint32_t w = 0;
-        for (uint32_t d1 = 0; d1 < R; ++d1)
+        for (uint32_t d1 = 0; d1 < NR; ++d1)
           for (uint32_t k = 0; k < ND; ++k) {
-            const uint32_t i1 = 512 * d1 + t, i2 = uint32_t(T) * pl.C + (k >> 1);
+            const uint32_t i1 = tpt * d1 + t, i2 = uint32_t(T) * pl.C + (k >> 1);
             const uint64_t sb = pl.SB[2 * i2 + (k & 1)], s = (uint64_t(pl.SA[i1]) + sb) % n;
             const uint64_t wa = (k & 1) ? pl.SA[pl.M1 + i1] : pl.SA[i1], wb = pl.SB[2 * i2];   // the split the kernels weight with
             const uint32_t wbit = pl.width_of_s(s) - pl.q, wrap = (wa > 0 && wb > 0 && wa + wb <= n) ? 1u : 0u;
             w |= (wbit | (wrap << 1)) << (2 * (d1 * ND + k));
           }
-        pl.DI[T * 512 + t] = w;
-      }
-  }
-  if (pl.r5 == 1 && pl.M1 == 256 && pl.C == 4 && pl.M2 >= 8) {
-    // columns of 256 (kernels_v3.hip): 256 threads per tile, thread t owns the run i1 = t (8 digits, 2 bits each)
-    pl.DI.assign(pl.tiles() * 256, 0u);
-    for (size_t T = 0; T < pl.tiles(); ++T)
-      for (uint32_t t = 0; t < 256; ++t) {
-        uint32_t w = 0;
-        for (uint32_t k = 0; k < 8; ++k) {
-          const uint32_t i1 = t, i2 = uint32_t(T) * 4 + (k >> 1);
-          const uint64_t sb = pl.SB[2 * i2 + (k & 1)], s = (uint64_t(pl.SA[i1]) + sb) % n;
-          const uint64_t wa = (k & 1) ? pl.SA[pl.M1 + i1] : pl.SA[i1], wb = pl.SB[2 * i2];
-          const uint32_t wbit = pl.width_of_s(s) - pl.q, wrap = (wa > 0 && wb > 0 && wa + wb <= n) ? 1u : 0u;
-          w |= (wbit | (wrap << 1)) << (2 * k);
-        }
-        pl.DI[T * 256 + t] = w;
-      }
-  }
-  if (pl.r5 == 5 && ((pl.M1 == 1280 && pl.C == 4) || (pl.M1 == 2560 && pl.C == 2)) && pl.M2 >= 8) {
-    // columns of 1280 = 5 x 256 and 2560 = 5 x 512 (kernels_v5.hip): 640 threads per tile, thread t owns the runs i1 = t + 640 d1
-    // (two runs of eight digits, or four of four)
-    const uint32_t NR = pl.M1 / 640, ND = 2 * pl.C;
-    pl.DI.assign(pl.tiles() * 640, 0u);
-    for (size_t T = 0; T < pl.tiles(); ++T)
-      for (uint32_t t = 0; t < 640; ++t) {
-        uint32_t w = 0;
-        for (uint32_t d1 = 0; d1 < NR; ++d1)
-          for (uint32_t k = 0; k < ND; ++k) {
-            const uint32_t i1 = 640 * d1 + t, i2 = uint32_t(T) * pl.C + (k >> 1);
-            const uint64_t sb = pl.SB[2 * i2 + (k & 1)], s = (uint64_t(pl.SA[i1]) + sb) % n;
-            const uint64_t wa = (k & 1) ? pl.SA[pl.M1 + i1] : pl.SA[i1], wb = pl.SB[2 * i2];
-            const uint32_t wbit = pl.width_of_s(s) - pl.q, wrap = (wa > 0 && wb > 0 && wa + wb <= n) ? 1u : 0u;
-            w |= (wbit | (wrap << 1)) << (2 * (d1 * ND + k));
-          }
-        pl.DI[T * 640 + t] = w;
+        pl.DI[T * tpt + t] = w;
       }
   }
   if (pl.I4 != (uint64_t(1) << 48)) throw std::runtime_error("internal: omega_4 is expected to be 2^48");   // the kernels shift instead of multiplying
@@ -349,6 +377,16 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
     pl.W5c[0] = gf::half(gf::half(gf::sub(a, b))); pl.W5c[1] = k1; pl.W5c[2] = gf::sub(k2, k1); pl.W5c[3] = gf::add(k1, k2);
   }
   return pl;
+}
+
+// The kernels a plan runs: those that serve its shape, narrowed by MI355_KERNELS (A/B tests, debugging): unset or "v2" keeps them,
+// "v2rows" / "v2cols" keep only the register-resident rows / columns, anything else takes the generic ones (the split sweeps stay).
+inline KernelChoice choose_kernels(const Plan& pl, const char* mi355_kernels) {
+  KernelChoice k = served_kernels(pl.r5, pl.M1, pl.M2, pl.C, pl.split5);
+  const std::string sel = mi355_kernels ? mi355_kernels : "v2";
+  if (sel != "v2" && sel != "v2rows") k.rows = RowKernels::kGeneric;
+  if (sel != "v2" && sel != "v2cols" && k.resident_cols()) k.cols = ColKernels::kGeneric;
+  return k;
 }
 
 }  // namespace mi355

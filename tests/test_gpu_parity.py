@@ -338,17 +338,17 @@ def test_c3_136279841_full_size():
 @pytest.mark.parametrize("p,plan,shape", [(30402457, None, "m1=512:m2=2048:c=8"), (30402457, "m2=2048,c=4", "m1=512:m2=2048:c=4"),
                                           (100000007, None, "m1=1280:m2=2048:c=4"), (38000009, "m2=2048,c=2", "m1=512:m2=2048:c=2")])
 def test_rows_of_2048_two_to_a_tile(p, plan, shape, monkeypatch):
-    """rows of 2048 on the register-resident row kernel (kernels_v2.hip, RL = 1: two rows per 4096-pair tile; the reference's
-    forward1024 / sqr512 shapes, kernels/marin.cl:1190,1517): n = 2^21 with register-resident and with generic columns, n = 5 2^20
-    (p ~ 100 M) with the radix-5 columns -- squarings, x a, the LL step (subtraction folded into the next sweep), multiplicand and mul
-    against the oracle's digits, and against the generic rows (MI355_TUNE bit 6) on the same inputs."""
+    """rows of 2048 on the register-resident row kernels: n = 2^21 with register-resident and with generic columns, two rows per 4096-pair
+    tile (kernels_v2.hip, RL = 1; the reference's forward1024 / sqr512 shapes, kernels/marin.cl:1190,1517), and n = 5 2^20 (p ~ 100 M,
+    M1 = 1280) with the radix-5 columns, one row per tile (k2_rows2048_planes) -- squarings, x a, the LL step, multiplicand and mul
+    against the oracle's digits, and against the generic rows (MI355_KERNELS=v2cols: the same columns) on the same inputs."""
     o = orc.Oracle(p, 3)
     rng = np.random.default_rng(p)
     w = o.widths().astype(np.uint64)
     d0 = (rng.integers(0, 1 << 62, o.n, dtype=np.uint64) & ((np.uint64(1) << w) - np.uint64(1))) | (w << np.uint64(32))
     with Engine(p, 4, plan=plan) as e:
         assert shape in e.describe(), e.describe()
-        monkeypatch.setenv("MI355_TUNE", "64")
+        monkeypatch.setenv("MI355_KERNELS", "v2cols")
         with Engine(p, 4, plan=plan) as g:
             e.set_digits(0, d0); g.set_digits(0, d0); o.set_digits(0, d0)
             for it in range(3):
@@ -365,33 +365,6 @@ def test_rows_of_2048_two_to_a_tile(p, plan, shape, monkeypatch):
             e.square_mul(0); o.square_mul(0)
             assert np.array_equal(e.digits(0), o.digits(0))
             assert e.res64(0) == o.res64(0)
-
-
-@pytest.mark.parametrize("p", [30402457, 100000007])
-def test_rows_of_2048_one_plane_per_thread_forced(p, monkeypatch):
-    """k2_rows2048_planes forced (MI355_TUNE bit 14) where the default keeps two rows to a tile (n = 2^21, 5 2^20): more than one round of
-    tiles per CU, radix-8 and radix-5 columns around it -- squarings, x a, LL step, multiplicand / mul against the oracle's digits."""
-    o = orc.Oracle(p, 3)
-    rng = np.random.default_rng(p + 1)
-    w = o.widths().astype(np.uint64)
-    d0 = (rng.integers(0, 1 << 62, o.n, dtype=np.uint64) & ((np.uint64(1) << w) - np.uint64(1))) | (w << np.uint64(32))
-    monkeypatch.setenv("MI355_TUNE", "16384")
-    with Engine(p, 4) as e:
-        e.set_digits(0, d0); o.set_digits(0, d0)
-        for it in range(3):
-            e.square_mul(0); o.square_mul(0)
-        assert np.array_equal(e.digits(0), o.digits(0))
-        e.square_mul(0, 3); o.square_mul(0, 3)
-        e.sub(0, 2); o.sub(0, 2)
-        e.square_mul(0); o.square_mul(0)
-        assert np.array_equal(e.digits(0), o.digits(0))
-        e.copy(1, 0); o.copy(1, 0)
-        e.square_mul(1); o.square_mul(1)
-        e.set_multiplicand(2, 1); o.set_multiplicand(2, 1)
-        e.mul(0, 2, 3); o.mul(0, 2, 3)
-        e.square_mul(0); o.square_mul(0)
-        assert np.array_equal(e.digits(0), o.digits(0))
-        assert e.res64(0) == o.res64(0)
 
 
 def test_full_size_properties_no_oracle():

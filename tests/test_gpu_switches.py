@@ -1,7 +1,7 @@
-"""The environment switches of the engine (README.md, "Switches": MI355_KERNELS, MI355_TUNE bits, MI355_BOOST, MI355_HOST_CARRY; MI355_THREADS
-is read once per process and is not varied here) select kernels, tile orders and thread mappings, never results: every setting -- alone and in the combinations
-that can meet in one engine -- gives the oracle's digit vectors on shapes of every kernel set ("combinations untested").
-The switches are read when an engine is created.  Needs a real MI355X:  python -m pytest tests -m gpu"""
+"""The environment switches of the engine (README.md, "Switches": MI355_KERNELS, MI355_TUNE bits 0 and 5, MI355_HOST_CARRY) select kernels,
+tile orders and the read-back path, never results: every setting -- alone and in every combination -- gives the oracle's digit vectors on
+shapes of every kernel set ("combinations untested").  The switches are read when an engine is created.
+Needs a real MI355X:  python -m pytest tests -m gpu"""
 import itertools
 
 import numpy as np
@@ -11,17 +11,16 @@ import orc
 
 pytestmark = pytest.mark.gpu
 
-# exponent, plan: radix-8 columns + rows of 4096 (R = 2: the one shape whose front order bit 5 changes), rows of 2048 (two to a tile /
-# planes: bits 6, 13, 14), radix-4 columns and rows (bits 7-11), radix-5 columns of 1280 x 4 and 2560 x 2 (bit 5), generic small tiles
-# (bits 3, 4), runs of two digits (C = 1: the carry-fix path)
+# exponent, plan: radix-8 columns + rows of 4096 (R = 2: the one shape whose front order bit 5 changes), rows of 2048 (one to a tile),
+# radix-4 columns and rows (plane forms; the pair-form columns at 256 x 4096, the last entry), radix-5 columns of 1280 x 4 and 2560 x 2
+# (bit 5), generic small tiles, runs of two digits (C = 1: the carry-fix path)
 SHAPES = [(300007, "m2=8,c=4"), (300007, "m2=4096"), (1200007, "m2=2048,c=4"), (600011, "m2=2048"), (300007, "m2=1024"), (132049, "m2=16,c=4"),
-          (800283, "m2=16,c=4"), (800283, "m2=8,c=2"), (9941, "m2=16,c=4"), (9941, "m2=128,c=2"), (521, "m2=8,c=2"), (127, "m2=2,c=1")]
+          (800283, "m2=16,c=4"), (800283, "m2=8,c=2"), (9941, "m2=16,c=4"), (9941, "m2=128,c=2"), (521, "m2=8,c=2"), (127, "m2=2,c=1"),
+          (30402457, "m2=4096")]
 
 KERNELS = [None, "generic", "v2rows", "v2cols"]
-TUNE_SINGLE = [0, 1, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 8192, 16384]
-# bits that can act on one engine together: tile orders x boost x thread mappings x forced forms
-TUNE_COMBOS = [1 | 4 | 32, 1 | 32 | 64, 8 | 16, 4 | 512 | 2048, 256 | 1024, 1 | 4 | 8192, 32 | 16384, 1 | 4 | 8 | 16 | 32 | 64 | 128,
-               1 | 4 | 32 | 512 | 2048 | 16384]
+TUNE = [0, 1, 32, 33]   # tile orders of the back (bit 0) and front (bit 5) sweeps
+HOST_CARRY = [None, "1"]
 
 
 def Engine(*a, **k):
@@ -72,23 +71,22 @@ def check(refs, p, plan, label):
     assert g64 == r64, (p, plan, label)
 
 
+def set_switches(monkeypatch, ks, tune, host):
+    for name, value in (("MI355_KERNELS", ks), ("MI355_TUNE", tune), ("MI355_HOST_CARRY", host)):
+        if value is None: monkeypatch.delenv(name, raising=False)
+        else: monkeypatch.setenv(name, str(value))
+
+
 @pytest.mark.parametrize("p,plan", SHAPES)
 def test_every_switch_alone_gives_the_same_digits(p, plan, refs, monkeypatch):
-    for ks in KERNELS:
-        for tune in TUNE_SINGLE:
-            if ks is None: monkeypatch.delenv("MI355_KERNELS", raising=False)
-            else: monkeypatch.setenv("MI355_KERNELS", ks)
-            monkeypatch.setenv("MI355_TUNE", str(tune))
-            check(refs, p, plan, "kernels=%s tune=%d" % (ks, tune))
+    alone = [(None, None, None)] + [(ks, None, None) for ks in KERNELS[1:]] + [(None, t, None) for t in TUNE] + [(None, None, "1")]
+    for ks, tune, host in alone:
+        set_switches(monkeypatch, ks, tune, host)
+        check(refs, p, plan, "kernels=%s tune=%s host_carry=%s" % (ks, tune, host))
 
 
 @pytest.mark.parametrize("p,plan", SHAPES)
 def test_switch_combinations_give_the_same_digits(p, plan, refs, monkeypatch):
-    for ks, tune, boost, host in itertools.product(KERNELS[:2] + KERNELS[3:], TUNE_COMBOS, ("25", "100"), (None, "1")):
-        if ks is None: monkeypatch.delenv("MI355_KERNELS", raising=False)
-        else: monkeypatch.setenv("MI355_KERNELS", ks)
-        monkeypatch.setenv("MI355_TUNE", str(tune))
-        monkeypatch.setenv("MI355_BOOST", boost)
-        if host is None: monkeypatch.delenv("MI355_HOST_CARRY", raising=False)
-        else: monkeypatch.setenv("MI355_HOST_CARRY", host)
-        check(refs, p, plan, "kernels=%s tune=%d boost=%s host_carry=%s" % (ks, tune, boost, host))
+    for ks, tune, host in itertools.product(KERNELS, TUNE, HOST_CARRY):
+        set_switches(monkeypatch, ks, tune, host)
+        check(refs, p, plan, "kernels=%s tune=%d host_carry=%s" % (ks, tune, host))

@@ -100,6 +100,98 @@ def test_plan_weight_tables_and_digit_info_words():
     assert "m1=1280:m2=8:c=4 digits=20480 di_checked=20480" in out and "m1=2560:m2=8:c=2 digits=40960 di_checked=40960" in out   # radix-5 columns
 
 
+def _parent_kernels(r5, m1, m2, c, split5, sel):
+    """the kernel choice of the engine before plan.hpp choose_kernels existed, restated from the shape tests that the launchers of
+    kernels_v2/v3/v5.hip made on every launch (with MI355_TUNE = 0), column and row sets in the order they were tried"""
+    sel = "v2" if sel is None else sel
+    cols, rows = "generic", "generic"
+    if split5:
+        cols = "split"
+    elif sel in ("v2", "v2cols"):
+        if r5 == 5 and (m1, c) in ((1280, 4), (2560, 2)) and m2 >= 8:
+            cols = "radix5-%d" % m1
+        elif r5 == 1 and m1 == 256 and c == 4 and m2 >= 8:
+            cols = "radix4-planes" if m2 // 4 <= 512 else "radix4-pairs"
+        elif r5 == 1 and m1 in (512, 1024, 2048) and m1 * c == 4096 and m2 >= 2 * c:
+            cols = "radix8-%d" % m1
+    if sel in ("v2", "v2rows"):
+        if m2 == 1024:
+            rows = "radix4-planes" if m1 < 512 else "radix4-pairs"
+        elif m2 in (4096, 8192):
+            rows = "rows%d" % m2
+        elif m2 == 2048 and (m1 < 512 or m1 == 1280):
+            rows = "rows2048-one"
+        elif m2 == 2048 and m1 % 2 == 0 and m1 >= 512:
+            rows = "rows2048-two"
+    return cols, rows
+
+
+def _gpu_test_plans():
+    """every (exponent, plan) the GPU tests of the Goldilocks engine name: module-level shape lists and parametrized cases"""
+    import test_gpu_operand_edges as oe
+    import test_gpu_parity as gp
+    import test_gpu_switches as gs
+    cases = {(p, plan) for p, plan in gs.SHAPES} | {(p, spec) for p, spec, _ in oe.SHAPES.values()} | set(gp.SMALL_CASES)
+    cases |= {(oe._p_max(n), spec) for n, spec, _ in oe.FULL}
+    for mod in (gp, oe):
+        for fn in vars(mod).values():
+            for mark in getattr(fn, "pytestmark", []):
+                if mark.name != "parametrize":
+                    continue
+                names = [a.strip() for a in mark.args[0].split(",")] if isinstance(mark.args[0], str) else list(mark.args[0])
+                if "p" not in names or "odd" in names:   # ("odd": the second field family)
+                    continue
+                for vals in mark.args[1]:
+                    vals = vals if len(names) > 1 else (vals,)
+                    d = dict(zip(names, vals))
+                    if d["p"] < 2**32:
+                        cases.add((d["p"], d.get("plan")))
+    return cases
+
+
+def test_kernel_choice_of_every_tested_plan_matches_the_parent_predicates():
+    """plan.hpp choose_kernels: the variants of the column and row sweeps for the automatic plan of every exponent of the reference's size
+    table, for every (exponent, plan) the GPU tests name, and for each MI355_KERNELS value on a few plans -- against the predicates the
+    engine tested on every launch before (restated above).  The labels of the operand-edge shapes are facts of the choice, and every kernel
+    variant is reached by some GPU test without a switch."""
+    import json
+    import test_gpu_operand_edges as oe
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_outputs.json")))
+    auto = {(int(p), None) for p, n in gold["transform_size"].items() if int(n) > 0}
+    tested = _gpu_test_plans()
+    sels = [None, "v2", "v2rows", "v2cols", "generic", "", "v3"]
+    narrowed = {(p, plan, sel) for p, plan in [(9815459, None), (136279841, None), (205271257, None), (332000003, None), (30402457, None),
+                                               (4000000007, None), (300007, "m2=1024"), (300007, "m2=2048")] for sel in sels}
+    queries = sorted({(p, plan, None) for p, plan in auto | tested} | narrowed, key=str)
+    args = ["k:%d%s%s" % (p, ":" + plan if plan else "", "" if sel is None else "@" + sel) for p, plan, sel in queries]
+    got = {}
+    for (p, plan, sel), line in zip(queries, _build_and_run("plan_query.cpp", args).splitlines()):
+        f = dict(t.split("=", 1) for t in line.split()[2:])
+        want = _parent_kernels(int(f["r5"]), int(f["m1"]), int(f["m2"]), int(f["c"]), f["split5"] == "1", sel)
+        assert (f["cols"], f["rows"]) == want, (p, plan, sel, line)
+        got[(p, plan, sel)] = want
+    assert len(got) == len(queries)
+    labels = {"generic-c1": ("generic", "generic"), "generic-c2": ("generic", "generic"), "radix8-cols": ("radix8-1024", "generic"),
+              "radix8-rows4096": ("generic", "rows4096"), "radix4-cols256": ("radix4-planes", "generic"),
+              "radix4-rows1024": ("generic", "radix4-planes"), "rows2048-planes": ("generic", "rows2048-one"),
+              "radix5-cols1280": ("radix5-1280", "generic"), "radix5-cols2560": ("radix5-2560", "generic"),
+              "rows8192": ("generic", "rows8192"), "split5": ("split", "generic")}
+    assert sorted(labels) == sorted(oe.SHAPES)
+    for label, (p, spec, _) in oe.SHAPES.items():
+        assert got[(p, spec, None)] == labels[label], label
+    # the full-size shapes: C2, C3, C4, rows of 2048 two to a tile at n = 2^21, one to a tile at n = 5 2^20, the split sweeps
+    assert got[(9815459, None, None)] == ("radix4-planes", "radix4-planes") and got[(136279841, None, None)] == ("radix8-1024", "rows4096")
+    assert got[(205271257, None, None)] == ("radix5-1280", "rows4096") and got[(30402457, None, None)] == ("radix8-512", "rows2048-two")
+    assert got[(100000007, None, None)] == ("radix5-1280", "rows2048-one") and got[(4000000007, None, None)] == ("split", "rows8192")
+    assert got[(30402457, "m2=4096", None)] == ("radix4-pairs", "rows4096")
+    assert got[(136279841, None, "generic")] == ("generic", "generic") and got[(136279841, None, "v2rows")] == ("generic", "rows4096")
+    assert got[(205271257, None, "v2cols")] == ("radix5-1280", "generic") and got[(4000000007, None, "generic")] == ("split", "generic")
+    cols = {"generic", "split", "radix8-512", "radix8-1024", "radix8-2048", "radix4-pairs", "radix4-planes", "radix5-1280", "radix5-2560"}
+    rows = {"generic", "radix4-pairs", "radix4-planes", "rows4096", "rows8192", "rows2048-one", "rows2048-two"}
+    assert {got[(p, plan, None)][0] for p, plan in tested} == cols
+    assert {got[(p, plan, None)][1] for p, plan in tested} == rows
+
+
 def test_product_library_and_sources_hold_no_rejected_experiments():
     """The experiments that were measured and did not make the product (cooperative one-launch squaring, back + front in one launch;
     DESIGN.md section 8) and the A/B build macros of rejected variants are gone: the library exports and contains nothing of them, and no
