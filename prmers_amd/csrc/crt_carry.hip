@@ -173,29 +173,6 @@ __global__ void __launch_bounds__(256) k_crt_residual(Geom g, uint64_t* __restri
   if (c) digits[size_t(run) * kRun] += c;
 }
 
-static uint64_t host_pow61(uint64_t a, uint64_t e) {
-  uint64_t r = 1;
-  while (e) { if (e & 1) r = mul61(r, a); a = mul61(a, a); e >>= 1; }
-  return r;
-}
-
-Geom make_geom(uint32_t p, size_t n, uint32_t odd, uint32_t a) {
-  if (odd != 1 && odd != 3 && odd != 9) throw std::runtime_error("crt: odd radix must be 1, 3 or 9");
-  if (n == 0 || n % odd || n % kRun || n > 0xfffffff0ull) throw std::runtime_error("crt: bad transform size");
-  uint32_t ln = 0;
-  while ((size_t(odd) << ln) < n) ++ln;
-  if ((size_t(odd) << ln) != n) throw std::runtime_error("crt: transform size must be odd * 2^k");
-  if (a == 0) throw std::runtime_error("crt: factor must be >= 1");
-  Geom g;
-  g.p = p; g.n = uint32_t(n); g.odd = odd; g.ln = ln; g.a = a;
-  auto inv_small = [](uint64_t x, uint64_t m) { for (uint64_t y = 1; y < m; ++y) if (x * y % m == 1) return y; return uint64_t(0); };
-  g.l61 = uint32_t(inv_small(n % 61, 61)); g.l31 = uint32_t(inv_small(n % 31, 31));
-  g.inv31 = host_pow61(M31, M61 - 2);
-  g.q = uint32_t(p / n); g.t = uint32_t(p % n);
-  g.lt61 = uint32_t(uint64_t(g.l61) * (g.t % 61) % 61); g.lt31 = uint32_t(uint64_t(g.l31) * (g.t % 31) % 31);
-  return g;
-}
-
 void crt_carry_launch(const Geom& g, const uint64_t* in61, const uint32_t* in31, uint64_t* digits, uint64_t* carry, uint64_t* residual,
                       bool fold_residual, hipStream_t s) {
   const size_t nruns = (size_t(g.n) + kRun - 1) / kRun;

@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "crt_arith.hpp"
 #include "crt_engine.hpp"
 #include "crt_field.hpp"
 
@@ -48,38 +49,6 @@ __device__ __forceinline__ typename F::C tw_m(const typename F::C* __restrict__ 
 
 __device__ __forceinline__ uint32_t brev(uint32_t i, uint32_t bits) { return bits ? (__brev(i) >> (32 - bits)) : 0u; }
 
-// ---- odd axis: DFT of length 1, 3 or 9 with scalar roots --------------------------------------------------------------------
-// DFT-3 with w + w^2 = -1: y0 = x0 + (x1 + x2), y1,2 = x0 - (x1 + x2) / 2 +- c (x1 - x2), c = (w - w^2) / 2: one scalar product.
-// DFT-9 = 3 x 3 (Cooley-Tukey): three DFT-3 over a1 (a = 3 a1 + a0), twiddles r^(a0 k0) (four non-trivial), three DFT-3 over a0
-// -> X[k0 + 3 k1]: 10 scalar-times-complex products instead of the 64 of the direct sums.  (Reference: fft-middle.cl:663-720.)
-template <class F>
-__device__ __forceinline__ void dft3(typename F::C& x0, typename F::C& x1, typename F::C& x2, typename F::S c) {
-  using C = typename F::C;
-  const C t1 = cadd<F>(x1, x2), t2 = cscale<F>(csub<F>(x1, x2), c);
-  const C u = csub<F>(x0, chalf<F>(t1));
-  x0 = cadd<F>(x0, t1); x1 = cadd<F>(u, t2); x2 = csub<F>(u, t2);
-}
-template <class F, int ODD>
-__device__ __forceinline__ void dft_odd(typename F::C (&x)[ODD], const typename F::S* __restrict__ r /* r^e, e < 9 */, typename F::S c3) {
-  using C = typename F::C;
-  if (ODD == 3) {
-    dft3<F>(x[0], x[1], x[2], c3);
-  } else if (ODD == 9) {
-#pragma unroll
-    for (int a0 = 0; a0 < 3; ++a0) dft3<F>(x[a0], x[a0 + 3], x[a0 + 6], c3);     // x[a0 + 3 k0] <- Y[a0][k0]
-    x[1 + 3] = cscale<F>(x[1 + 3], r[1]); x[1 + 6] = cscale<F>(x[1 + 6], r[2]);
-    x[2 + 3] = cscale<F>(x[2 + 3], r[2]); x[2 + 6] = cscale<F>(x[2 + 6], r[4]);
-    C y[9];
-#pragma unroll
-    for (int k0 = 0; k0 < 3; ++k0) {
-      C z0 = x[3 * k0], z1 = x[3 * k0 + 1], z2 = x[3 * k0 + 2];
-      dft3<F>(z0, z1, z2, c3);
-      y[k0] = z0; y[k0 + 3] = z1; y[k0 + 6] = z2;                                // X[k0 + 3 k1]
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) x[k] = y[k];
-  }
-}
 
 // weight exponents of the digits b + m t, t = 0 .. odd-1, kept incrementally: s = p j mod n advances by p m mod n
 struct ColumnWalk {
@@ -425,8 +394,7 @@ using crt::F31; using crt::F61; using crt::M31; using crt::M61;
 
 void chk(hipError_t e, const char* what) { if (e != hipSuccess) throw std::runtime_error(std::string("crt engine: ") + what + ": " + hipGetErrorString(e)); }
 
-uint64_t pow61(uint64_t a, uint64_t e) { uint64_t r = 1; while (e) { if (e & 1) r = crt::mul61(r, a); a = crt::mul61(a, a); e >>= 1; } return r; }
-uint32_t pow31(uint32_t a, uint64_t e) { uint32_t r = 1; while (e) { if (e & 1) r = crt::mul31(r, a); a = crt::mul31(a, a); e >>= 1; } return r; }
+using crt::pow31; using crt::pow61;
 
 // an element of exact order 2^k in the norm-1 subgroup of Z/p[i] (order p + 1 = 2^61 resp. 2^31): (t + i)^((p - 1) 2^(bits - k)) for the first t
 // that gives exact order 2^k; the exponent is applied as (p - 1) first (z^(p-1) = conj(z) / z has norm 1), then by squaring
@@ -462,16 +430,6 @@ typename F::C normalise_root(typename F::C r, unsigned ln, typename F::C want) {
     p = crt::cmul<F>(p, w8sq);
   }
   throw std::runtime_error("crt engine: no 8th root of the expected form");
-}
-
-template <class S, class POW>
-S odd_root(unsigned odd, S modulus, POW pw) {   // a primitive odd-th root of unity among the scalars (odd | p - 1)
-  for (S g = 2;; ++g) {
-    const S r = pw(g, (uint64_t(modulus) - 1) / odd);
-    bool ok = r != 1;
-    for (unsigned d = 2; ok && d < odd; ++d) if (odd % d == 0 && pw(r, odd / d) == 1) ok = false;
-    if (ok && pw(r, odd) == 1) return r;
-  }
 }
 
 }  // namespace
@@ -570,17 +528,10 @@ CrtEngine::CrtEngine(uint32_t p, size_t reg_count, uint32_t odd, size_t n_forced
     gr.logH2 = logH2; gr.logH1 = gr.logh - logH2;
     gr.minv = 0;
     if (odd > 1) for (uint32_t y = 1; y < odd; ++y) if ((uint64_t(gr.m % odd) * y) % odd == 1) gr.minv = y;
-    const uint64_t r61 = odd > 1 ? odd_root<uint64_t>(odd, M61, pow61) : 1;
-    const uint32_t r31 = odd > 1 ? odd_root<uint32_t>(odd, M31, pow31) : 1;
-    for (unsigned k = 0; k < 9; ++k) {
-      gr.r61[k] = pow61(r61, k % odd); gr.r61i[k] = pow61(r61, (odd - k % odd) % odd);
-      gr.r31[k] = pow31(r31, k % odd); gr.r31i[k] = pow31(r31, (odd - k % odd) % odd);
-    }
     {
-      const unsigned cube = odd == 9 ? 3 : 1;            // w3 = r^3 for radix 9, r itself for radix 3
-      const uint64_t w61 = gr.r61[cube % 9], w61sq = crt::mul61(w61, w61);
-      const uint32_t w31 = gr.r31[cube % 9], w31sq = crt::mul31(w31, w31);
-      gr.c3_61 = odd > 1 ? F61::half(F61::sub(w61, w61sq)) : 0; gr.c3_31 = odd > 1 ? F31::half(F31::sub(w31, w31sq)) : 0;
+      const crt::OddTables ot = crt::make_odd_tables(odd);   // crt_arith.hpp: the tables the CPU and device tests of dft_odd use too
+      for (unsigned k = 0; k < 9; ++k) { gr.r61[k] = ot.r61[k]; gr.r61i[k] = ot.r61i[k]; gr.r31[k] = ot.r31[k]; gr.r31i[k] = ot.r31i[k]; }
+      gr.c3_61 = ot.c3_61; gr.c3_31 = ot.c3_31;
       gr.mm = gr.m % odd;
       gr.pm = uint32_t((uint64_t(p) * gr.m) % n);
       gr.lpm61 = uint32_t(uint64_t(im.g.l61) * (gr.pm % 61) % 61); gr.lpm31 = uint32_t(uint64_t(im.g.l31) * (gr.pm % 31) % 31);

@@ -4,7 +4,10 @@
 // All values canonical ([0, p)).  2 has order 61 resp. 31, so n-th roots of two are powers of two and an IBDWT weight is a
 // bit rotation; the 2-power roots of unity live in the norm-1 subgroup of Z/p[i] (order p + 1 = 2^61 resp. 2^31).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+
+#include <stdexcept>
 
 #include "gf.hpp"
 
@@ -46,21 +49,21 @@ struct F61 {
   using S = uint64_t;
   struct alignas(16) C { uint64_t re, im; };
   static constexpr uint64_t M = M61;
-  static GF_HD S add(S a, S b) { const S s = a + b; return s >= M ? s - M : s; }
-  static GF_HD S sub(S a, S b) { return a >= b ? a - b : a + M - b; }
-  static GF_HD S neg(S a) { return a ? M - a : 0; }
-  static GF_HD S mul(S a, S b) { return mul61(a, b); }
-  static GF_HD S half(S a) { return (a & 1) ? (a + M) >> 1 : a >> 1; }
+  static GF_HDM S add(S a, S b) { const S s = a + b; return s >= M ? s - M : s; }
+  static GF_HDM S sub(S a, S b) { return a >= b ? a - b : a + M - b; }
+  static GF_HDM S neg(S a) { return a ? M - a : 0; }
+  static GF_HDM S mul(S a, S b) { return mul61(a, b); }
+  static GF_HDM S half(S a) { return (a & 1) ? (a + M) >> 1 : a >> 1; }
 };
 struct F31 {
   using S = uint32_t;
   struct alignas(8) C { uint32_t re, im; };
   static constexpr uint32_t M = M31;
-  static GF_HD S add(S a, S b) { const S s = a + b; return s >= M ? s - M : s; }
-  static GF_HD S sub(S a, S b) { return a >= b ? a - b : a + M - b; }
-  static GF_HD S neg(S a) { return a ? M - a : 0; }
-  static GF_HD S mul(S a, S b) { return mul31(a, b); }
-  static GF_HD S half(S a) { return (a & 1) ? (a + M) >> 1 : a >> 1; }
+  static GF_HDM S add(S a, S b) { const S s = a + b; return s >= M ? s - M : s; }
+  static GF_HDM S sub(S a, S b) { return a >= b ? a - b : a + M - b; }
+  static GF_HDM S neg(S a) { return a ? M - a : 0; }
+  static GF_HDM S mul(S a, S b) { return mul31(a, b); }
+  static GF_HDM S half(S a) { return (a & 1) ? (a + M) >> 1 : a >> 1; }
 };
 
 template <class F> GF_HD typename F::C cadd(typename F::C a, typename F::C b) { return {F::add(a.re, b.re), F::add(a.im, b.im)}; }
@@ -89,19 +92,19 @@ constexpr int kRun = 8;   // digits per thread of the carry sweep
 // s advances by t, l s by l t, and a wrap of s takes n resp. 1 off -- no division after the run's first digit.
 struct DigitWalk {
   uint32_t s, A61, A31;   // p j mod n, l61 s mod 61, l31 s mod 31
-  GF_HD void start(const Geom& g, uint32_t j) {
+  GF_HDM void start(const Geom& g, uint32_t j) {
     s = uint32_t((uint64_t(g.p) * j) % g.n);
     A61 = uint32_t((uint64_t(g.l61) * (s % 61)) % 61); A31 = uint32_t((uint64_t(g.l31) * (s % 31)) % 31);
   }
-  GF_HD uint32_t width(const Geom& g) const {
+  GF_HDM uint32_t width(const Geom& g) const {
     const uint64_t st = uint64_t(s) + g.t;
     return g.q + (st > 0 ? 1u : 0u) + (st > g.n ? 1u : 0u) - (s > 0 ? 1u : 0u);
   }
-  GF_HD uint32_t weight61() const { return s ? (62 - A61) % 61 : 0; }     // l (n - s) = 1 - A (mod 61)
-  GF_HD uint32_t weight31() const { return s ? (32 - A31) % 31 : 0; }
-  GF_HD uint32_t unweight61() const { return s ? (A61 + 60) % 61 : 0; }   // 61 - (1 - A) mod 61 = (A - 1) mod 61
-  GF_HD uint32_t unweight31() const { return s ? (A31 + 30) % 31 : 0; }
-  GF_HD void next(const Geom& g) {
+  GF_HDM uint32_t weight61() const { return s ? (62 - A61) % 61 : 0; }     // l (n - s) = 1 - A (mod 61)
+  GF_HDM uint32_t weight31() const { return s ? (32 - A31) % 31 : 0; }
+  GF_HDM uint32_t unweight61() const { return s ? (A61 + 60) % 61 : 0; }   // 61 - (1 - A) mod 61 = (A - 1) mod 61
+  GF_HDM uint32_t unweight31() const { return s ? (A31 + 30) % 31 : 0; }
+  GF_HDM void next(const Geom& g) {
     uint64_t sn = uint64_t(s) + g.t;
     A61 += g.lt61; A31 += g.lt31;
     if (sn >= g.n) { sn -= g.n; A61 += 60; A31 += 30; }   // l n = 1 (mod 61 / 31)
@@ -111,12 +114,37 @@ struct DigitWalk {
   }
 };
 
-Geom make_geom(uint32_t p, size_t n, uint32_t odd, uint32_t a);   // crt_carry.hip (host)
+// host: the geometry of a transform size (throws on a size or factor the sweep does not take)
+inline uint64_t host_pow61(uint64_t a, uint64_t e) {
+  uint64_t r = 1;
+  while (e) { if (e & 1) r = mul61(r, a); a = mul61(a, a); e >>= 1; }
+  return r;
+}
+
+inline Geom make_geom(uint32_t p, size_t n, uint32_t odd, uint32_t a) {
+  if (odd != 1 && odd != 3 && odd != 9) throw std::runtime_error("crt: odd radix must be 1, 3 or 9");
+  if (n == 0 || n % odd || n % kRun || n > 0xfffffff0ull) throw std::runtime_error("crt: bad transform size");
+  uint32_t ln = 0;
+  while ((size_t(odd) << ln) < n) ++ln;
+  if ((size_t(odd) << ln) != n) throw std::runtime_error("crt: transform size must be odd * 2^k");
+  if (a == 0) throw std::runtime_error("crt: factor must be >= 1");
+  Geom g;
+  g.p = p; g.n = uint32_t(n); g.odd = odd; g.ln = ln; g.a = a;
+  auto inv_small = [](uint64_t x, uint64_t m) { for (uint64_t y = 1; y < m; ++y) if (x * y % m == 1) return y; return uint64_t(0); };
+  g.l61 = uint32_t(inv_small(n % 61, 61)); g.l31 = uint32_t(inv_small(n % 31, 31));
+  g.inv31 = host_pow61(M31, M61 - 2);
+  g.q = uint32_t(p / n); g.t = uint32_t(p % n);
+  g.lt61 = uint32_t(uint64_t(g.l61) * (g.t % 61) % 61); g.lt31 = uint32_t(uint64_t(g.l31) * (g.t % 31) % 31);
+  return g;
+}
+
+#if defined(__HIPCC__)
 // the fused unweight + Garner + carry sweep on device buffers (crt_carry.hip): digits[n], carry[2 * runs], residual[runs]
 void crt_carry_launch(const Geom& g, const uint64_t* in61, const uint32_t* in31, uint64_t* digits, uint64_t* carry, uint64_t* residual,
                       bool fold_residual, hipStream_t s);
 
 void crt_carry_launch_linked(const Geom& g, const uint64_t* in61, const uint32_t* in31, uint64_t* digits, uint64_t* edge, hipStream_t s);
+#endif
 
 }  // namespace crt
 }  // namespace mi355

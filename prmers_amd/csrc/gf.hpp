@@ -18,8 +18,10 @@
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define GF_HD __host__ __device__ __forceinline__
+#define GF_HDM GF_HD   // member functions (a plain C++ compiler must not see "static" twice, or on a non-static member)
 #else
 #define GF_HD static inline
+#define GF_HDM inline
 #endif
 
 namespace gf {

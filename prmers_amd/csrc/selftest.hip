@@ -1,6 +1,8 @@
-// Device self-test of the GF(P) primitives (gf.hpp, gfdft.hpp): the device code paths differ from the host
-// ones (borrow-reusing sub, P left for a negated zero), so they are checked on the GPU itself against 128-bit
-// host arithmetic, modulo P, on edge values and random operands.  Reached through mi355_engine_selftest().
+// Device self-test of the arithmetic the kernels are built from: the GF(P) primitives (gf.hpp, gfdft.hpp), their consumers in the radix-8 kernels
+// (kernels_v2_common.hpp: dft8p, seam64, p2_mul, dft4) and the second field family (crt_field.hpp, crt_arith.hpp).  The device code paths differ
+// from the host ones (inline-assembly reductions, borrow-reusing sub, P left for a negated zero; intrinsics and 64-bit shifts in the second family),
+// so the case families of selftest_cases.hpp are evaluated on the GPU itself, one lane per case, and checked against 128-bit host arithmetic --
+// the second family also word for word against the host evaluation of the same templates.  Reached through mi355_engine_selftest().
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -8,99 +10,123 @@
 #include <string>
 #include <vector>
 
-#include "gfdft.hpp"
+#include "kernels_v2_common.hpp"
+#include "selftest_cases.hpp"
 
 namespace mi355 {
 
 namespace {
-constexpr int kOps = 6 + 192;   // add, sub, mul, add_lazy, fold, mul_u32, then mul_pow2 for every shift
+using namespace cases;
 
-__global__ void k_selftest(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, uint64_t* __restrict__ out, int n) {
+template <class Fam>
+__global__ void k_selftest_family(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, const uint64_t* __restrict__ aux, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint64_t x = a[i], y = b[i];
-  uint64_t* o = out + size_t(i) * kOps;
-  o[0] = gf::add(x, y);
-  o[1] = gf::sub(x, y);
-  o[2] = gf::mul(x, y);
-  o[3] = gf::add_lazy(x, y);
-  o[4] = gf::fold(x + y);                 // any 64-bit value
-  o[5] = gf::mul_u32(x, uint32_t(y));
-  for (unsigned s = 0; s < 192; ++s) o[6 + s] = gf::mul_pow2(x, s);   // runtime s: every branch of mul_pow2
+  Fam::eval(in + size_t(i) * Fam::IN, out + size_t(i) * Fam::OUT, aux);
 }
 
-__global__ void k_selftest_dft8(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, int n) {
+__global__ void k_selftest_dft4(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint64_t f[8], g[8], h[8];
-  for (int j = 0; j < 8; ++j) f[j] = g[j] = h[j] = in[size_t(i) * 8 + j];
-  gf::dft8<false, 0>(f); gf::dft8<true, 1>(g); gf::dft8<false, 2>(h);
-  for (int j = 0; j < 8; ++j) { out[size_t(i) * 24 + j] = f[j]; out[size_t(i) * 24 + 8 + j] = g[j]; out[size_t(i) * 24 + 16 + j] = h[j]; }
+  uint64_t f[4], g[4];
+  for (int j = 0; j < 4; ++j) f[j] = g[j] = in[size_t(i) * 4 + j];
+  v2::dft4<false>(f[0], f[1], f[2], f[3]); v2::dft4<true>(g[0], g[1], g[2], g[3]);
+  for (int j = 0; j < 4; ++j) { out[size_t(i) * 8 + j] = f[j]; out[size_t(i) * 8 + 4 + j] = g[j]; }
 }
 
-typedef unsigned __int128 u128;
-uint64_t mulmod(uint64_t a, uint64_t b) { return uint64_t((u128(a) * b) % gf::P); }
+// eight waves to a work-group, the wave index made scalar as the kernels do, so that seam64's switch is taken wave-uniformly
+__global__ void __launch_bounds__(512) k_selftest_chain(const uint64_t* __restrict__ tuples, size_t ntuples, const uint64_t* __restrict__ fac, uint64_t* __restrict__ out) {
+  const int g = blockIdx.x * 512 + threadIdx.x;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) & 7);
+  const uint64_t* ta = tuples + 8 * GfChain::tuple_of(g, 0, ntuples);
+  const uint64_t* tb = tuples + 8 * GfChain::tuple_of(g, 1, ntuples);
+  uint64_t* o = out + size_t(g) * GfChain::OUT;
+  v2::P2 x[8], y[8];
+  uint64_t sw[8];
+  for (int k = 0; k < 8; ++k) { x[k] = y[k] = {ta[k], tb[k]}; sw[k] = fac[size_t(g) * 8 + k]; }
+  v2::dft8p<false, 1>(x);
+  v2::seam64<false, true>(x, wave);
+  for (int k = 0; k < 8; ++k) { o[k] = x[k].a; o[8 + k] = x[k].b; }
+  v2::dft8p<false, 2>(x);
+  for (int k = 0; k < 8; ++k) { x[k] = v2::p2_mul(x[k], sw[k]); o[16 + k] = x[k].a; o[24 + k] = x[k].b; }
+  v2::dft8p<true>(y);
+  v2::seam64<true>(y, wave);
+  v2::dft8p<true, 2>(y);
+  for (int k = 0; k < 8; ++k) { y[k] = v2::p2_mul(y[k], sw[k]); o[32 + k] = y[k].a; o[40 + k] = y[k].b; }
+}
+
 void chk(hipError_t e, const char* what) { if (e != hipSuccess) throw std::runtime_error(std::string("selftest: ") + what + ": " + hipGetErrorString(e)); }
+
+struct DevWords {   // device copy of a word vector (freed on every way out)
+  uint64_t* p = nullptr;
+  explicit DevWords(size_t n) { chk(hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * 8), "hipMalloc"); }
+  explicit DevWords(const std::vector<uint64_t>& v) : DevWords(v.size()) { if (!v.empty()) chk(hipMemcpy(p, v.data(), v.size() * 8, hipMemcpyHostToDevice), "copy"); }
+  ~DevWords() { (void)hipFree(p); }
+  DevWords(const DevWords&) = delete;
+  DevWords& operator=(const DevWords&) = delete;
+  void fetch(std::vector<uint64_t>& v, const char* what) const { chk(hipMemcpy(v.data(), p, v.size() * 8, hipMemcpyDeviceToHost), what); }
+};
+
+// one family: cases up, one lane per case, results down, check; in / out are left for the caller
+template <class Fam>
+void run_family(const char* name, std::vector<uint64_t>& in, std::vector<uint64_t>& out) {
+  std::vector<uint64_t> aux;
+  in.clear(); Fam::fill(in); Fam::aux(aux);
+  const size_t n = in.size() / Fam::IN;
+  out.assign(n * Fam::OUT, 0);
+  {
+    DevWords din(in), daux(aux), dout(out.size());
+    hipLaunchKernelGGL(k_selftest_family<Fam>, dim3(uint32_t((n + 63) / 64)), dim3(64), 0, 0, din.p, dout.p, daux.p, int(n));
+    chk(hipGetLastError(), name);
+    dout.fetch(out, name);
+  }
+  if (Fam::kHostEqualsDevice) {   // plain C++ on both sides: the same words
+    std::vector<uint64_t> h(Fam::OUT);
+    for (size_t i = 0; i < n; ++i) {
+      Fam::eval(in.data() + i * Fam::IN, h.data(), aux.data());
+      for (int k = 0; k < Fam::OUT; ++k)
+        if (h[k] != out[i * Fam::OUT + k])
+          throw std::runtime_error(std::string("selftest: ") + name + msg(": device and host evaluation differ, case %zu word %d: %016llx / %016llx", i, k, MI355_X(out[i * Fam::OUT + k]), MI355_X(h[k])));
+    }
+  }
+  const std::string err = Fam::check(in.data(), out.data(), n);
+  if (!err.empty()) throw std::runtime_error("selftest: " + err);
+}
 }  // namespace
 
 // throws std::runtime_error with the first mismatch
 void selftest_primitives(int device) {
   chk(hipSetDevice(device), "hipSetDevice");
-  const uint64_t P = gf::P;
-  std::vector<uint64_t> edge = {0, 1, 2, P - 1, P - 2, P, 0xffffffffull, 0x100000000ull, 0xffffffff00000000ull, 0x8000000000000000ull,
-                                0xfffffffeffffffffull, 0x00000000fffffffeull, 0x123456789abcdef0ull % P,
-                                // operands whose products take the rare paths of gf::mul's tail: 2^64 - 1 = (2^32 + 1)(2^32 - 1) (low half >= P, no
-                                // carry), (P - 1)^2 (borrow out of lo - hh - c), products with an empty low word or an all-ones high word
-                                0x100000001ull, 0x00000001ffffffffull, 0xfffffffe00000001ull, 0x0000000100000000ull + 0xfffffffeull, 0xffffffff00000000ull - 1,
-                                0x00000000ffff0001ull, 0xffff0000ffff0001ull};
-  std::vector<uint64_t> a, b;
-  for (uint64_t x : edge) for (uint64_t y : edge) { a.push_back(x); b.push_back(y); }
-  uint64_t s = 0x9e3779b97f4a7c15ull;
-  for (int i = 0; i < 4096; ++i) { s = s * 6364136223846793005ull + 1442695040888963407ull; a.push_back(s % P); s = s * 6364136223846793005ull + 1442695040888963407ull; b.push_back(s % P); }
-  const int n = int(a.size());
-  uint64_t *da, *db, *dout;
-  chk(hipMalloc(reinterpret_cast<void**>(&da), n * 8), "hipMalloc"); chk(hipMalloc(reinterpret_cast<void**>(&db), n * 8), "hipMalloc");
-  chk(hipMalloc(reinterpret_cast<void**>(&dout), size_t(n) * kOps * 8), "hipMalloc");
-  chk(hipMemcpy(da, a.data(), n * 8, hipMemcpyHostToDevice), "copy"); chk(hipMemcpy(db, b.data(), n * 8, hipMemcpyHostToDevice), "copy");
-  hipLaunchKernelGGL(k_selftest, dim3((n + 63) / 64), dim3(64), 0, 0, da, db, dout, n);
-  std::vector<uint64_t> out(size_t(n) * kOps);
-  chk(hipMemcpy(out.data(), dout, out.size() * 8, hipMemcpyDeviceToHost), "kernel / copy back");
-  std::string err;
-  auto fail = [&](const char* op, int i, unsigned sft) {
-    if (err.empty()) { char buf[160]; std::snprintf(buf, sizeof buf, "%s mismatch: a=%016llx b=%016llx s=%u", op, (unsigned long long)a[i], (unsigned long long)b[i], sft); err = buf; }
-  };
-  for (int i = 0; i < n; ++i) {
-    const uint64_t x = a[i], y = b[i], xm = x % P, ym = y % P;   // operands may be P itself (the lazy zero)
-    const uint64_t* o = &out[size_t(i) * kOps];
-    if (o[0] % P != uint64_t((u128(xm) + ym) % P) || o[0] > P) fail("add", i, 0);
-    if (o[1] % P != uint64_t((u128(xm) + P - ym) % P) || o[1] > P) fail("sub", i, 0);
-    if (o[2] != mulmod(xm, ym)) fail("mul", i, 0);
-    if (o[3] % P != uint64_t((u128(xm) + ym) % P)) fail("add_lazy", i, 0);
-    if (o[4] != (x + y) % P) fail("fold", i, 0);
-    if (o[5] != mulmod(xm, uint32_t(y))) fail("mul_u32", i, 0);
-    for (unsigned sft = 0; sft < 192; ++sft) {
-      const uint64_t r = o[6 + sft], want = mulmod(xm, gf::pow(2, sft));
-      if (r % P != want || (sft != 0 && r > P)) fail("mul_pow2", i, sft);
-    }
+  std::vector<uint64_t> in, out, tuples, dft8_out;
+  run_family<GfScalar>("gf scalars", in, out);
+  run_family<GfDft8>("gf dft8", tuples, dft8_out);
+  {   // v2::dft4
+    in.clear(); GfDft4::fill(in);
+    const size_t n = in.size() / GfDft4::IN;
+    out.assign(n * GfDft4::OUT, 0);
+    DevWords din(in), dout(out.size());
+    hipLaunchKernelGGL(k_selftest_dft4, dim3(uint32_t((n + 63) / 64)), dim3(64), 0, 0, din.p, dout.p, int(n));
+    chk(hipGetLastError(), "gf dft4");
+    dout.fetch(out, "gf dft4");
+    const std::string err = GfDft4::check(in.data(), out.data(), n);
+    if (!err.empty()) throw std::runtime_error("selftest: " + err);
   }
-  // butterflies: canonical and LAZY variants against the host's canonical dft8 (same source, host path)
-  const int nd = 512;
-  std::vector<uint64_t> din(size_t(nd) * 8), dres(size_t(nd) * 24);
-  for (size_t i = 0; i < din.size(); ++i) { s = s * 6364136223846793005ull + 1442695040888963407ull; din[i] = (i < 64) ? edge[i % edge.size()] % P : s % P; }
-  uint64_t *dd, *dr;
-  chk(hipMalloc(reinterpret_cast<void**>(&dd), din.size() * 8), "hipMalloc"); chk(hipMalloc(reinterpret_cast<void**>(&dr), dres.size() * 8), "hipMalloc");
-  chk(hipMemcpy(dd, din.data(), din.size() * 8, hipMemcpyHostToDevice), "copy");
-  hipLaunchKernelGGL(k_selftest_dft8, dim3((nd + 63) / 64), dim3(64), 0, 0, dd, dr, nd);
-  chk(hipMemcpy(dres.data(), dr, dres.size() * 8, hipMemcpyDeviceToHost), "dft8 kernel / copy back");
-  for (int i = 0; i < nd && err.empty(); ++i) {
-    uint64_t f[8], g[8];
-    for (int j = 0; j < 8; ++j) f[j] = g[j] = din[size_t(i) * 8 + j];
-    gf::dft8<false, 0>(f); gf::dft8<true, 0>(g);
-    for (int j = 0; j < 8; ++j)
-      if (dres[size_t(i) * 24 + j] % P != f[j] || dres[size_t(i) * 24 + 8 + j] % P != g[j] || dres[size_t(i) * 24 + 16 + j] % P != f[j]) err = "dft8 mismatch";
+  {   // the lazy outputs through their consumers
+    std::vector<uint64_t> fac; GfChain::factors(fac);
+    const size_t ntuples = tuples.size() / 8;
+    out.assign(size_t(GfChain::kThreads) * GfChain::OUT, 0);
+    DevWords dt(tuples), df(fac), dout(out.size());
+    hipLaunchKernelGGL(k_selftest_chain, dim3(GfChain::kThreads / 512), dim3(512), 0, 0, dt.p, ntuples, df.p, dout.p);
+    chk(hipGetLastError(), "gf chain");
+    dout.fetch(out, "gf chain");
+    const std::string err = GfChain::check(tuples.data(), ntuples, fac.data(), out.data(), dft8_out.data());
+    if (!err.empty()) throw std::runtime_error("selftest: " + err);
   }
-  (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout); (void)hipFree(dd); (void)hipFree(dr);
-  if (!err.empty()) throw std::runtime_error("selftest: " + err);
+  run_family<CrtScalar>("crt scalars", in, out);
+  run_family<CrtCmul>("crt cmul", in, out);
+  run_family<CrtBfly>("crt bfly", in, out);
+  run_family<CrtOdd>("crt dft_odd", in, out);
+  run_family<CrtWalk>("crt DigitWalk", in, out);
 }
 
 }  // namespace mi355

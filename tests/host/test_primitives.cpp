@@ -1,6 +1,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "gfdft.hpp"
+#include "selftest_cases.hpp"
 typedef unsigned __int128 u128;
 static uint64_t ref_mul(uint64_t a, uint64_t b){ return (uint64_t)(((u128)a*b) % gf::P); }
 int main(){
@@ -59,6 +60,23 @@ int main(){
         if (gf::fold(f1[k]) != f0[k]) { if (bad++<5) printf("dft8 LAZY=1 bad\n"); }
         if (gf::fold(f2[k]) != g0[k]) { if (bad++<5) printf("dft8 LAZY=2 bad\n"); }
       }
+    }
+  }
+  // the case families of the device self-test (selftest_cases.hpp) through the host forms: every scalar function over its documented operand
+  // domain (lazy operands anywhere in [0, 2^64), the others up to P, the rare tails of the product), and dft8<INV, LAZY> for both directions and
+  // LAZY = 0, 1, 2 on tuples over the edge alphabet, with the condition that every slot which may be lazy really held a value above P
+  {
+    using namespace mi355::cases;
+    const std::string e1 = run_on_host<GfScalar>(), e2 = run_on_host<GfDft8>();
+    if (!e1.empty()) { bad++; printf("%s\n", e1.c_str()); }
+    if (!e2.empty()) { bad++; printf("%s\n", e2.c_str()); }
+    // v2::dft4 is device-only; its direct sums are checked by the self-test.  mul_pow2(a, 0) is the one call that passes its operand through
+    // un-folded: among the shifts of seam64_const (slot k = 1..7 at wave w, both directions) a zero occurs for wave 0 only -- the case that
+    // seam64's FOLD0 folds by hand
+    for (int w = 0; w < 8; ++w) for (int k = 1; k < 8; ++k) for (int inv = 0; inv < 2; ++inv) {
+      const unsigned s = GfChain::seam_shift(k, w, inv != 0);
+      if (s >= 192 || (s == 0) != (w == 0)) { bad++; printf("seam64 shift of slot %d at wave %d is %u\n", k, w, s); }
+      if (gf::pow(2, s) != gf::pow(gf::root_of_unity(64), inv ? 64 - (k * w) % 64 : (k * w) % 64)) { bad++; printf("seam64 shift of slot %d at wave %d is not omega_64^(k w)\n", k, w); }
     }
   }
   printf(bad? "FAIL %d\n":"OK %d\n", bad); return bad!=0;

@@ -196,6 +196,44 @@ def test_subtraction_matrix_small_shapes(shape, form):
                 _assert_value(e, 0, _red(x - sum(vs), p) ** 2, (shape, form, "accumulated", x.bit_length(), vs))
 
 
+# ---- all-zero and unit registers ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_zero_and_one_through_every_product(shape):
+    """An all-zero register (and the value 1) through square_mul, mul and square_mul_n.  With zeros everywhere every negated shift of the
+    butterflies returns P on the device ("a negated zero is left as P", gf.hpp), so this is the end-to-end companion of the self-test's
+    operands equal to P: the result must be exactly 0 (resp. the closed form).
+    (test_gpu_parity.test_edge_values squares a zero register at p = 1279 only, a shape that none of SHAPES' kernel sets serves.)"""
+    p, spec, _ = SHAPES[shape]
+    Mp = (1 << p) - 1
+    rng = random.Random(zlib.crc32(shape.encode()))
+    y = rng.randrange(Mp)
+    with Engine(p, 6, plan=spec) as e:
+        e.set_int(5, y); e.set_multiplicand(2, 5)
+        e.set(4, 0); e.set_multiplicand(3, 4)                 # a zero multiplicand image
+        for a in (1, 3, 2**32 - 1):
+            e.set(0, 0); e.square_mul(0, a)
+            assert e.get_int(0) == 0, (shape, "0^2", a)
+            e.square_mul(0, a)                                  # the result of a zero squaring as the next operand
+            assert e.get_int(0) == 0, (shape, "0^2 twice", a)
+            e.set(0, 0); e.mul(0, 2, a)
+            assert e.get_int(0) == 0, (shape, "0 * y", a)
+            e.set_int(0, y); e.mul(0, 3, a)
+            assert e.get_int(0) == 0, (shape, "y * 0", a)
+            e.set(0, 0); e.square_mul_n(0, 3, a, 0)
+            assert e.get_int(0) == 0, (shape, "square_mul_n on 0", a)
+            e.set(0, 0); e.square_mul_n(0, 2, a, 2)             # 0 -> -2 -> 4 a - 2
+            _assert_value(e, 0, 4 * a - 2, (shape, "LL steps from 0", a))
+            e.set(0, 1); e.square_mul(0, a)
+            _assert_value(e, 0, a, (shape, "1^2", a))
+            e.set(0, 1); e.mul(0, 2, a)
+            _assert_value(e, 0, y * a, (shape, "1 * y", a))
+            e.set(0, 1); e.square_mul_n(0, 3, a, 0)
+            _assert_value(e, 0, a ** 7, (shape, "square_mul_n on 1", a))
+        e.set(0, 0); e.square_mul(0); e.set(1, 0)
+        assert e.is_equal(0, 1)
+
+
 # ---- full size: the largest exponent of each transform size -----------------------------------------------------------------------
 
 def _p_max(n):

@@ -547,7 +547,21 @@ def test_gmp_pins_at_baseline_exponents(p):
 def test_device_selftest_of_field_primitives():
     """mi355_engine_selftest: the device code paths of gf.hpp / gfdft.hpp (borrow-reusing sub, P for a negated zero,
     lazy sums, every shift of mul_pow2, the LAZY butterflies) against 128-bit host arithmetic on edge and random
-    operands, operands equal to P included."""
+    operands, operands equal to P included.
+
+    The cases are the families of prmers_amd/csrc/selftest_cases.hpp, one lane per case:
+    - every scalar function over its documented operand domain: a lazy operand anywhere in [0, 2^64) (mul in either position, mul_u32,
+      mul_pow2 for all 192 shifts with a runtime and with a compile-time shift, the minuend of sub, one operand of add_lazy, fold), the
+      others up to P itself; the operand list must reach every (borrow, carry) case of the product's tail, else the self-test fails;
+    - dft8<INV, LAZY> for both directions and LAZY = 0, 1, 2 on tuples over an alphabet of values around 0, 2^32, 2^63, P (and P itself)
+      against the direct 8-point sums; slots that gfdft.hpp calls canonical are <= P, and for every slot that may be lazy at least one device
+      output was above P, else the self-test fails naming the slot;
+    - the consumers as k2_rows4096 chains them, with eight waves: dft8p<false, 1>, seam64<false, true> (folded at wave 0), dft8p<false, 2>,
+      p2_mul; dft8p<true>, seam64<true>, dft8p<true, 2>, p2_mul -- products are canonical; v2::dft4 on every 4-tuple of the alphabet;
+    - the second field family: scalars, cmul61 / cmul31, bfly61 and bfly<F, R, INV>, dft_odd, DigitWalk -- the cases of
+      tests/host/test_crt_primitives.cpp, compared with the host evaluation word for word and with the 128-bit sums.
+    Out of scope: the file-local dft5 / dft5p, seam_rows*, seam64w*, seam32w* of the kernel sources (moving them into headers is a refactor of
+    its own); they are covered by the whole-engine tests only."""
     from prmers_amd.engine import load_library
     L = load_library()
     assert L.mi355_engine_selftest(0) == 1, L.mi355_engine_last_error().decode()

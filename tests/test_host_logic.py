@@ -19,8 +19,18 @@ def _build_and_run(src, args=()):
 
 
 def test_field_primitives_and_dft8():
-    """gf::mul / mul_u32 / mul_pow2 (all 192 shifts) / dft8 against 128-bit reference arithmetic."""
+    """gf::mul / mul_u32 / mul_pow2 (all 192 shifts) / dft8 against 128-bit reference arithmetic; every function over its documented operand
+    domain (lazy operands anywhere in [0, 2^64)), dft8<INV, LAZY> on tuples over the edge alphabet with an un-folded value seen in every slot
+    that may hold one, and the shifts of seam64 (zero for wave 0 only)."""
     out = _build_and_run("test_primitives.cpp")
+    assert out.strip().startswith("OK"), out
+
+
+def test_second_family_primitives_at_their_operand_bounds():
+    """crt_field.hpp / crt_arith.hpp on the host against 128-bit arithmetic mod M61 / M31: scalars over any 64-bit value, cmul61 / cmul31 at M61,
+    M61 + 7 and the limb edges, bfly61 and bfly<F, R, INV> for R = 2, 4, 8 with every input at the maximum (a wrapped 64-bit sum shows, 2^64 = 8
+    mod M61), dft_odd<F, 3|9> with the engine's root tables, DigitWalk for every digit of a few sizes.  The device self-test runs the same cases."""
+    out = _build_and_run("test_crt_primitives.cpp")
     assert out.strip().startswith("OK"), out
 
 
