@@ -1,4 +1,4 @@
-// Arithmetic of the second field family that the kernels of crt_engine.hip / crt_rows.hpp are built from, host + gfx950 device and
+// Arithmetic of the second field family that the kernels of crt_kernels.hip (crt_rows.hpp, crt_carry.hpp) are built from, host + gfx950 device and
 // includable by a plain C++ compiler: the 8th-root rotations, the lazy Z/M61 forms with their radix-2/4/8 butterflies, the limb-wise
 // complex products, the generic butterflies and the odd-axis DFTs.  No LDS, grid or table code here: a kernel and a CPU test
 // (tests/host/test_crt_primitives.cpp) instantiate the same templates.
@@ -155,8 +155,6 @@ GF_HD void dft_odd(typename F::C (&x)[ODD], const typename F::S* __restrict__ r 
 }
 
 // ---- host: the scalar tables of the odd axis (CrtEngine's constructor; the tests of dft_odd use the same ones) ----
-inline uint64_t pow61(uint64_t a, uint64_t e) { uint64_t r = 1; while (e) { if (e & 1) r = mul61(r, a); a = mul61(a, a); e >>= 1; } return r; }
-inline uint32_t pow31(uint32_t a, uint64_t e) { uint32_t r = 1; while (e) { if (e & 1) r = mul31(r, a); a = mul31(a, a); e >>= 1; } return r; }
 template <class S, class POW>
 inline S odd_root(unsigned odd, S modulus, POW pw) {   // a primitive odd-th root of unity among the scalars (odd | p - 1)
   for (S g = 2;; ++g) {

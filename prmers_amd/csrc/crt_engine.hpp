@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <memory>
 #include <string>
 
 namespace mi355 {
@@ -63,8 +64,7 @@ class CrtEngine {
 
  private:
   struct Impl;
-  Impl* im_;
-  void release();
+  std::unique_ptr<Impl> im_;
   void check_digits(size_t reg, const char* what) const;
   void ensure_headroom(size_t reg);                       // relax a register whose additions would overflow the next transform
   uint64_t* canon_digits(size_t reg, int slot);           // device-side canonical form (canon.hip), slot 0 / 1

@@ -104,23 +104,22 @@ struct DigitWalk {
   GF_HDM uint32_t weight31() const { return s ? (32 - A31) % 31 : 0; }
   GF_HDM uint32_t unweight61() const { return s ? (A61 + 60) % 61 : 0; }   // 61 - (1 - A) mod 61 = (A - 1) mod 61
   GF_HDM uint32_t unweight31() const { return s ? (A31 + 30) % 31 : 0; }
-  GF_HDM void next(const Geom& g) {
-    uint64_t sn = uint64_t(s) + g.t;
-    A61 += g.lt61; A31 += g.lt31;
+  // to the digit d places on: ds = p d mod n with its images d61 = l61 ds mod 61, d31 = l31 ds mod 31 (the next digit: t, lt61, lt31)
+  GF_HDM void next(const Geom& g, uint32_t ds, uint32_t d61, uint32_t d31) {
+    uint64_t sn = uint64_t(s) + ds;
+    A61 += d61; A31 += d31;
     if (sn >= g.n) { sn -= g.n; A61 += 60; A31 += 30; }   // l n = 1 (mod 61 / 31)
     s = uint32_t(sn);
     A61 = A61 >= 122 ? A61 - 122 : (A61 >= 61 ? A61 - 61 : A61);
     A31 = A31 >= 62 ? A31 - 62 : (A31 >= 31 ? A31 - 31 : A31);
   }
+  GF_HDM void next(const Geom& g) { next(g, g.t, g.lt61, g.lt31); }
 };
 
-// host: the geometry of a transform size (throws on a size or factor the sweep does not take)
-inline uint64_t host_pow61(uint64_t a, uint64_t e) {
-  uint64_t r = 1;
-  while (e) { if (e & 1) r = mul61(r, a); a = mul61(a, a); e >>= 1; }
-  return r;
-}
+inline uint64_t pow61(uint64_t a, uint64_t e) { uint64_t r = 1; while (e) { if (e & 1) r = mul61(r, a); a = mul61(a, a); e >>= 1; } return r; }
+inline uint32_t pow31(uint32_t a, uint64_t e) { uint32_t r = 1; while (e) { if (e & 1) r = mul31(r, a); a = mul31(a, a); e >>= 1; } return r; }
 
+// host: the geometry of a transform size (throws on a size or factor the sweep does not take)
 inline Geom make_geom(uint32_t p, size_t n, uint32_t odd, uint32_t a) {
   if (odd != 1 && odd != 3 && odd != 9) throw std::runtime_error("crt: odd radix must be 1, 3 or 9");
   if (n == 0 || n % odd || n % kRun || n > 0xfffffff0ull) throw std::runtime_error("crt: bad transform size");
@@ -132,19 +131,11 @@ inline Geom make_geom(uint32_t p, size_t n, uint32_t odd, uint32_t a) {
   g.p = p; g.n = uint32_t(n); g.odd = odd; g.ln = ln; g.a = a;
   auto inv_small = [](uint64_t x, uint64_t m) { for (uint64_t y = 1; y < m; ++y) if (x * y % m == 1) return y; return uint64_t(0); };
   g.l61 = uint32_t(inv_small(n % 61, 61)); g.l31 = uint32_t(inv_small(n % 31, 31));
-  g.inv31 = host_pow61(M31, M61 - 2);
+  g.inv31 = pow61(M31, M61 - 2);
   g.q = uint32_t(p / n); g.t = uint32_t(p % n);
   g.lt61 = uint32_t(uint64_t(g.l61) * (g.t % 61) % 61); g.lt31 = uint32_t(uint64_t(g.l31) * (g.t % 31) % 31);
   return g;
 }
-
-#if defined(__HIPCC__)
-// the fused unweight + Garner + carry sweep on device buffers (crt_carry.hip): digits[n], carry[2 * runs], residual[runs]
-void crt_carry_launch(const Geom& g, const uint64_t* in61, const uint32_t* in31, uint64_t* digits, uint64_t* carry, uint64_t* residual,
-                      bool fold_residual, hipStream_t s);
-
-void crt_carry_launch_linked(const Geom& g, const uint64_t* in61, const uint32_t* in31, uint64_t* digits, uint64_t* edge, hipStream_t s);
-#endif
 
 }  // namespace crt
 }  // namespace mi355

@@ -8,8 +8,10 @@
 //                 partner row in LDS, inverse -- one launch and one pass over the data for what were five launches
 // Frequencies are left in the digit-reversed order of the in-place transform inside a kernel and in natural order in HBM.
 // Reference for the algebra: third_party/aevum/src/cl/fft-middle.cl, fftp.cl (the tail square), docs/mersenne2_mixed_crt_2d_half_fast/
-// mersenne2_mixed_crt_2d_half_fast.cpp:829-915.  Included by crt_engine.hip only, after crt_arith.hpp (the arithmetic these kernels call).
+// mersenne2_mixed_crt_2d_half_fast.cpp:829-915.  Device only; included by crt_kernels.hip.
 #pragma once
+#include "crt_arith.hpp"
+#include "crt_kernels.hpp"
 
 namespace mi355 {
 namespace crt {
@@ -17,12 +19,6 @@ namespace crt {
 constexpr uint32_t kFastSlots = 2048;
 constexpr uint32_t kFastPlane = kFastSlots + kFastSlots / 16;   // skewed by a + a / 16
 constexpr uint32_t kFastLdsBytes = kFastPlane * 8 * 3;
-
-struct FastTables {   // per field: omega_L^x for the two pass lengths (x < L), omega_m^(H1 k2) (k2 < H2), omega_m^k (k <= h),
-                      // and the two-level table of the four-step twiddles: omega_m^e = lo[e & 1023] * hi[e >> 10] (e < m)
-  const F61::C *w1_61, *w2_61, *v61, *u61, *lo61, *hi61;
-  const F31::C *w1_31, *w2_31, *v31, *u31, *lo31, *hi31;
-};
 
 struct Planes { uint64_t* re; uint64_t* im; uint2* c3; };
 
@@ -256,7 +252,7 @@ __global__ void __launch_bounds__(SLOTS / 8) k_cols_one(Grid gr, const typename 
 }
 
 // ---- middle: rows k1 and H1 - k1 (work-group 0 of a grid row: rows 0 and H1 / 2, each its own partner) ----
-// The conjugate-symmetric untangle / square / re-tangle (crt_engine.hip: spectrum_sq, repack) per field: Z/M31[i] on the generic forms
+// The conjugate-symmetric untangle / square / re-tangle (crt_kernels.hip: spectrum_lin, repack) per field: Z/M31[i] on the generic forms
 // with the fused product, Z/M61[i] on the lazy forms (sums of up to three canonical values, one fold before a product).
 struct Pw31 {
   using C = F31::C;

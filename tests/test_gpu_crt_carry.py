@@ -1,5 +1,5 @@
 """First HIP kernel of the second field family: the fused unweight + Garner + carry sweep over GF(M61^2) x GF(M31^2)
-(prmers_amd/csrc/crt_carry.hip; reference third_party/aevum/src/cl/carry.cl:506-588) through the C ABI, against the CRT oracle
+(prmers_amd/csrc/crt_kernels.hip, crt_carry.hpp; reference third_party/aevum/src/cl/carry.cl:506-588) through the C ABI, against the CRT oracle
 (oracle/oracle_crt.c).  Needs a real MI355X:  python -m pytest tests -m gpu"""
 import ctypes as C
 

@@ -1,5 +1,5 @@
-"""The resident GF(M61^2) x GF(M31^2) squaring engine with a prime-factor radix-3 / radix-9 axis (prmers_amd/csrc/crt_engine.hip,
-SURVEY.md 8f N1; reference third_party/aevum/src/cl/fft-middle.cl:663-720, pfaunpack.cl:12-56, carry.cl:506-588) through the C ABI,
+"""The resident GF(M61^2) x GF(M31^2) squaring engine with a prime-factor radix-3 / radix-9 axis (prmers_amd/csrc/crt_engine.hip, kernels in
+crt_kernels.hip; reference third_party/aevum/src/cl/fft-middle.cl:663-720, pfaunpack.cl:12-56, carry.cl:506-588) through the C ABI,
 against the CRT oracle (oracle/oracle_crt.c), Python integers and the libgmp pins.  Needs a real MI355X:  python -m pytest tests -m gpu"""
 import json
 import os
