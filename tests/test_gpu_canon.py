@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import canon_cases
 import orc
 
 pytestmark = pytest.mark.gpu
@@ -140,3 +141,16 @@ def test_full_size_check_moves_no_register_over_pcie():
         e.sub(1, 1)
         assert not e.is_equal(0, 1)
         assert np.array_equal(e.digits(0), o.digits(0))
+        # random digits send no carry through the scan (tests/canon_cases.py): one designed vector at this geometry, 2048 blocks in 256
+        # stretches of eight -- chains over several stretches and one that leaves the last stretch, wraps and ends in the third
+        w = o.widths().astype(np.uint64)
+        assert canon_cases.geometry(o.n)[:2] == (2048, 8)
+        c = canon_cases.merged("several_stretches+wrap_from_last_stretch", w, ["several_stretches", "wrap_from_last_stretch"])
+        assert (c.d <= (np.uint64(1) << w)).all()          # a 0/1 chain: the device path, no host fallback
+        e.set_digits(2, c.d); e.set_digits(3, c.t)
+        assert np.array_equal(e.digits(2) & np.uint64(0xffffffff), c.t)
+        assert e.res64(2) == canon_cases.low64(c.t, w)
+        assert e.is_equal(2, 3) and e.is_equal(3, 2)
+        c.t[canon_cases.geometry(o.n)[2]] ^= np.uint64(1)
+        e.set_digits(3, c.t)
+        assert not e.is_equal(2, 3)
