@@ -8,11 +8,14 @@
 // and rotates the file when the test is complete; -ckpt DIR resumes from / saves version-2 checkpoints together with the
 // Gerbicz-Li rollback point (every -backup N iterations, at the end of a partial run, and on SIGINT / SIGTERM, which end the
 // run with exit code 0 like the reference's interrupt path, RunPrpOrLlMarin.cpp:296-309); -proof POWER writes the residues a proof of that power needs under
-// <p>/proof/; -json FILE appends the result line.
+// <p>/proof/ and, after the last iteration of a PRP run, builds the proof file <p>-<POWER>.proof in the working directory on the engine
+// (caller_formats.h build_proof; the reference's name, ProofManagerMarin.cpp:129-132); -json FILE appends the result line.
+// -verify FILE loads a proof file and checks it on the engine: exit code 0 = valid, 1 = invalid.
 //
 //   g++ -std=c++17 -O2 -Iinclude examples/prp_cli.cpp -ldl -lgmp -o mi355_prp
 //   ./mi355_prp <p> | -worktodo FILE  [-d DEVICE] [-ll | -llsafe [-llsafe_block B]] [-erroriter N] [-checklevel L] [-maxiters K] [-ckpt DIR]
 //               [-backup N] [-proof POWER] [-json FILE] [-lib path/to/libmi355_engine.so]
+//   ./mi355_prp -verify FILE [-d DEVICE] [-fft SPEC] [-lib so]
 // -d DEVICE is the reference's device selector (src/io/CliParser.cpp:198): BASELINE configs[4] is eight of these processes, `-d i
 // -worktodo file_i`, one per GPU.  -llsafe is the Lucas-Lehmer test with error detection by block re-computation
 // (src/modes/RunLlSafeMarin.cpp:95-392, run_ll_safe below).
@@ -96,9 +99,9 @@ static int run_ll_safe(engine* eng, uint32_t p, uint64_t block, uint64_t errorit
 }
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::fprintf(stderr, "usage: %s <p> | -worktodo FILE [-d DEVICE] [-ll | -llsafe [-llsafe_block B]] [-erroriter N] [-checklevel L] [-maxiters K] [-ckpt DIR] [-backup N] [-proof POWER] [-json FILE] [-fft SPEC] [-lib so]\n", argv[0]); return 2; }
+  if (argc < 2) { std::fprintf(stderr, "usage: %s <p> | -worktodo FILE [-d DEVICE] [-ll | -llsafe [-llsafe_block B]] [-erroriter N] [-checklevel L] [-maxiters K] [-ckpt DIR] [-backup N] [-proof POWER] [-json FILE] [-fft SPEC] [-lib so]\n       %s -verify FILE [-d DEVICE] [-fft SPEC] [-lib so]\n", argv[0], argv[0]); return 2; }
   uint32_t p = uint32_t(std::strtoul(argv[1], nullptr, 10));
-  bool ll = false, llsafe = false; uint64_t erroriter = 0, checklevel = 0, maxiters = 0, backup = 0, llsafe_block = 0; std::string lib, worktodo, ckpt_dir, json_file, fft; uint32_t proof_power = 0;
+  bool ll = false, llsafe = false; uint64_t erroriter = 0, checklevel = 0, maxiters = 0, backup = 0, llsafe_block = 0; std::string lib, worktodo, ckpt_dir, json_file, fft, verify_file; uint32_t proof_power = 0;
   size_t device = 0;
   fmt::WorkEntry entry;
   for (int i = 1; i < argc; ++i) {
@@ -111,11 +114,22 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "-ckpt") && i + 1 < argc) ckpt_dir = argv[++i];
     else if (!std::strcmp(argv[i], "-backup") && i + 1 < argc) backup = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "-proof") && i + 1 < argc) proof_power = uint32_t(std::strtoul(argv[++i], nullptr, 10));
+    else if (!std::strcmp(argv[i], "-verify") && i + 1 < argc) verify_file = argv[++i];
     else if (!std::strcmp(argv[i], "-json") && i + 1 < argc) json_file = argv[++i];
     else if (!std::strcmp(argv[i], "-erroriter") && i + 1 < argc) erroriter = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "-checklevel") && i + 1 < argc) checklevel = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "-maxiters") && i + 1 < argc) maxiters = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "-lib") && i + 1 < argc) lib = argv[++i];
+  }
+  if (!verify_file.empty()) {
+    fmt::Proof pr;
+    try { pr = fmt::Proof::load(verify_file); } catch (const std::exception& e) { std::fprintf(stderr, "Error: %s\n", e.what()); std::printf("proof INVALID\n"); return 1; }
+    try {
+      engine_hip eng(pr.p, fmt::kProofVerifyRegisters, device, false, lib, fft);
+      const bool ok = fmt::verify_proof(eng, pr);
+      std::printf("proof of M%u, power %u: %s\n", pr.p, pr.power(), ok ? "valid" : "INVALID");
+      return ok ? 0 : 1;
+    } catch (const std::exception& e) { std::fprintf(stderr, "Error: %s\n", e.what()); return 2; }
   }
   if (!worktodo.empty()) {
     entry = fmt::first_worktodo_entry(worktodo);
@@ -126,7 +140,7 @@ int main(int argc, char** argv) {
   std::signal(SIGINT, on_signal);
   std::signal(SIGTERM, on_signal);
   try {
-    std::unique_ptr<engine> eng(new engine_hip(p, 8, device, false, lib, fft));
+    std::unique_ptr<engine_hip> eng(new engine_hip(p, 8, device, false, lib, fft));
     if (llsafe) return run_ll_safe(eng.get(), p, llsafe_block, erroriter, maxiters, json_file);
     const size_t R0 = 0, R1 = 1, R2 = 2, R3 = 3, R4 = 4, R5 = 5, RBASE = 6, RTMP = 7;
     eng->set(R1, 1);
@@ -204,7 +218,7 @@ int main(int argc, char** argv) {
         }
       }
       // proof residues (ProofManagerMarin::checkpointMarin, ProofManagerMarin.cpp:84-120) and periodic backups (:430-447)
-      if (proof && proof->should_checkpoint(uint32_t(iter + 1))) proof->save(uint32_t(iter + 1), residue_words(eng.get(), R0, p));
+      if (proof && proof->should_checkpoint(uint32_t(iter + 1))) proof->save(uint32_t(iter + 1), eng->get_words(R0));   // packed on the device
       if (!ckpt.empty() && backup && done % backup == 0 && iter + 1 < total) checkpoint(uint32_t(iter + 1));
     }
     if (!ckpt.empty() && !complete) checkpoint(uint32_t(last_iter));   // iterations completed = the next iteration index
@@ -225,6 +239,14 @@ int main(int argc, char** argv) {
       if (!worktodo.empty()) {
         const bool more = fmt::rotate_worktodo(worktodo, "worktodo_save.txt");
         std::printf("Entry removed from %s and saved to worktodo_save.txt%s\n", worktodo.c_str(), more ? "; more entries remain" : "; no more entries");
+      }
+      if (proof) {   // ProofManagerMarin::proof (ProofManagerMarin.cpp:124-151), on an engine of its own: power + 1 registers
+        eng.reset();
+        engine_hip pe(p, proof_power + 1, device, false, lib, fft);
+        const fmt::Proof pr = fmt::build_proof(pe, p, proof_power, ".", stdout);
+        const std::string name = fmt::proof_file_name(p, proof_power);
+        if (!pr.save(name)) throw std::runtime_error("cannot write " + name);
+        std::printf("Proof file: %s\n", name.c_str());
       }
     }
     return 0;

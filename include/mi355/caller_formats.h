@@ -4,6 +4,7 @@
 //   * worktodo.txt entries and their rotation      -- src/io/WorktodoParser.cpp:78-400,402-427, RunPrpOrLlMarin.cpp:727-751
 //   * result line (PrimeNet-style JSON)            -- src/io/JsonBuilder.cpp:322-472
 //   * PRP proof checkpoints (residue files)        -- src/core/ProofSetMarin.cpp:56-122,156-158, ProofManagerMarin.cpp:84-120
+//   * PRP proof file, hash chain, build / verify   -- src/core/ProofMarin.cpp:33-217, ProofSetMarin.cpp:213-311
 //   * words / type-1 residue / hex                  -- include/core/AlgoUtils.hpp:165-223
 // Header-only, no dependency on the engine library: everything works on an `engine` (include/mi355/engine_iface.h or the
 // reference's include/marin/engine.h) or on plain vectors, so it is testable without a GPU (tests/host/test_caller_formats.cpp).
@@ -16,6 +17,7 @@
 #include <cstring>
 #include <filesystem>
 #include <fstream>
+#include <iterator>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -314,6 +316,227 @@ class ProofPoints {
   std::string dir_;
   std::vector<uint32_t> points_;
 };
+
+// ---- SHA3-256 (FIPS 202) for the hash chain of a proof.  Written for this header: the round constants come from the standard's LFSR
+//      (x^8 + x^6 + x^5 + x^4 + 1) and the rotation offsets from its (x, y) -> (y, 2x + 3y) walk, both generated at first use; pinned by
+//      digests that hashlib computes (tests/test_proof.py) ---------------------------------------------------------------------------
+class Sha3_256 {
+ public:
+  Sha3_256() { std::memset(a_, 0, sizeof a_); }
+  Sha3_256& update(const void* data, size_t len) {
+    const unsigned char* p = static_cast<const unsigned char*>(data);
+    for (size_t i = 0; i < len; ++i) {
+      a_[fill_ >> 3] ^= uint64_t(p[i]) << (8 * (fill_ & 7));   // lanes are little-endian
+      if (++fill_ == kRate) { permute(a_); fill_ = 0; }
+    }
+    return *this;
+  }
+  std::vector<unsigned char> finish() {   // 32 bytes; the object is spent afterwards
+    a_[fill_ >> 3] ^= uint64_t(0x06) << (8 * (fill_ & 7));                 // domain bits 01 + first pad bit
+    a_[(kRate - 1) >> 3] ^= uint64_t(0x80) << (8 * ((kRate - 1) & 7));      // last pad bit
+    permute(a_);
+    std::vector<unsigned char> out(32);
+    for (size_t i = 0; i < 32; ++i) out[i] = static_cast<unsigned char>(a_[i >> 3] >> (8 * (i & 7)));
+    return out;
+  }
+
+ private:
+  static constexpr size_t kRate = 136;   // 1600 - 2 * 256 bits
+  struct Tables {
+    uint64_t rc[24];
+    unsigned rot[25];
+    Tables() {
+      unsigned lfsr = 1;
+      for (int r = 0; r < 24; ++r) {
+        rc[r] = 0;
+        for (int j = 0; j < 7; ++j) {
+          if (lfsr & 1u) rc[r] ^= uint64_t(1) << ((1u << j) - 1);
+          lfsr = ((lfsr << 1) ^ ((lfsr & 0x80u) ? 0x71u : 0u)) & 0xffu;
+        }
+      }
+      rot[0] = 0;
+      for (unsigned t = 0, x = 1, y = 0; t < 24; ++t) {
+        rot[x + 5 * y] = ((t + 1) * (t + 2) / 2) % 64;
+        const unsigned ny = (2 * x + 3 * y) % 5;
+        x = y; y = ny;
+      }
+    }
+  };
+  static uint64_t rotl(uint64_t v, unsigned s) { return s ? (v << s) | (v >> (64 - s)) : v; }
+  static void permute(uint64_t* A) {
+    static const Tables T;
+    uint64_t B[25], C[5];
+    for (int round = 0; round < 24; ++round) {
+      for (int x = 0; x < 5; ++x) C[x] = A[x] ^ A[x + 5] ^ A[x + 10] ^ A[x + 15] ^ A[x + 20];
+      for (int x = 0; x < 5; ++x) {
+        const uint64_t d = C[(x + 4) % 5] ^ rotl(C[(x + 1) % 5], 1);
+        for (int y = 0; y < 5; ++y) A[x + 5 * y] ^= d;
+      }
+      for (int x = 0; x < 5; ++x)
+        for (int y = 0; y < 5; ++y) B[y + 5 * ((2 * x + 3 * y) % 5)] = rotl(A[x + 5 * y], T.rot[x + 5 * y]);
+      for (int y = 0; y < 5; ++y)
+        for (int x = 0; x < 5; ++x) A[x + 5 * y] = B[x + 5 * y] ^ (~B[(x + 1) % 5 + 5 * y] & B[(x + 2) % 5 + 5 * y]);
+      A[0] ^= T.rc[round];
+    }
+  }
+  uint64_t a_[25];
+  size_t fill_ = 0;
+};
+
+// ---- PRP proof: file (GIMPS version 2, ProofMarin::save / load, src/core/ProofMarin.cpp:33-199), hash chain, build and verify on an
+//      engine -- the C++ twin of prmers_amd/proof.py: same bytes from both ------------------------------------------------------------
+inline size_t proof_residue_size(uint32_t p) { return (size_t(p) - 1) / 8 + 1; }
+inline std::string proof_file_name(uint32_t p, uint32_t power) { return std::to_string(p) + "-" + std::to_string(power) + ".proof"; }   // ProofManagerMarin.cpp:129-132
+// SHA3-256 over [the previous digest,] the (p - 1) / 8 + 1 little-endian bytes of a residue
+inline std::vector<unsigned char> proof_hash(uint32_t p, const std::vector<uint32_t>& words, const std::vector<unsigned char>& prefix = {}) {
+  std::vector<unsigned char> bytes(words.size() * 4);
+  for (size_t i = 0; i < bytes.size(); ++i) bytes[i] = static_cast<unsigned char>(words[i / 4] >> (8 * (i % 4)));
+  Sha3_256 h;
+  if (!prefix.empty()) h.update(prefix.data(), prefix.size());
+  return h.update(bytes.data(), proof_residue_size(p)).finish();
+}
+inline uint64_t proof_hash64(const std::vector<unsigned char>& digest) {   // its first 8 bytes, little-endian
+  uint64_t h = 0;
+  for (int i = 7; i >= 0; --i) h = (h << 8) | digest[size_t(i)];
+  return h;
+}
+
+struct Proof {
+  uint32_t p = 0;
+  std::vector<uint32_t> B;
+  std::vector<std::vector<uint32_t>> middles;
+  uint32_t power() const { return uint32_t(middles.size()); }
+
+  std::string bytes() const {
+    std::string out = "PRP PROOF\nVERSION=2\nHASHSIZE=64\nPOWER=" + std::to_string(power()) + "\nNUMBER=M" + std::to_string(p) + "\n";
+    auto put = [&](const std::vector<uint32_t>& r) { for (size_t i = 0; i < proof_residue_size(p); ++i) out += char((i / 4 < r.size() ? r[i / 4] : 0u) >> (8 * (i % 4))); };
+    put(B);
+    for (const auto& m : middles) put(m);
+    return out;
+  }
+  bool save(const std::string& path) const {
+    std::ofstream f(path, std::ios::binary);
+    const std::string b = bytes();
+    f.write(b.data(), std::streamsize(b.size()));
+    return f.good();
+  }
+  // refuses any other version or hash size, a power outside 1 .. 12, cofactor proofs (a NUMBER with '/') and a file that is too short or too long
+  static Proof load(const std::string& path) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot open proof file " + path);
+    const std::string raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    size_t pos = 0;
+    auto line = [&]() {
+      const size_t e = raw.find('\n', pos);
+      if (e == std::string::npos) throw std::runtime_error(path + ": incomplete proof header");
+      const std::string l = raw.substr(pos, e - pos);
+      pos = e + 1;
+      return l;
+    };
+    auto field = [&](const char* key) {
+      const std::string l = line(), k = std::string(key) + "=";
+      if (l.compare(0, k.size(), k) != 0) throw std::runtime_error(path + ": unexpected header line " + l);
+      return l.substr(k.size());
+    };
+    auto number = [&](const std::string& v, const char* what) -> uint64_t {
+      if (v.empty() || v.size() > 10 || v.find_first_not_of("0123456789") != std::string::npos) throw std::runtime_error(path + ": bad " + what + " " + v);
+      return std::stoull(v);
+    };
+    if (line() != "PRP PROOF") throw std::runtime_error(path + ": not a PRP proof file");
+    const std::string version = field("VERSION"), hashsize = field("HASHSIZE"), power = field("POWER"), num = field("NUMBER");
+    if (version != "2") throw std::runtime_error(path + ": unsupported proof version " + version);
+    if (hashsize != "64") throw std::runtime_error(path + ": unsupported hash size " + hashsize);
+    const uint64_t k = number(power, "power");
+    if (k < 1 || k > 12) throw std::runtime_error(path + ": proof power " + power + " is outside 1 .. 12");
+    if (num.find('/') != std::string::npos) throw std::runtime_error(path + ": proofs of cofactors (" + num + ") are not supported");
+    if (num.empty() || num[0] != 'M') throw std::runtime_error(path + ": NUMBER=" + num + " is not a Mersenne number");
+    const uint64_t e = number(num.substr(1), "exponent");
+    if (e < 2 || e > 0xffffffffull) throw std::runtime_error(path + ": bad exponent " + num);
+    Proof pr;
+    pr.p = uint32_t(e);
+    const size_t size = proof_residue_size(pr.p);
+    if (raw.size() - pos != size * (k + 1)) throw std::runtime_error(path + ": " + std::to_string(raw.size() - pos) + " residue bytes where power " + power + " needs " + std::to_string(size * (k + 1)));
+    auto take = [&]() {
+      std::vector<uint32_t> r((size_t(pr.p) + 31) / 32, 0u);
+      for (size_t i = 0; i < size; ++i) r[i / 4] |= uint32_t(static_cast<unsigned char>(raw[pos + i])) << (8 * (i % 4));
+      pos += size;
+      return r;
+    };
+    pr.B = take();
+    for (uint64_t i = 0; i < k; ++i) pr.middles.push_back(take());
+    return pr;
+  }
+};
+
+// the 64-bit exponents h_0 .. h_(k-1) of a proof
+inline std::vector<uint64_t> proof_hash_chain(const Proof& pr) {
+  std::vector<unsigned char> digest = proof_hash(pr.p, pr.B);
+  std::vector<uint64_t> hs;
+  for (const auto& m : pr.middles) { digest = proof_hash(pr.p, m, digest); hs.push_back(proof_hash64(digest)); }
+  return hs;
+}
+
+// Engine: set_words(reg, words), get_words(reg), exp_mul(a, h, b, tmp), exp_mul2(a, h, b, tmp), square_mul_n(reg, count), is_equal(a, b)
+// (engine_hip has them; tests/host/test_proof_formats.cpp runs the two functions on a GMP stand-in).
+//
+// The proof of M_p from the point files under <base_dir>/<p>/proof/ (ProofSetMarin::computeProof, src/core/ProofSetMarin.cpp:213-311, with
+// every fold "below <- below^h * top" as one exp_mul on the engine instead of a host mpz power).  Level L loads the residues at
+// points[s (2 i + 1) - 1], s = 2^(power - L - 1), onto a stack of registers and folds for every trailing one bit of i; the register left is
+// the level's middle.  Needs power + 1 registers: the stack never exceeds `power`, register `power` is the temporary.  A missing or
+// damaged point file throws with its name (ProofPoints::load).  log: one line per level, as the reference prints them.
+template <class Engine>
+Proof build_proof(Engine& eng, uint32_t p, uint32_t power, const std::string& base_dir = ".", std::FILE* log = nullptr) {
+  if (power < 1 || power > 12) throw std::runtime_error("proof power " + std::to_string(power) + " is outside 1 .. 12");
+  const ProofPoints pts(p, power, base_dir);
+  const size_t tmp = power;
+  Proof pr;
+  pr.p = p;
+  pr.B = pts.load(p);
+  std::vector<unsigned char> digest = proof_hash(p, pr.B);
+  std::vector<uint64_t> hashes;
+  for (uint32_t level = 0; level < power; ++level) {
+    const size_t s = size_t(1) << (power - level - 1);
+    size_t top = 0;
+    for (size_t i = 0; i < (size_t(1) << level); ++i) {
+      eng.set_words(top++, pts.load(pts.points()[s * (2 * i + 1) - 1]));
+      for (uint32_t k = 0; (i >> k) & 1; ++k) { --top; eng.exp_mul(top - 1, hashes[level - 1 - k], top, tmp); }
+    }
+    if (top != 1) throw std::runtime_error("internal: proof stack not folded");
+    pr.middles.push_back(eng.get_words(0));
+    digest = proof_hash(p, pr.middles.back(), digest);
+    hashes.push_back(proof_hash64(digest));
+    if (log) {
+      const std::vector<uint32_t>& m = pr.middles.back();
+      const uint64_t m64 = (uint64_t(m.size() > 1 ? m[1] : 0u) << 32) | m[0];
+      std::fprintf(log, "proof [%u] : M %016llx, h %016llx\n", level, static_cast<unsigned long long>(m64), static_cast<unsigned long long>(hashes.back()));
+    }
+  }
+  return pr;
+}
+
+// true when the proof shows B = 3^(2^p): A = 3, B = proof.B, span = p; per middle M with its h: B <- M^h * (B^2 if span is odd, else B),
+// A <- A^h * M, span <- (span + 1) / 2; then A^(2^span) == B on the engine.  Needs 5 registers.
+constexpr size_t kProofVerifyRegisters = 5;
+template <class Engine>
+bool verify_proof(Engine& eng, const Proof& pr) {
+  size_t RA = 0, RB = 1, RM = 2, RM2 = 3, RT = 4;
+  std::vector<uint32_t> three((size_t(pr.p) + 31) / 32, 0u);
+  three[0] = 3;
+  eng.set_words(RA, three);
+  eng.set_words(RB, pr.B);
+  const std::vector<uint64_t> hs = proof_hash_chain(pr);
+  uint64_t span = pr.p;
+  for (size_t i = 0; i < pr.middles.size(); ++i) {
+    eng.set_words(RM, pr.middles[i]);
+    eng.set_words(RM2, pr.middles[i]);
+    if (span & 1) eng.exp_mul2(RM, hs[i], RB, RT); else eng.exp_mul(RM, hs[i], RB, RT);   // the new B, in RM
+    eng.exp_mul(RA, hs[i], RM2, RT);
+    std::swap(RB, RM);
+    span = (span + 1) / 2;
+  }
+  eng.square_mul_n(RA, size_t(span));
+  return eng.is_equal(RA, RB);
+}
 
 }  // namespace formats
 }  // namespace mi355

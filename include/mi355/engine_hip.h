@@ -57,6 +57,11 @@ class engine_hip final : public engine {
     int (*square_mul_copy)(void*, size_t, size_t, uint32_t) = nullptr;
     int (*mul_copy)(void*, size_t, size_t, size_t, uint32_t) = nullptr;
     int (*square_mul_n)(void*, size_t, uint32_t, size_t, uint32_t) = nullptr;   // optional (libraries before round 3 lack it)
+    // optional as well (a library or test shim without them is served by the compositions below)
+    int (*set_words)(void*, size_t, const uint32_t*, size_t) = nullptr;
+    int (*get_words)(void*, size_t, uint32_t*, size_t) = nullptr;
+    int (*exp_mul)(void*, size_t, uint64_t, size_t, size_t) = nullptr;
+    int (*exp_mul2)(void*, size_t, uint64_t, size_t, size_t) = nullptr;
 
     template <class F> void bind(F& f, const char* name) {
       f = reinterpret_cast<F>(dlsym(so, name));
@@ -89,6 +94,10 @@ class engine_hip final : public engine {
       bind(addsub, "mi355_engine_addsub"); bind(addsub_copy, "mi355_engine_addsub_copy"); bind(mul_add, "mi355_engine_mul_add");
       bind(square_mul_copy, "mi355_engine_square_mul_copy"); bind(mul_copy, "mi355_engine_mul_copy");
       square_mul_n = reinterpret_cast<decltype(square_mul_n)>(dlsym(so, "mi355_engine_square_mul_n"));
+      set_words = reinterpret_cast<decltype(set_words)>(dlsym(so, "mi355_engine_set_words"));
+      get_words = reinterpret_cast<decltype(get_words)>(dlsym(so, "mi355_engine_get_words"));
+      exp_mul = reinterpret_cast<decltype(exp_mul)>(dlsym(so, "mi355_engine_exp_mul"));
+      exp_mul2 = reinterpret_cast<decltype(exp_mul2)>(dlsym(so, "mi355_engine_exp_mul2"));
     }
     ~Api() { if (so) dlclose(so); }
   };
@@ -99,6 +108,18 @@ class engine_hip final : public engine {
 
   void ok(int rc, const char* op) const {
     if (!rc) throw std::runtime_error(std::string("MI355 ") + op + " failed: " + _api.last_error());
+  }
+  void exp_mul_any(const Reg a, const uint64_t h, const Reg b, const Reg tmp, const bool square_b) const {
+    if (auto f = square_b ? _api.exp_mul2 : _api.exp_mul) { ok(f(_h, a, h, b, tmp), square_b ? "exp_mul2" : "exp_mul"); return; }
+    if (a == b || a == tmp || b == tmp) throw std::runtime_error("MI355 exp_mul failed: a, b and tmp must be three different registers");
+    if (square_b) square_mul(b);
+    if (h == 0) copy(a, b);
+    set_multiplicand(tmp, a);
+    int top = 63;
+    while (top > 0 && !((h >> top) & 1)) --top;
+    for (int i = top - 1; i >= 0 && h != 0; --i) { square_mul(a); if ((h >> i) & 1) mul(a, tmp); }
+    set_multiplicand(b, b);
+    if (h != 0) mul(a, b);
   }
 
  protected:
@@ -135,6 +156,49 @@ class engine_hip final : public engine {
   void square_mul_n(const Reg src, const size_t count, const uint32_t a = 1, const uint32_t sub_after = 0) const {
     if (_api.square_mul_n) { ok(_api.square_mul_n(_h, src, a, count, sub_after), "square_mul_n"); return; }
     for (size_t i = 0; i < count; ++i) { square_mul(src, a); if (sub_after) sub(src, sub_after); }
+  }
+  // a = a^h * b (exp_mul) / a^h * b^2 (exp_mul2): the fold of a PRP proof (PRPLL's expMul / expMul2) as one library call; b and tmp are
+  // consumed.  Not part of the reference's engine; the composition of its operations when the library does not export them.
+  void exp_mul(const Reg a, const uint64_t h, const Reg b, const Reg tmp) const { exp_mul_any(a, h, b, tmp, false); }
+  void exp_mul2(const Reg a, const uint64_t h, const Reg b, const Reg tmp) const { exp_mul_any(a, h, b, tmp, true); }
+  // the canonical residue as ceil(p / 32) little-endian words (2^p - 1 reads as 0) / a register from such words: packed and cut on the
+  // device by the library, through the digit vector when it does not export the word entry points
+  std::vector<uint32_t> get_words(const Reg src) const {
+    if (_api.get_words && _api.word_count) {
+      std::vector<uint32_t> w(_api.word_count(_h));
+      ok(_api.get_words(_h, src, w.data(), w.size()), "get_words");
+      return w;
+    }
+    std::vector<uint64_t> d(_n);
+    get(d.data(), src);
+    size_t bits = 0;
+    bool ones = true;
+    for (uint64_t v : d) { bits += size_t(v >> 32); ones = ones && uint32_t(v) == (uint64_t(1) << (v >> 32)) - 1; }
+    std::vector<uint32_t> w((bits + 31) / 32, 0u);
+    if (ones) return w;
+    size_t bit = 0;
+    for (uint64_t v : d) {
+      const uint64_t x = uint64_t(uint32_t(v)) << (bit % 32);
+      w[bit / 32] |= uint32_t(x);
+      if (bit / 32 + 1 < w.size()) w[bit / 32 + 1] |= uint32_t(x >> 32);
+      bit += size_t(v >> 32);
+    }
+    return w;
+  }
+  void set_words(const Reg dst, const std::vector<uint32_t>& w) const {
+    if (_api.set_words) { ok(_api.set_words(_h, dst, w.data(), w.size()), "set_words"); return; }
+    std::vector<uint64_t> d(_n);
+    get(d.data(), dst);   // the widths
+    size_t bit = 0;
+    for (uint64_t& v : d) {
+      const unsigned width = unsigned(v >> 32);
+      const size_t i = bit / 32;
+      uint64_t u = (i < w.size() ? w[i] : 0u) >> (bit % 32);
+      if (bit % 32) u |= uint64_t(i + 1 < w.size() ? w[i + 1] : 0u) << (32 - bit % 32);
+      v = (u & ((uint64_t(1) << width) - 1)) | (uint64_t(width) << 32);
+      bit += width;
+    }
+    set(dst, d.data());
   }
   // fused variants: one sweep each in the library instead of the base-class compositions (engine.h:65-131)
   void mul_add(const Reg dst, const Reg mul_src, const Reg add_src, const uint32_t a = 1) const override { ok(_api.mul_add(_h, dst, mul_src, add_src, a), "mul_add"); }

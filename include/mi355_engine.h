@@ -82,6 +82,12 @@ MI355_ENGINE_API int mi355_engine_mul_copy(mi355_engine_handle handle, size_t ds
    subtraction borrows through the digits).  (A one-cooperative-launch form for transforms of at most 2^20 words was built and measured
    slower than three launches per squaring; it is not in this library: DESIGN.md 5.2c.) */
 MI355_ENGINE_API int mi355_engine_square_mul_n(mi355_engine_handle handle, size_t reg, uint32_t factor, size_t count, uint32_t sub);
+/* a = a^h * b (PRPLL's expMul: the fold of a PRP proof, built and verified on the engine); b and tmp are consumed (left as multiplicand
+   images).  h = 0: a = b.  Same result as prepare(tmp, a); left-to-right binary square_mul / mul over the bits of h; prepare(b, b);
+   mul(a, b), issued by the library in one call.  a, b, tmp distinct; a and b hold residues. */
+MI355_ENGINE_API int mi355_engine_exp_mul(mi355_engine_handle handle, size_t a, uint64_t h, size_t b, size_t tmp);
+/* the same with b squared first: a = a^h * b^2 (PRPLL's expMul2; verification needs it when a span is odd) */
+MI355_ENGINE_API int mi355_engine_exp_mul2(mi355_engine_handle handle, size_t a, uint64_t h, size_t b, size_t tmp);
 
 /* ---- rest of the engine surface the Marin callers use ---- */
 /* engine::get / engine::set(Reg, uint64*) (engine.h:24-25): n digits, value | width << 32, strongly
@@ -132,7 +138,7 @@ MI355_ENGINE_API int mi355_crt_carry(uint32_t exponent, size_t transform_words, 
    transform sizes README.md:907-926, e.g. "crt:9" = the radix-9 family, "crt:3:words=6291456").  words = 0 / absent: the smallest
    admissible odd * 2^k.  Served by that engine: the 19 core entry points (create ... equal), get_digits / set_digits (sizes with words of
    at most 32 bits), res64, raw images and checkpoints (12 bytes per word + a kind tag per register), time_square_mul (sub must be 0), kernel_count /
-   kernel_name, algorithmic_bytes, describe, the fused register operations (as compositions). */
+   kernel_name, algorithmic_bytes, describe, the fused register operations and exp_mul / exp_mul2 (as compositions). */
 MI355_ENGINE_API size_t mi355_crt_transform_size(uint32_t exponent, uint32_t odd_radix);
 /* the engine's own digits of a crt handle: plain u64 values in base 2^width_j, logical order (canonical != 0: after the strong carry;
    0: as they are on the device, weakly carried) -- test and debugging access; mi355_engine_get_digits / set_digits on such a handle

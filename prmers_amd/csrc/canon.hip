@@ -210,6 +210,48 @@ __global__ void __launch_bounds__(256) k_add_complement(CanonGeom g, T* __restri
   dst[pos_of(g, j)] += ((T(1) << w) - T(1)) - canon[j];
 }
 
+// ---- residue words <-> canonical digits (get_words / set_words without a full-register trip over PCIe and a host loop) ----
+// Digit k of the canonical form covers the bits [ceil(p k / n), ceil(p (k + 1) / n)) of the residue, so both directions are closed forms.
+//
+// k_pack_words: one thread per output 32-bit word i.  The first digit that reaches bit 32 i is k = floor(32 i n / p) (the largest k with
+// ceil(p k / n) <= 32 i: one 64-bit division per WORD, the digit offsets after it are shifts); digit pieces are ORed in until bit 32 i + 32.
+// No atomics: every word is written once, by its thread.  Canonical digits are below 2^width, so the pieces do not overlap, and nothing lies
+// at or above bit p, so the tail of the last word is zero.  With widths near 17 a word takes pieces of three digits; a digit of 39 bits
+// spans up to three words.  The value 2^p - 1 needs no case here: it is decided on the DEVICE, by k_apply, which writes the canonical
+// digits as zeros when flag word [0] is set -- the words come out all zero.
+template <class T>
+__global__ void __launch_bounds__(256) k_pack_words(CanonGeom g, const T* __restrict__ nat, uint32_t* __restrict__ words, uint32_t wc) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= wc) return;
+  const uint64_t b0 = uint64_t(i) * 32, b1 = b0 + 32;
+  uint64_t k = (b0 * g.n) / g.p;          // 32 i < p: k < n
+  uint64_t o = ceil_pj_n(g, k);
+  uint32_t acc = 0;
+  while (o < b1 && k < g.n) {
+    const uint64_t v = nat[k];
+    acc |= (o >= b0) ? uint32_t(v << (o - b0)) : uint32_t(v >> (b0 - o));   // shifts below 32 resp. below the digit's width
+    o = ceil_pj_n(g, ++k);
+  }
+  words[i] = acc;
+}
+
+// k_unpack_words: one thread per digit j.  It reads the two words it overlaps (a third when a wide digit starts high in its first word),
+// masks to the width and stores the digit at its memory position: natural order (M1 = 0, the u64 family) or tile-major (pos_of -- the
+// store k_scatter does, without the natural-order array in between).  The words hold a value below 2^p; words at and above wc read as zero.
+template <class T>
+__global__ void __launch_bounds__(256) k_unpack_words(CanonGeom g, const uint32_t* __restrict__ words, uint32_t wc, T* __restrict__ digits) {
+  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= g.n) return;
+  const uint64_t o = ceil_pj_n(g, j);
+  const uint32_t w = uint32_t(ceil_pj_n(g, uint64_t(j) + 1) - o);
+  const uint64_t i = o >> 5;
+  const uint32_t s = uint32_t(o & 31);
+  const uint64_t w0 = i < wc ? words[i] : 0u, w1 = i + 1 < wc ? words[i + 1] : 0u;
+  uint64_t v = (w0 | (w1 << 32)) >> s;
+  if (s + w > 64 && i + 2 < wc) v |= uint64_t(words[i + 2]) << (64 - s);
+  digits[pos_of(g, j)] = T(v & ((uint64_t(1) << w) - 1));
+}
+
 // the whole pipeline on an array in natural order or tile-major order (g.M1)
 template <class T>
 void launch_pipeline(const CanonGeom& g, const T* digits, T* out, T* A, T* B, uint32_t* agg, uint32_t* cin, uint32_t* flags, hipStream_t s) {
@@ -266,6 +308,19 @@ hipError_t canon_set_small(const DevPlan& pl, uint32_t p, uint32_t* digits, uint
   hipLaunchKernelGGL(k_set_small, dim3(1), dim3(64), 0, s, geom_of(pl, p), digits, value);
   return hipGetLastError();
 }
+// canon: n canonical digits in natural order (canon_launch) -> words: ceil(p / 32) little-endian words of the residue
+hipError_t canon_pack_words(const DevPlan& pl, uint32_t p, const uint32_t* canon, uint32_t* words, hipStream_t s) {
+  CanonGeom g = geom_of(pl, p); g.M1 = 0;
+  const uint32_t wc = uint32_t((uint64_t(p) + 31) / 32);
+  hipLaunchKernelGGL(k_pack_words<uint32_t>, dim3((wc + 255) / 256), dim3(256), 0, s, g, canon, words, wc);
+  return hipGetLastError();
+}
+// words: ceil(p / 32) words of a value below 2^p -> the digits of a register (tile-major)
+hipError_t canon_unpack_words(const DevPlan& pl, uint32_t p, const uint32_t* words, uint32_t* digits, hipStream_t s) {
+  const uint32_t wc = uint32_t((uint64_t(p) + 31) / 32);
+  hipLaunchKernelGGL(k_unpack_words<uint32_t>, dim3((pl.n + 255) / 256), dim3(256), 0, s, geom_of(pl, p), words, wc, digits);
+  return hipGetLastError();
+}
 hipError_t canon_compare(const uint32_t* a, const uint32_t* b, uint32_t n, uint32_t* diff_flag, hipStream_t s) {
   hipLaunchKernelGGL(k_compare<uint32_t>, dim3((n + 255) / 256), dim3(256), 0, s, a, b, n, diff_flag);
   return hipGetLastError();
@@ -294,6 +349,16 @@ hipError_t canon64_launch(uint32_t p, uint32_t n, uint32_t odd, const uint64_t* 
   uint64_t* A = static_cast<uint64_t*>(scratch);
   uint32_t* agg = reinterpret_cast<uint32_t*>(A + 2 * size_t(n));
   launch_pipeline<uint64_t>(g, digits, out, A, A + n, agg, agg + nb, agg + 2 * nb, s);
+  return hipGetLastError();
+}
+hipError_t canon64_pack_words(uint32_t p, uint32_t n, uint32_t odd, const uint64_t* canon, uint32_t* words, hipStream_t s) {
+  const uint32_t wc = uint32_t((uint64_t(p) + 31) / 32);
+  hipLaunchKernelGGL(k_pack_words<uint64_t>, dim3((wc + 255) / 256), dim3(256), 0, s, geom64(p, n, odd), canon, words, wc);
+  return hipGetLastError();
+}
+hipError_t canon64_unpack_words(uint32_t p, uint32_t n, uint32_t odd, const uint32_t* words, uint64_t* digits, hipStream_t s) {
+  const uint32_t wc = uint32_t((uint64_t(p) + 31) / 32);
+  hipLaunchKernelGGL(k_unpack_words<uint64_t>, dim3((n + 255) / 256), dim3(256), 0, s, geom64(p, n, odd), words, wc, digits);
   return hipGetLastError();
 }
 hipError_t canon64_compare(const uint64_t* a, const uint64_t* b, uint32_t n, uint32_t* diff_flag, hipStream_t s) {

@@ -95,6 +95,8 @@ hipError_t canon64_launch(uint32_t p, uint32_t n, uint32_t odd, const uint64_t* 
 hipError_t canon64_compare(const uint64_t* a, const uint64_t* b, uint32_t n, uint32_t* diff_flag, hipStream_t s);
 hipError_t canon64_relax(uint32_t p, uint32_t n, uint32_t odd, const uint64_t* in, uint64_t* out, hipStream_t s);
 hipError_t canon64_add_complement(uint32_t p, uint32_t n, uint32_t odd, uint64_t* dst, const uint64_t* canon, hipStream_t s);
+hipError_t canon64_pack_words(uint32_t p, uint32_t n, uint32_t odd, const uint64_t* canon, uint32_t* words, hipStream_t s);
+hipError_t canon64_unpack_words(uint32_t p, uint32_t n, uint32_t odd, const uint32_t* words, uint64_t* digits, hipStream_t s);
 
 struct CrtEngine::Impl {
   crt::Geom g;
@@ -471,6 +473,24 @@ void CrtEngine::addsub(long sum_out, long sum_copy, long diff_out, long diff_cop
 void CrtEngine::mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t f) { mul(dst, mul_src, f); add(dst, add_src); }
 void CrtEngine::square_mul_copy(size_t src, size_t dst_copy, uint32_t f) { square_mul(src, f); copy(dst_copy, src); }
 void CrtEngine::mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t f) { mul(dst, src, f); copy(dst_copy, dst); }
+// a = a^h * b: set_multiplicand(tmp, a), left-to-right binary square_mul / mul over the bits of h below its top bit, set_multiplicand(b, b),
+// mul(a, b).  Checked before the first launch: a refused call leaves the registers as they were.
+void CrtEngine::exp_mul(size_t a, uint64_t h, size_t b, size_t tmp, bool square_b) {
+  check_digits(a, "exp_mul"); check_digits(b, "exp_mul");
+  if (tmp >= im_->regs.size()) throw std::runtime_error("exp_mul: register index out of range");
+  if (a == b || a == tmp || b == tmp) throw std::runtime_error("exp_mul: a, b and tmp must be three different registers");
+  if (square_b) square_mul(b, 1);
+  if (h == 0) copy(a, b);
+  set_multiplicand(tmp, a);
+  int top = 63;
+  while (top > 0 && !((h >> top) & 1)) --top;
+  for (int i = top - 1; i >= 0 && h != 0; --i) {
+    square_mul(a, 1);
+    if ((h >> i) & 1) mul(a, tmp, 1);
+  }
+  set_multiplicand(b, b);
+  if (h != 0) mul(a, b, 1);
+}
 
 void CrtEngine::set_u32(size_t reg, uint32_t a) {
   Impl& im = *im_;
@@ -559,13 +579,28 @@ void CrtEngine::set_digits_encoded(size_t reg, const uint64_t* d, size_t count) 
   set_digits(reg, v.data(), count);
 }
 
-// canonical little-endian 32-bit words of the residue, 2^p - 1 -> 0 (what the plugin ABI exchanges: EngineApi.cpp:210-218)
+// canonical little-endian 32-bit words of the residue, 2^p - 1 -> 0 (what the plugin ABI exchanges: EngineApi.cpp:210-218).  Packed on the
+// device from the canonical digits (canon.hip k_pack_words, which sees 2^p - 1 as zeros): ceil(p / 32) words cross PCIe, not n u64 digits.
 void CrtEngine::get_words(size_t reg, uint32_t* w, size_t count) {
   Impl& im = *im_;
-  const size_t n = im.g.n, need = (size_t(im.g.p) + 31) / 32;
+  const size_t need = (size_t(im.g.p) + 31) / 32;
   if (count < need) throw std::runtime_error("get_words: buffer too small");
+  check_digits(reg, "get_words");
+  if (!im.host_carry) {
+    const uint64_t* c = canon_digits(reg, 0);
+    uint32_t* dw = static_cast<uint32_t*>(im.canon);   // the pipeline's first work array (8 n bytes >= the words) is free once the digits are out
+    chk(canon64_pack_words(im.g.p, im.g.n, im.gr.odd, c, dw, im.stream), "pack");
+    chk(hipMemcpyAsync(w, dw, need * 4, hipMemcpyDeviceToHost, im.stream), "copy");
+    uint32_t flags[4];
+    if (canon_flags_ok(flags)) { std::memset(w + need, 0, (count - need) * 4); return; }
+  }
+  get_words_host(reg, w, count);
+}
+void CrtEngine::get_words_host(size_t reg, uint32_t* w, size_t count) {
+  Impl& im = *im_;
+  const size_t n = im.g.n;
   std::vector<uint64_t> d(n);
-  get_digits(reg, d.data(), n, true);
+  get_digits_host(reg, d.data(), n);
   bool ones = true;
   for (size_t j = 0; j < n && ones; ++j) ones = d[j] == ((uint64_t(1) << im.width[j]) - 1);
   std::memset(w, 0, count * 4);
@@ -580,12 +615,25 @@ void CrtEngine::get_words(size_t reg, uint32_t* w, size_t count) {
     bit += im.width[j];
   }
 }
-// reg <- the value of `count` little-endian 32-bit words (< 2^p; bits beyond p must be zero): cut into digits on the host
+// reg <- the value of `count` little-endian 32-bit words (< 2^p; bits beyond p must be zero): the words go up and are cut into digits on the
+// device (canon.hip k_unpack_words); MI355_HOST_CARRY=1 cuts them on the host
 void CrtEngine::set_words(size_t reg, const uint32_t* w, size_t count) {
   Impl& im = *im_;
   const size_t n = im.g.n, need = (size_t(im.g.p) + 31) / 32;
   if (count > need) for (size_t k = need; k < count; ++k) if (w[k]) throw std::runtime_error("set_words: value does not fit 2^p");
   if (count >= need && (im.g.p & 31) && (w[need - 1] >> (im.g.p & 31))) throw std::runtime_error("set_words: value does not fit 2^p");
+  if (!im.host_carry) {
+    if (reg >= im.regs.size()) throw std::runtime_error("set_words: register index out of range");
+    chk(hipSetDevice(im.device), "hipSetDevice");
+    uint32_t* dw = reinterpret_cast<uint32_t*>(im.scratch);   // 8 n bytes: room for the words of every admissible size
+    if (count < need) chk(hipMemsetAsync(dw, 0, need * 4, im.stream), "memset");
+    chk(hipMemcpyAsync(dw, w, std::min(count, need) * 4, hipMemcpyHostToDevice, im.stream), "copy");
+    chk(canon64_unpack_words(im.g.p, im.g.n, im.gr.odd, dw, im.regs[reg].x, im.stream), "unpack");
+    chk(hipStreamSynchronize(im.stream), "sync");
+    im.regs[reg].image = false;
+    im.excess[reg] = 0;
+    return;
+  }
   std::vector<uint64_t> d(n, 0);
   size_t bit = 0;
   auto word = [&](size_t k) -> uint64_t { return k < count ? w[k] : 0; };

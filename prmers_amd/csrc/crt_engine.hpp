@@ -45,6 +45,8 @@ class CrtEngine {
   void mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t f);
   void square_mul_copy(size_t src, size_t dst_copy, uint32_t f);
   void mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t f);
+  // a = a^h * b (b squared first when square_b), PRPLL's expMul / expMul2, composed of the operations above; b and tmp end as images
+  void exp_mul(size_t a, uint64_t h, size_t b, size_t tmp, bool square_b);
   bool equal(size_t a, size_t b);
   void set_digits(size_t reg, const uint64_t* d, size_t count);
   void get_digits(size_t reg, uint64_t* d, size_t count, bool canonical);
@@ -71,6 +73,7 @@ class CrtEngine {
   bool canon_flags_ok(uint32_t (&flags)[4]);
   const uint64_t* canonical_on_device(size_t src);        // canonical digits of src in device memory (slot 1)
   void get_digits_host(size_t reg, uint64_t* d, size_t count);   // read-back + host carry (fallback, MI355_HOST_CARRY=1)
+  void get_words_host(size_t reg, uint32_t* w, size_t count);    // words packed by the host loop (the same fallback)
   void launch_transform(size_t reg, int mode, size_t other, uint32_t a, bool timed);
 };
 

@@ -376,10 +376,24 @@ uint64_t Engine::res64(size_t src) {
   return r64;
 }
 
+// The words are packed on the device from the canonical digits (canon.hip k_pack_words; 2^p - 1 comes out as 0 there): word_count() words
+// cross PCIe instead of the n digits.  MI355_HOST_CARRY=1, or a canonical form that falls back, take the host loop (get_words_host).
 void Engine::get_words(size_t src, uint32_t* w, size_t count) {
   if (count != word_count()) throw std::runtime_error("get_words: count must equal word_count()");
+  if (!host_carry_) {
+    uint32_t* d = canon_digits(src, 0);
+    uint32_t* dw = canon_;   // the pipeline's first work array (n words >= word_count(): widths are below 32) is free once the digits are out
+    HIPCHK(canon_pack_words(dp_, pl_.p, d, dw, stream_));
+    HIPCHK(hipMemcpyAsync(w, dw, count * 4, hipMemcpyDeviceToHost, stream_));
+    uint32_t flags[4];
+    if (canon_flags_ok(flags)) return;
+  }
+  get_words_host(src, w, count);
+}
+
+void Engine::get_words_host(size_t src, uint32_t* w, size_t count) {
   std::vector<uint64_t> v;
-  read_values(src, v);
+  read_values_host(src, v);
   bool all_ones = true;   // 2^p - 1 == 0 (engine.h:188-196)
   for (size_t k = 0; k < pl_.n && all_ones; ++k) all_ones = (v[k] == (uint64_t(1) << width_[k]) - 1);
   std::memset(w, 0, count * 4);
@@ -397,20 +411,36 @@ void Engine::get_words(size_t src, uint32_t* w, size_t count) {
 void Engine::set_words(size_t dst, const uint32_t* w, size_t count) {
   check_reg(dst);
   if (count != word_count()) throw std::runtime_error("set_words: count must equal word_count()");
-  // bits at and above p are folded back (2^p = 1), so any count-word value is accepted
-  std::vector<uint32_t> src(w, w + count);
-  src.push_back(0);
+  // bits at and above p are folded back (2^p = 1), so any count-word value is accepted; the fold runs on the host, before the upload,
+  // and only for a value that has such bits
   const unsigned top = pl_.p % 32;
-  uint64_t fold = 0;
-  if (top) { fold = src[count - 1] >> top; src[count - 1] &= (1u << top) - 1; }
-  for (size_t i = 0; fold && i < count; ++i) {  // add the folded bits at bit 0
-    const uint64_t t = uint64_t(src[i]) + (fold & 0xffffffffu);
-    src[i] = uint32_t(t);
-    fold = (fold >> 32) + (t >> 32);
+  std::vector<uint32_t> src;
+  if (host_carry_ || (top && (w[count - 1] >> top))) {
+    src.assign(w, w + count);
+    src.push_back(0);
+    uint64_t fold = 0;
+    if (top) { fold = src[count - 1] >> top; src[count - 1] &= (1u << top) - 1; }
+    for (size_t i = 0; fold && i < count; ++i) {  // add the folded bits at bit 0
+      const uint64_t t = uint64_t(src[i]) + (fold & 0xffffffffu);
+      src[i] = uint32_t(t);
+      fold = (fold >> 32) + (t >> 32);
+    }
+    if (top && (src[count - 1] >> top)) {  // the addition rippled past bit p once more
+      src[count - 1] &= (1u << top) - 1;
+      for (size_t i = 0; i < count; ++i) { if (++src[i] != 0) break; }
+    }
+    w = src.data();
   }
-  if (top && (src[count - 1] >> top)) {  // the addition rippled past bit p once more
-    src[count - 1] &= (1u << top) - 1;
-    for (size_t i = 0; i < count; ++i) { if (++src[i] != 0) break; }
+  if (!host_carry_) {
+    // the words go up as they are and are cut into digits on the device (canon.hip k_unpack_words), straight into tile-major order
+    HIPCHK(hipSetDevice(device_));
+    uint32_t* dw = reinterpret_cast<uint32_t*>(work());
+    HIPCHK(hipMemcpyAsync(dw, w, count * 4, hipMemcpyHostToDevice, stream_));
+    HIPCHK(canon_unpack_words(dp_, pl_.p, dw, digits(dst), stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    kind_[dst] = kDigits;
+    pending_carry_[dst] = 0;
+    return;
   }
   std::vector<uint32_t> nat(pl_.n);
   size_t bit = 0;
@@ -633,6 +663,24 @@ void Engine::mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t a) {
   run_front(dst);   // reads digits(dst) (+ pending carries) and leaves them in place
   run_middle(work(), image(mul_src), work(), 1);
   back_ext(dst, a, -1, long(add_src));
+}
+
+// a = a^h * b: prepare(tmp, a), left-to-right binary square_mul / mul over the bits of h below its top bit, prepare(b, b), mul(a, b).
+// Everything is checked before the first launch, so a refused call leaves the registers as they were.
+void Engine::exp_mul(size_t a, uint64_t h, size_t b, size_t tmp, bool square_b) {
+  need_digits(a, "exp_mul"); need_digits(b, "exp_mul"); check_reg(tmp);
+  if (a == b || a == tmp || b == tmp) throw std::runtime_error("exp_mul: a, b and tmp must be three different registers");
+  if (square_b) square_mul(b, 1);
+  if (h == 0) copy(a, b);
+  prepare(tmp, a);
+  int top = 63;
+  while (top > 0 && !((h >> top) & 1)) --top;
+  for (int i = top - 1; i >= 0 && h != 0; --i) {
+    square_mul(a, 1);
+    if ((h >> i) & 1) mul(a, tmp, 1);
+  }
+  prepare(b, b);
+  if (h != 0) mul(a, b, 1);
 }
 
 void Engine::sub_u32(size_t r, uint32_t v) {

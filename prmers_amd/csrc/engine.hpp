@@ -52,6 +52,8 @@ class Engine {
   void mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t a);
   void square_mul_copy(size_t src, size_t dst_copy, uint32_t a);
   void mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t a);
+  // a = a^h * b (b squared first when square_b): the fold of a PRP proof (PRPLL's expMul / expMul2).  b and tmp end as multiplicand images.
+  void exp_mul(size_t a, uint64_t h, size_t b, size_t tmp, bool square_b);
 
   size_t register_data_size() const { return reg_bytes_ + 8; }
   void get_data(size_t src, void* data, size_t size);
@@ -82,6 +84,7 @@ class Engine {
   void swap_with_work(size_t r) { std::swap(slot_[r], slot_[nregs_]); }
   void read_values(size_t src, std::vector<uint64_t>& v);   // natural order, strongly carried digits
   void read_values_host(size_t src, std::vector<uint64_t>& v);   // the same through D2H + host carry (reference's way)
+  void get_words_host(size_t src, uint32_t* w, size_t count);    // words packed by the host loop (fallback, MI355_HOST_CARRY=1)
   uint32_t* canon_digits(size_t r, int slot);   // device: canonical digits of r in natural order (canon.hip), slot 0 / 1
   bool canon_flags_ok(uint32_t (&flags)[4]);    // reads the flag words; false: fall back to the host carry
   void write_values(size_t dst, const std::vector<uint32_t>& natural);

@@ -76,6 +76,8 @@ def load_library():
         "mi355_engine_square_mul_copy": (C.c_int, [vp, sz, sz, u32]),
         "mi355_engine_square_mul_n": (C.c_int, [vp, sz, u32, sz, u32]),
         "mi355_engine_mul_copy": (C.c_int, [vp, sz, sz, sz, u32]),
+        "mi355_engine_exp_mul": (C.c_int, [vp, sz, C.c_uint64, sz, sz]),
+        "mi355_engine_exp_mul2": (C.c_int, [vp, sz, C.c_uint64, sz, sz]),
         "mi355_crt_carry": (C.c_int, [u32, sz, u32, u32, vp, vp, vp, vp, sz, dp]),
         "mi355_crt_transform_size": (sz, [u32, u32]),
         "mi355_engine_describe": (C.c_int, [vp, C.c_char_p, sz]),
@@ -101,6 +103,7 @@ EXPORTS = [
     "mi355_engine_kernel_name", "mi355_engine_algorithmic_bytes", "mi355_engine_selftest",
     "mi355_crt_carry", "mi355_crt_transform_size", "mi355_engine_describe", "mi355_crt_get_raw_digits", "mi355_crt_set_raw_digits",
     "mi355_engine_addsub", "mi355_engine_addsub_copy", "mi355_engine_mul_add", "mi355_engine_square_mul_copy", "mi355_engine_mul_copy", "mi355_engine_square_mul_n",
+    "mi355_engine_exp_mul", "mi355_engine_exp_mul2",
 ]
 
 
@@ -111,6 +114,17 @@ def resolve_plan(p, spec=None):
     if not L.mi355_engine_resolve_fft(p, spec.encode() if spec else None, buf, 256):
         raise EngineError(L.mi355_engine_last_error().decode())
     return buf.value.decode()
+
+
+def u64_arg(name, v):
+    """v as a uint64_t argument of the C ABI (see u32_arg)"""
+    try:
+        iv = operator.index(v)
+    except TypeError:
+        raise TypeError("%s must be an integer, not %s" % (name, type(v).__name__)) from None
+    if not 0 <= iv <= 0xFFFFFFFFFFFFFFFF:
+        raise ValueError("%s = %d is outside the 64-bit range [0, 2**64) of the engine's C ABI" % (name, iv))
+    return iv
 
 
 def _ptr(a):
@@ -184,10 +198,20 @@ class Engine:
         self._ok(self.L.mi355_engine_square_mul_n(self.h, src, u32_arg("factor", a), count, u32_arg("sub", sub)))
     def mul_copy(self, dst, src, dst_copy, a=1): self._ok(self.L.mi355_engine_mul_copy(self.h, dst, src, dst_copy, u32_arg("factor", a)))
 
+    def exp_mul(self, a, h, b, tmp):
+        """a = a^h * b with a 64-bit h, in one engine call (the fold of a PRP proof); b and tmp are consumed."""
+        self._ok(self.L.mi355_engine_exp_mul(self.h, a, u64_arg("h", h), b, tmp))
+
+    def exp_mul2(self, a, h, b, tmp):
+        """a = a^h * b^2; b and tmp are consumed."""
+        self._ok(self.L.mi355_engine_exp_mul2(self.h, a, u64_arg("h", h), b, tmp))
+
     def is_equal(self, lhs, rhs):
         out = C.c_int(0)
         self._ok(self.L.mi355_engine_equal(self.h, lhs, rhs, C.byref(out)))
         return bool(out.value)
+
+    equal = is_equal        # the names prmers_amd/proof.py uses
 
     def pow(self, dst, src, e):
         """dst = src^e, src is erased (engine.h:160-170)."""
@@ -220,6 +244,8 @@ class Engine:
         w = np.zeros(self.word_count, dtype=np.uint32)
         self._ok(self.L.mi355_engine_get_words(self.h, src, _ptr(w), w.size))
         return w
+
+    get_words = words
 
     def set_words(self, dst, w):
         w = np.ascontiguousarray(w, dtype=np.uint32)

@@ -11,6 +11,7 @@ Everything here talks to an engine only through its interface (set / copy / squa
 set_multiplicand / mul / get_int / digits / get_checkpoint / set_checkpoint), so the same driver runs
 on prmers_amd.Engine (MI355X) and, in the CPU tests, on an oracle-backed stand-in.
 """
+import bisect
 import math
 import os
 import struct
@@ -223,7 +224,7 @@ def _square_n(eng, reg, count, sub=0):
 
 def run_prp_or_ll(eng, p, mode="prp", gerbicz=True, erroriter=0, checklevel=0, max_iters=None,
                   log=None, ckpt_path=None, backup_every=0, resume=None, stop_after_s=None, on_check=None, should_stop=None,
-                  backup_interval_s=None):
+                  backup_interval_s=None, proof_power=0, proof_dir="."):
     """One PRP (mode "prp") or LL-unsafe (mode "ll") test of 2^p-1 on `eng` (>= 8 registers).
 
     Returns a dict: is_prime, res64, res2048, iterations, gerbicz_checks, gerbicz_errors, complete.
@@ -239,6 +240,9 @@ def run_prp_or_ll(eng, p, mode="prp", gerbicz=True, erroriter=0, checklevel=0, m
     returns with complete = False and interrupted = True -- the reference's SIGINT path (RunPrpOrLlMarin.cpp:296-309).
     A checkpoint carries the Gerbicz-Li rollback point (R4 / R5 inside the register dump, itersave / jsave / checkpass in
     the side file): a check that fails after a resume rolls back to the block the checkpoint itself was verified from.
+    proof_power > 0 (PRP only): the residue words at the 2^proof_power proof points are saved under <proof_dir>/<p>/proof/ as the run
+    passes them (prmers_amd/proof.py ProofPoints; the reference's ProofManagerMarin::checkpointMarin) -- a run resumed from a checkpoint
+    goes on from its iteration, the points before it are on disk already; proof.build_proof turns them into the proof file.
     """
     import time as _time
     t_start = _time.time()
@@ -285,6 +289,11 @@ def run_prp_or_ll(eng, p, mode="prp", gerbicz=True, erroriter=0, checklevel=0, m
     interrupted = False
     batched = hasattr(eng, "square_mul_n")
 
+    points = None
+    if proof_power and prp:
+        from .proof import ProofPoints
+        points = ProofPoints(p, proof_power, proof_dir)
+
     last_backup = [t_start]
 
     def checkpoint(at):
@@ -320,6 +329,8 @@ def run_prp_or_ll(eng, p, mode="prp", gerbicz=True, erroriter=0, checklevel=0, m
                 r = min(r, 256 - (done & 255))
             if should_stop is not None or stop_after_s is not None:
                 r = min(r, 256)
+            if points is not None:
+                r = min(r, points.points[bisect.bisect_right(points.points, it)] - it)   # (p itself is a point: there is a next one)
             r = max(r, 1)
         _square_n(eng, R0, r, 0 if prp else 2)
         it += r - 1
@@ -369,6 +380,9 @@ def run_prp_or_ll(eng, p, mode="prp", gerbicz=True, erroriter=0, checklevel=0, m
                     itersave, jsave = it, j
                     if stop_after_s is not None and _time.time() - t_start > stop_after_s and it != total - 1:
                         state = {"it": it, "j": j}
+        if points is not None and points.should_checkpoint(it + 1):   # R0 holds the residue after it + 1 squarings (after a rollback too)
+            get_words = getattr(eng, "get_words", None)
+            points.save(it + 1, get_words(R0) if get_words else pack_words(eng.digits(R0), p))
         it += 1
         j -= 1
         if ckpt_path and it < total and ((backup_every and done % backup_every == 0) or
