@@ -62,6 +62,9 @@ class engine_hip final : public engine {
     int (*get_words)(void*, size_t, uint32_t*, size_t) = nullptr;
     int (*exp_mul)(void*, size_t, uint64_t, size_t, size_t) = nullptr;
     int (*exp_mul2)(void*, size_t, uint64_t, size_t, size_t) = nullptr;
+    int (*mul_sum)(void*, size_t, size_t, size_t, size_t) = nullptr;
+    int (*mul_sum_is_fused)(void*) = nullptr;
+    int (*square_mul_bits)(void*, size_t, uint32_t, const uint8_t*, size_t) = nullptr;
 
     template <class F> void bind(F& f, const char* name) {
       f = reinterpret_cast<F>(dlsym(so, name));
@@ -98,6 +101,9 @@ class engine_hip final : public engine {
       get_words = reinterpret_cast<decltype(get_words)>(dlsym(so, "mi355_engine_get_words"));
       exp_mul = reinterpret_cast<decltype(exp_mul)>(dlsym(so, "mi355_engine_exp_mul"));
       exp_mul2 = reinterpret_cast<decltype(exp_mul2)>(dlsym(so, "mi355_engine_exp_mul2"));
+      mul_sum = reinterpret_cast<decltype(mul_sum)>(dlsym(so, "mi355_engine_mul_sum"));
+      mul_sum_is_fused = reinterpret_cast<decltype(mul_sum_is_fused)>(dlsym(so, "mi355_engine_mul_sum_is_fused"));
+      square_mul_bits = reinterpret_cast<decltype(square_mul_bits)>(dlsym(so, "mi355_engine_square_mul_bits"));
     }
     ~Api() { if (so) dlclose(so); }
   };
@@ -161,6 +167,19 @@ class engine_hip final : public engine {
   // consumed.  Not part of the reference's engine; the composition of its operations when the library does not export them.
   void exp_mul(const Reg a, const uint64_t h, const Reg b, const Reg tmp) const { exp_mul_any(a, h, b, tmp, false); }
   void exp_mul2(const Reg a, const uint64_t h, const Reg b, const Reg tmp) const { exp_mul_any(a, h, b, tmp, true); }
+  // The P-1 operations (prmers_amd/pm1.py), non-virtual extras like square_mul_n: the compositions when the library does not export them.
+  // dst = dst * (a + b) for two multiplicand images (left intact; tmp is scratch): one product where the plan's capacity allows it
+  void mul_sum(const Reg dst, const Reg src_a, const Reg src_b, const Reg tmp) const {
+    if (_api.mul_sum) { ok(_api.mul_sum(_h, dst, src_a, src_b, tmp), "mul_sum"); return; }
+    if (dst == tmp || dst == src_a || dst == src_b || tmp == src_a || tmp == src_b) throw std::runtime_error("MI355 mul_sum failed: dst, tmp and the multiplicands must differ");
+    copy(tmp, dst); mul(dst, src_a); mul(tmp, src_b); add(dst, tmp);
+  }
+  bool mul_sum_is_fused() const { return _api.mul_sum_is_fused && _api.mul_sum_is_fused(_h) != 0; }
+  // src = src^(2^nbits) * a^B, B the nbits bits of `bits` (most significant first, packed in bytes): one square_mul per bit in one call
+  void square_mul_bits(const Reg src, const uint32_t a, const uint8_t* bits, const size_t nbits) const {
+    if (_api.square_mul_bits) { ok(_api.square_mul_bits(_h, src, a, bits, nbits), "square_mul_bits"); return; }
+    for (size_t i = 0; i < nbits; ++i) square_mul(src, ((bits[i >> 3] >> (7 - (i & 7))) & 1) ? a : 1u);
+  }
   // the canonical residue as ceil(p / 32) little-endian words (2^p - 1 reads as 0) / a register from such words: packed and cut on the
   // device by the library, through the digit vector when it does not export the word entry points
   std::vector<uint32_t> get_words(const Reg src) const {

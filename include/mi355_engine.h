@@ -6,6 +6,9 @@
  * pattern binds it unchanged; the C++ adapter that serves `-engine-marin` is include/mi355/engine_hip.h
  * (hook: src/marin/gpu.cpp:149).
  *
+ * 49 symbols: the 19 shapes of that ABI, digit I/O, raw images, the fused register operations, the proof fold (exp_mul / exp_mul2), the
+ * P-1 operations (mul_sum / mul_sum_is_fused / square_mul_bits), timing hooks, the device self-test and the mi355_crt_* entry points.
+ *
  * Conventions (same as the reference ABI, EngineApi.cpp:447-517):
  *   - int results: 1 = ok, 0 = failure; the message is in mi355_engine_last_error() (thread-local,
  *     owned by the library).  create() returns NULL on failure.  No exception ever crosses the ABI.
@@ -88,6 +91,23 @@ MI355_ENGINE_API int mi355_engine_square_mul_n(mi355_engine_handle handle, size_
 MI355_ENGINE_API int mi355_engine_exp_mul(mi355_engine_handle handle, size_t a, uint64_t h, size_t b, size_t tmp);
 /* the same with b squared first: a = a^h * b^2 (PRPLL's expMul2; verification needs it when a span is odd) */
 MI355_ENGINE_API int mi355_engine_exp_mul2(mi355_engine_handle handle, size_t a, uint64_t h, size_t b, size_t tmp);
+
+/* ---- P-1 factoring (prmers_amd/pm1.py; the reference: src/modes/RunPM1.cpp) ---- */
+/* dst = dst * (a + b): src_a and src_b are multiplicand images and stay intact, dst holds a residue, tmp is scratch (content unspecified
+   afterwards); dst, tmp and the sources pairwise distinct, src_a == src_b allowed; everything is checked before the first launch.  The
+   transform is linear, so the row sweep adds the two images word by word and the operation is ONE product (three sweeps and one more read
+   of 8n bytes) -- the inner step of stage 2, A <- A (X_k - Y_j), with the table stored as images of Mp - Y_j.  The summed operand has
+   digits up to twice the usual bound: where the plan's worst case does not fit (plan.hpp sum_product_ok; crudely 2 (q + 1) + 1 + log2 n
+   >= 64: the largest exponents of a transform size) and on a crt handle the same result comes from the two-product composition
+   copy(tmp, dst); mul(dst, a); mul(tmp, b); add(dst, tmp). */
+MI355_ENGINE_API int mi355_engine_mul_sum(mi355_engine_handle handle, size_t dst, size_t src_a, size_t src_b, size_t tmp);
+/* 1: mul_sum runs as one product on this handle's plan; 0: as the two-product composition (or the handle is not valid) */
+MI355_ENGINE_API int mi355_engine_mul_sum_is_fused(mi355_engine_handle handle);
+/* reg = reg^(2^nbits) * factor^B, B the integer whose nbits bits are in `bits`, most significant bit first, packed in bytes (bit 7 of
+   bits[0] first).  One square_mul(reg, bit ? factor : 1) per bit, issued by the library in one call: square_mul_n with a per-step
+   factor (stage 1 of P-1 is 3^E with about 1.44 B1 bits).  A factor above the plan's fused bound follows the rule of square_mul.
+   nbits = 0: nothing happens.  Both families. */
+MI355_ENGINE_API int mi355_engine_square_mul_bits(mi355_engine_handle handle, size_t reg, uint32_t factor, const uint8_t* bits, size_t nbits);
 
 /* ---- rest of the engine surface the Marin callers use ---- */
 /* engine::get / engine::set(Reg, uint64*) (engine.h:24-25): n digits, value | width << 32, strongly

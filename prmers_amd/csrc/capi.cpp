@@ -159,6 +159,11 @@ int mi355_engine_square_mul_n(mi355_engine_handle h, size_t r, uint32_t f, size_
 }
 int mi355_engine_exp_mul(mi355_engine_handle h, size_t a, uint64_t e, size_t b, size_t tmp) { return guarded([&] { if (crt(h)) crt(h)->exp_mul(a, e, b, tmp, false); else eng(h)->exp_mul(a, e, b, tmp, false); }); }
 int mi355_engine_exp_mul2(mi355_engine_handle h, size_t a, uint64_t e, size_t b, size_t tmp) { return guarded([&] { if (crt(h)) crt(h)->exp_mul(a, e, b, tmp, true); else eng(h)->exp_mul(a, e, b, tmp, true); }); }
+int mi355_engine_mul_sum(mi355_engine_handle h, size_t dst, size_t a, size_t b, size_t tmp) { return guarded([&] { if (crt(h)) crt(h)->mul_sum(dst, a, b, tmp); else eng(h)->mul_sum(dst, a, b, tmp); }); }
+int mi355_engine_mul_sum_is_fused(mi355_engine_handle h) { int r = 0; guarded([&] { r = (!crt(h) && eng(h)->mul_sum_is_fused()) ? 1 : 0; }); return r; }
+int mi355_engine_square_mul_bits(mi355_engine_handle h, size_t r, uint32_t f, const uint8_t* bits, size_t nbits) {
+  return guarded([&] { if (crt(h)) crt(h)->square_mul_bits(r, f, bits, nbits); else eng(h)->square_mul_bits(r, f, bits, nbits); });
+}
 int mi355_engine_mul_copy(mi355_engine_handle h, size_t dst, size_t src, size_t cp, uint32_t f) { return guarded([&] { if (crt(h)) crt(h)->mul_copy(dst, src, cp, f); else eng(h)->mul_copy(dst, src, cp, f); }); }
 
 int mi355_engine_get_digits(mi355_engine_handle h, size_t src, uint64_t* d, size_t count) {

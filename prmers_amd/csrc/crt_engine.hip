@@ -492,6 +492,24 @@ void CrtEngine::exp_mul(size_t a, uint64_t h, size_t b, size_t tmp, bool square_
   if (h != 0) mul(a, b, 1);
 }
 
+// dst = dst (a + b): copy(tmp, dst); mul(dst, a); mul(tmp, b); add(dst, tmp).  Checked before the first launch.
+void CrtEngine::mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp) {
+  Impl& im = *im_;
+  check_digits(dst, "mul_sum");
+  if (src_a >= im.regs.size() || src_b >= im.regs.size() || tmp >= im.regs.size()) throw std::runtime_error("mul_sum: register index out of range");
+  if (!im.regs[src_a].image || !im.regs[src_b].image) throw std::runtime_error("mul_sum: src_a and src_b must be multiplicands (set_multiplicand)");
+  if (dst == tmp || tmp == src_a || tmp == src_b)
+    throw std::runtime_error("mul_sum: dst, tmp and the multiplicands must be different registers (src_a == src_b is allowed)");
+  copy(tmp, dst); mul(dst, src_a, 1); mul(tmp, src_b, 1); add(dst, tmp);
+}
+void CrtEngine::square_mul_bits(size_t reg, uint32_t factor, const uint8_t* bits, size_t nbits) {
+  check_digits(reg, "square_mul_bits");
+  if (factor == 0) throw std::runtime_error("square_mul_bits: factor must be >= 1");
+  if (nbits == 0) return;
+  if (!bits) throw std::runtime_error("square_mul_bits: null bit string");
+  for (size_t i = 0; i < nbits; ++i) square_mul(reg, ((bits[i >> 3] >> (7 - (i & 7))) & 1) ? factor : 1u);
+}
+
 void CrtEngine::set_u32(size_t reg, uint32_t a) {
   Impl& im = *im_;
   if (reg >= im.regs.size()) throw std::runtime_error("set: register index out of range");

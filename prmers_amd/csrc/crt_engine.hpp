@@ -47,6 +47,10 @@ class CrtEngine {
   void mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t f);
   // a = a^h * b (b squared first when square_b), PRPLL's expMul / expMul2, composed of the operations above; b and tmp end as images
   void exp_mul(size_t a, uint64_t h, size_t b, size_t tmp, bool square_b);
+  // dst = dst (a + b) for two multiplicand images, as the exact two-product composition (this family has no fused form), and
+  // reg = reg^(2^nbits) factor^B as one square_mul per bit of B (most significant first): the P-1 operations of mi355_engine.h
+  void mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp);
+  void square_mul_bits(size_t reg, uint32_t factor, const uint8_t* bits, size_t nbits);
   bool equal(size_t a, size_t b);
   void set_digits(size_t reg, const uint64_t* d, size_t count);
   void get_digits(size_t reg, uint64_t* d, size_t count, bool canonical);

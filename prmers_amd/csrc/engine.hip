@@ -227,8 +227,8 @@ void Engine::run_front(size_t r) {
   else HIPCHK(cols_.front(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, work(), stream_));
 }
 
-void Engine::run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode) {
-  HIPCHK(rows_(dp_, in, y, out, mode, stream_));
+void Engine::run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, const uint64_t* y2) {
+  HIPCHK(rows_(dp_, in, y, y2, out, mode, stream_));
 }
 
 // work() -> digits(r) + run carries in cbuf(r): runs of 2C >= 4 digits leave them to the next sweep, which folds them in, runs of two
@@ -681,6 +681,31 @@ void Engine::exp_mul(size_t a, uint64_t h, size_t b, size_t tmp, bool square_b) 
   }
   prepare(b, b);
   if (h != 0) mul(a, b, 1);
+}
+
+// dst = dst (a + b).  Everything is checked before the first launch, so a refused call leaves the registers as they were.
+void Engine::mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp) {
+  need_digits(dst, "mul_sum"); check_reg(src_a); check_reg(src_b); check_reg(tmp);
+  if (kind_[src_a] != kImage || kind_[src_b] != kImage) throw std::runtime_error("mul_sum: src_a and src_b must be multiplicands (set_multiplicand)");
+  if (dst == tmp || dst == src_a || dst == src_b || tmp == src_a || tmp == src_b)
+    throw std::runtime_error("mul_sum: dst, tmp and the multiplicands must be different registers (src_a == src_b is allowed)");
+  HIPCHK(hipSetDevice(device_));
+  if (!pl_.sum_fast) {   // the summed operand is beyond the plan's capacity (plan.hpp sum_product_ok): two products, exact for every plan
+    copy(tmp, dst); mul(dst, src_a, 1); mul(tmp, src_b, 1); add(dst, tmp);
+    return;
+  }
+  run_front(dst);   // pending run carries (and a borrowed-through sub) of dst go in exactly as in mul
+  run_middle(work(), image(src_a), work(), 3, image(src_b));
+  run_back(dst, 1);
+}
+
+void Engine::square_mul_bits(size_t r, uint32_t factor, const uint8_t* bits, size_t nbits) {
+  need_digits(r, "square_mul_bits");
+  if (factor == 0) throw std::runtime_error("square_mul_bits: factor must be >= 1");
+  if (nbits == 0) return;
+  if (!bits) throw std::runtime_error("square_mul_bits: null bit string");
+  HIPCHK(hipSetDevice(device_));
+  for (size_t i = 0; i < nbits; ++i) square_chain(r, ((bits[i >> 3] >> (7 - (i & 7))) & 1) ? factor : 1u, nullptr);
 }
 
 void Engine::sub_u32(size_t r, uint32_t v) {

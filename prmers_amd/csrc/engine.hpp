@@ -54,6 +54,14 @@ class Engine {
   void mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t a);
   // a = a^h * b (b squared first when square_b): the fold of a PRP proof (PRPLL's expMul / expMul2).  b and tmp end as multiplicand images.
   void exp_mul(size_t a, uint64_t h, size_t b, size_t tmp, bool square_b);
+  // dst = dst * (a + b): src_a, src_b multiplicand images (left intact, may be the same register), tmp scratch.  One product through the row
+  // sweep's mode 3 where the plan's capacity allows it (plan.hpp sum_product_ok), else copy(tmp, dst); mul(dst, a); mul(tmp, b); add(dst, tmp).
+  // The inner step of P-1 stage 2, A <- A (X_k - Y_j), with the table stored as images of Mp - Y_j.
+  void mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp);
+  bool mul_sum_is_fused() const { return pl_.sum_fast; }
+  // reg = reg^(2^nbits) * factor^B, B the nbits-bit integer in `bits` (most significant bit first, packed in bytes, bit 7 of a byte first):
+  // one square_mul(reg, bit ? factor : 1) per bit -- square_mul_n with a per-step factor (stage 1 of P-1: 3^E)
+  void square_mul_bits(size_t r, uint32_t factor, const uint8_t* bits, size_t nbits);
 
   size_t register_data_size() const { return reg_bytes_ + 8; }
   void get_data(size_t src, void* data, size_t size);
@@ -99,7 +107,7 @@ class Engine {
                                                    // them); excess: bits of a carry word above the first digit's width (-1: a <= 15)
   void scale(size_t r, uint32_t a);   // r x a, run-wise (k_scale): factors above pl_.a_fast
   void run_front(size_t r);          // digits(r) (+ pending run carries) -> work_
-  void run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode);
+  void run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, const uint64_t* y2 = nullptr);
   void run_back(size_t r, uint32_t a, hipEvent_t* ev = nullptr);
 
   Plan pl_;

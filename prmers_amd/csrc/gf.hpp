@@ -154,6 +154,12 @@ GF_HD uint64_t fold(uint64_t a) {
 #endif
 }
 
+// a + b for ANY two 64-bit representatives (both may be un-folded: two stored outputs of dft8<INV, 2>, the words of two multiplicand
+// images).  a is folded first, so the 65-bit sum is below P + 2^64 and the single carry fold of add_lazy cannot overflow again
+// (fold(a) + b - 2^64 + EPS <= (P - 1) + (2^64 - 1) - 2^64 + EPS = 2^64 - 2).  The result is lazy like add_lazy's: congruent to a + b,
+// anywhere in [0, 2^64), only for values whose next use is a multiplication.
+GF_HD uint64_t add_lazy_any(uint64_t a, uint64_t b) { return add_lazy(fold(a), b); }
+
 GF_HD uint64_t sub(uint64_t a, uint64_t b) {
 #if defined(__HIP_DEVICE_COMPILE__)
   // the borrow comes out of the 32-bit subtract-with-borrow pair itself (one 64-bit compare less than

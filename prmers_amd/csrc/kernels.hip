@@ -326,9 +326,9 @@ __global__ void __launch_bounds__(1024) k_front(DevPlan pl, const uint32_t* __re
 }
 
 // ---------------------------------------------------------------------------------------------
-// middle: one work-group per row.  mode 0: square, 1: multiply by image Y, 2: forward only.
+// middle: one work-group per row.  mode 0: square, 1: multiply by image Y, 2: forward only, 3: multiply by the sum of the images Y and Y2.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* Win, const uint64_t* Yimg, uint64_t* Wout, int mode, uint32_t sub, uint32_t row,
+__device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* Win, const uint64_t* Yimg, const uint64_t* Yimg2, uint64_t* Wout, int mode, uint32_t sub, uint32_t row,
                                             P2* X, uint32_t tid, uint32_t nthr) {
   const uint32_t M2 = pl.M2;
   const P2* in = reinterpret_cast<const P2*>(Win) + size_t(row) * M2;
@@ -361,7 +361,11 @@ __device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* W
       r.a = gf::add(gf::sqr(u.a), gf::mul(gf::sqr(u.b), rho));
       r.b = gf::mul(u.b, gf::dbl(u.a));
     } else {          // marin.cl:387-392
-      const P2 y = Y[e];
+      P2 y = Y[e];
+      if (mode == 3) {   // the image of a sum is the word-wise sum of the images (lazy: the products below take any representative)
+        const P2 z = reinterpret_cast<const P2*>(Yimg2)[size_t(row) * M2 + e];
+        y = {gf::add_lazy_any(y.a, z.a), gf::add_lazy_any(y.b, z.b)};
+      }
       r.a = gf::add(gf::mul(u.a, y.a), gf::mul(gf::mul(u.b, y.b), rho));
       r.b = gf::add(gf::mul(u.a, y.b), gf::mul(u.b, y.a));
     }
@@ -372,8 +376,8 @@ __device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* W
   for (uint32_t e = tid; e < M2; e += nthr) out[e] = X[e];
 }
 __global__ void __launch_bounds__(1024) k_middle(DevPlan pl, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Yimg,
-                                                uint64_t* __restrict__ Wout, int mode, uint32_t sub) {
-  middle_body(pl, Win, Yimg, Wout, mode, sub, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
+                                                const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout, int mode, uint32_t sub) {
+  middle_body(pl, Win, Yimg, Yimg2, Wout, mode, sub, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -733,8 +737,8 @@ hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_
   hipLaunchKernelGGL(k_front, dim3(pl.M2 / pl.C), dim3(block_for_small(pl, tile)), tile * 16, s, pl, digits, cbuf_in, W);
   return hipGetLastError();
 }
-hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s) {
-  hipLaunchKernelGGL(k_middle, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Y, Wout, mode, 0u);
+hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) {
+  hipLaunchKernelGGL(k_middle, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Y, Y2, Wout, mode, 0u);
   return hipGetLastError();
 }
 hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s) {

@@ -64,11 +64,12 @@ __device__ __forceinline__ uint32_t idx_e(uint32_t t, uint32_t j) { return 4u * 
 //   S4 d4 (k1, k2, k3 = t3..2, d5 = t1..0) -> k4 ; x omega_16^(k4 (t & 3))
 //   S5 d5 (k1, k2, k3, k4 = t1..0)         -> k5 ; X[k], k = k1 + 4 k2 + 16 k3 + 64 k4 + 256 k5
 // pointwise in registers (rho = rho0 omega_4^k5), then the mirror image back to natural order.
-// mode 0: square, 1: multiply by image Y, 2: forward only (writes the image: register j of thread t at 256 j + t).
+// mode 0: square, 1: multiply by image Y, 2: forward only (writes the image: register j of thread t at 256 j + t),
+// 3: multiply by the word-wise sum of the images Y and Y2 (mode 1 with y = Y[i] + Y2[i], gf::add_lazy_any).
 // ---------------------------------------------------------------------------------------------
 template <int mode>
 __global__ void __launch_bounds__(kThreads) k2_rows1024(DevPlan pl, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Yimg,
-                                                        uint64_t* __restrict__ Wout, uint32_t sub) {
+                                                        const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout, uint32_t sub) {
   P2* X = reinterpret_cast<P2*>(v2::smem_v2);
   const uint32_t t = threadIdx.x, row = blockIdx.x;
   const P2* in = reinterpret_cast<const P2*>(Win) + size_t(row) * 1024;
@@ -145,7 +146,11 @@ __global__ void __launch_bounds__(kThreads) k2_rows1024(DevPlan pl, const uint64
         s0 = gf::sqr(u.a);
         r.b = gf::dbl(gf::mul(u.b, u.a));
       } else {           // marin.cl:387-392
-        const P2 y = Y[256 * k5 + t];
+        P2 y = Y[256 * k5 + t];
+        if (mode == 3) {
+          const P2 z = (reinterpret_cast<const P2*>(Yimg2) + size_t(row) * 1024)[256 * k5 + t];
+          y = {gf::add_lazy_any(y.a, z.a), gf::add_lazy_any(y.b, z.b)};
+        }
         q = gf::mul(gf::mul(u.b, y.b), rho0);
         s0 = gf::mul(u.a, y.a);
         r.b = gf::add(gf::mul(u.a, y.b), gf::mul(u.b, y.a));
@@ -212,7 +217,7 @@ __device__ __forceinline__ void twiddle3w(uint64_t (&x)[4], const uint64_t (&w)[
 
 template <int mode>
 __global__ void __launch_bounds__(2 * kThreads) k2_rows1024_planes(DevPlan pl, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Yimg,
-                                                                   uint64_t* __restrict__ Wout, uint32_t sub) {
+                                                                   const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout, uint32_t sub) {
   uint64_t* X = reinterpret_cast<uint64_t*>(v2::smem_v2);
   const uint32_t t = threadIdx.x >> 1, pln = threadIdx.x & 1u, row = blockIdx.x;
   const uint64_t* in = Win + size_t(row) * 2048;
@@ -283,7 +288,9 @@ __global__ void __launch_bounds__(2 * kThreads) k2_rows1024_planes(DevPlan pl, c
         m1 = gf::sqr(u);                      // a: u.a^2, b: u.b^2
         cross = gf::dbl(gf::mul(u, uo));      // 2 u.a u.b (both lanes)
       } else {           // marin.cl:387-392
-        const uint64_t y = Y[2 * (256 * k5 + t) + pln], yo = swap_planes(y);
+        uint64_t y = Y[2 * (256 * k5 + t) + pln];
+        if (mode == 3) y = gf::add_lazy_any(y, (Yimg2 + size_t(row) * 2048)[2 * (256 * k5 + t) + pln]);
+        const uint64_t yo = swap_planes(y);
         m1 = gf::mul(u, y);                   // a: u.a y.a, b: u.b y.b
         const uint64_t m3 = gf::mul(u, yo);   // a: u.a y.b, b: u.b y.a
         cross = gf::add(m3, swap_planes(m3));
@@ -688,20 +695,22 @@ __global__ void __launch_bounds__(kThreads) k_build_f0(DevPlan pl, uint64_t* __r
 // Two forms of every kernel (plan.hpp served_kernels picks one): a pair per thread (256 threads, the fewest instructions per word) and one
 // plane per thread (512 threads, twice the waves with half the stream each: where a CU gets one tile or fewer).
 template <int mode>
-static void launch_rows(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, bool planes, hipStream_t s) {
-  if (planes) hipLaunchKernelGGL(v3::k2_rows1024_planes<mode>, dim3(pl.M1), dim3(2 * v3::kThreads), v3::kLdsBytes, s, pl, Win, Y, Wout, 0u);
-  else hipLaunchKernelGGL(v3::k2_rows1024<mode>, dim3(pl.M1), dim3(v3::kThreads), v3::kLdsBytes, s, pl, Win, Y, Wout, 0u);
+static void launch_rows(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, bool planes, hipStream_t s) {
+  if (planes) hipLaunchKernelGGL(v3::k2_rows1024_planes<mode>, dim3(pl.M1), dim3(2 * v3::kThreads), v3::kLdsBytes, s, pl, Win, Y, Y2, Wout, 0u);
+  else hipLaunchKernelGGL(v3::k2_rows1024<mode>, dim3(pl.M1), dim3(v3::kThreads), v3::kLdsBytes, s, pl, Win, Y, Y2, Wout, 0u);
 }
-static hipError_t rows1024(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, bool planes, hipStream_t s) {
+static hipError_t rows1024(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, bool planes, hipStream_t s) {
   switch (mode) {
-    case 0: launch_rows<0>(pl, Win, Y, Wout, planes, s); break;
-    case 1: launch_rows<1>(pl, Win, Y, Wout, planes, s); break;
-    default: launch_rows<2>(pl, Win, Y, Wout, planes, s); break;
+    case 0: launch_rows<0>(pl, Win, Y, Y2, Wout, planes, s); break;
+    case 1: launch_rows<1>(pl, Win, Y, Y2, Wout, planes, s); break;
+    case 2: launch_rows<2>(pl, Win, Y, Y2, Wout, planes, s); break;
+    case 3: launch_rows<3>(pl, Win, Y, Y2, Wout, planes, s); break;
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
-hipError_t v3_rows1024_pairs(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s) { return rows1024(pl, Win, Y, Wout, mode, false, s); }
-hipError_t v3_rows1024_planes(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, uint64_t* Wout, int mode, hipStream_t s) { return rows1024(pl, Win, Y, Wout, mode, true, s); }
+hipError_t v3_rows1024_pairs(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) { return rows1024(pl, Win, Y, Y2, Wout, mode, false, s); }
+hipError_t v3_rows1024_planes(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) { return rows1024(pl, Win, Y, Y2, Wout, mode, true, s); }
 
 template <bool PLANES>
 static hipError_t cols_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s) {

@@ -58,6 +58,7 @@ struct Plan {
   uint32_t q = 0, t = 0;    // p = q*n + t
   uint32_t twh = 0;         // omega_m^e = TWlo[e & (2^twh-1)] * TWhi[e >> twh]
   uint32_t a_fast = 1;      // largest factor the back sweeps multiply in themselves (fused_factor_ok); above it: factor 1 + k_scale
+  bool sum_fast = false;    // dst x (a + b) fits one product (sum_product_ok): mul_sum runs the row sweep's mode 3; else two products
   size_t lds_front = 0, lds_mid = 0;
 
   // host tables (uploaded as-is)
@@ -107,14 +108,15 @@ struct Plan {
 //   next sweep       E = D + (carry >> 3q) + 3, the digit the carry word leaves behind (below 2^31, so that x a fits k_scale too).
 // Runs of two digits (C = 1) take their carries at once and the local carry passes restore the digits (Engine::carry_fix_now, sized for
 // a <= 15): only the 64-bit terms are checked there, and a_fast is capped at 15.
-inline bool fused_factor_ok(uint32_t q, size_t n, uint32_t C, uint64_t a) {
+// mult: the convolution bound times mult (sum_product_ok below: dst x (y1 + y2) with factor 1).
+inline bool carry_chain_ok(uint32_t q, size_t n, uint32_t C, uint64_t a, unsigned mult) {
   typedef unsigned __int128 u128;
   const u128 field = (u128(1) << 64) - (u128(1) << 32) + 1, lim = u128(1) << 64;
   const u128 D = (u128(1) << (q + 1)) - 1;
   const size_t runs = n / (2 * size_t(C));
   u128 E = D;
   for (int it = 0; it < 64; ++it) {
-    const u128 U = (C >= 2) ? u128(n - runs) * D * D + u128(runs) * E * E : u128(n) * D * D;
+    const u128 U = u128(mult) * ((C >= 2) ? u128(n - runs) * D * D + u128(runs) * E * E : u128(n) * D * D);
     if (U >= field) return false;
     const u128 chi = U >> q;
     u128 c = 0;
@@ -134,6 +136,19 @@ inline bool fused_factor_ok(uint32_t q, size_t n, uint32_t C, uint64_t a) {
   }
   return false;
 }
+inline bool fused_factor_ok(uint32_t q, size_t n, uint32_t C, uint64_t a) { return carry_chain_ok(q, n, C, a, 1); }
+
+// Whether dst x (y1 + y2), the row sweeps' multiply-by-the-sum-of-two-images (kernels.hpp, mode 3), is exact as ONE product.  The summed
+// multiplicand has digits up to 2 D (and 2 E, the run-remainder digit, once per run), the residue side D and E as before: by Cauchy-Schwarz
+// on two vectors of equal bound sum x_i (2 y_i) <= 2 ((n - n/2C) D^2 + (n/2C) E^2).  The unweighted coefficient is z_k = sum x_i y_j 2^c(i,j)
+// with c = e_i + e_j - e_k in {0, 1} (e_j = ceil(p j / n) - p j / n, the exponent of digit j's weight), so the bound on z_k is twice that
+// again.  (fused_factor_ok leaves this factor out: for one operand pair it is the bit the size rule 2 (q + 1) + log2 n < 64 keeps free.  Here
+// it decides: near the top of a range, where almost every digit is wide, about half the pairs have c = 1, and all-ones operands at
+// p = 204799 overflow the field with the doubled multiplicand.)  So: the model above at factor 1 with the convolution bound times 4,
+// iterated to the fixed point of E (the result is the next operation's input on either side).  Crude form: 2 (q + 1) + 1 + log2 n < 64 --
+// one bit more than the size rule, so the largest exponents of a transform size with odd log2 n, and of some 5 2^k sizes, do not have it.
+// Runs of two digits: the carry passes are sized for a factor of 15, the doubling is 2.
+inline bool sum_product_ok(uint32_t q, size_t n, uint32_t C) { return carry_chain_ok(q, n, C, 1, 4); }
 
 // Kernel variants of the column sweeps (front and back) and of the row sweep.
 enum class ColKernels : uint8_t {
@@ -283,6 +298,7 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
   pl.q = uint32_t(p / pl.n);
   pl.t = uint32_t(p % pl.n);
   pl.a_fast = fused_factor_limit(pl.q, pl.n, pl.C);
+  pl.sum_fast = sum_product_ok(pl.q, pl.n, pl.C);
   if (!build_tables) return pl;
 
   const size_t n = pl.n, m = pl.m;

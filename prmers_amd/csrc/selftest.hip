@@ -99,6 +99,7 @@ void selftest_primitives(int device) {
   chk(hipSetDevice(device), "hipSetDevice");
   std::vector<uint64_t> in, out, tuples, dft8_out;
   run_family<GfScalar>("gf scalars", in, out);
+  run_family<GfLazySum>("gf lazy sum", in, out);
   run_family<GfDft8>("gf dft8", tuples, dft8_out);
   {   // v2::dft4
     in.clear(); GfDft4::fill(in);

@@ -130,6 +130,42 @@ struct GfScalar {
   }
 };
 
+// gf::add_lazy_any: the sum of two multiplicand-image words in the row sweeps' mode 3 (multiply by the sum of two images).  BOTH operands
+// are lazy, so both run over [0, 2^64); the sum's only consumer is a product with another lazy word (the transformed residue), which is
+// evaluated too.  out = sum, sum * x.
+struct GfLazySum {
+  static constexpr int IN = 2, OUT = 2;
+  static constexpr bool kHostEqualsDevice = false;
+  static void aux(std::vector<uint64_t>&) {}
+  static void fill(std::vector<uint64_t>& in) {
+    std::vector<uint64_t> e; GfScalar::edges(e);
+    for (uint64_t x : e) for (uint64_t y : e) { in.push_back(x); in.push_back(y); }
+    Rng r(0xa4093822299f31d0ull);
+    for (int i = 0; i < 4096; ++i) { in.push_back(r.next()); in.push_back(r.next()); }
+    // both operands in [P, 2^64) or just below P: the carry fold of the sum lands next to 2^64
+    for (int i = 0; i < 4096; ++i) {
+      const uint64_t hi = 0xffffffff00000000ull, lo = 0xfffffffe00000000ull;
+      in.push_back((r.next() & 0xffffffffull) | (i & 1 ? hi : lo)); in.push_back((r.next() & 0xffffffffull) | (i & 2 ? hi : lo));
+    }
+  }
+  static GF_HDM void eval(const uint64_t* in, uint64_t* o, const uint64_t*) {
+    o[0] = gf::add_lazy_any(in[0], in[1]);
+    o[1] = gf::mul(o[0], in[0]);
+  }
+  static std::string check(const uint64_t* in, const uint64_t* out, size_t n) {
+    size_t both_lazy = 0, sum_lazy = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const uint64_t x = in[2 * i], y = in[2 * i + 1];
+      const uint64_t sum = uint64_t((u128(x % P) + y % P) % P);
+      if (out[2 * i] % P != sum) return msg("gf add_lazy_any: a=%016llx b=%016llx got %016llx", MI355_X(x), MI355_X(y), MI355_X(out[2 * i]));
+      if (out[2 * i + 1] != gf_mulmod(sum, x)) return msg("gf mul of a lazy sum: a=%016llx b=%016llx got %016llx", MI355_X(x), MI355_X(y), MI355_X(out[2 * i + 1]));
+      both_lazy += (x > P && y > P); sum_lazy += out[2 * i] > P;
+    }
+    if (!both_lazy || !sum_lazy) return msg("gf add_lazy_any: the operand list misses a lazy case (both operands above P: %zu, sum above P: %zu)", both_lazy, sum_lazy);
+    return "";
+  }
+};
+
 // ------------------------------------------------------------------------------------------------------------------------------------
 // GF(P) butterflies
 // ------------------------------------------------------------------------------------------------------------------------------------

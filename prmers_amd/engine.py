@@ -78,6 +78,9 @@ def load_library():
         "mi355_engine_mul_copy": (C.c_int, [vp, sz, sz, sz, u32]),
         "mi355_engine_exp_mul": (C.c_int, [vp, sz, C.c_uint64, sz, sz]),
         "mi355_engine_exp_mul2": (C.c_int, [vp, sz, C.c_uint64, sz, sz]),
+        "mi355_engine_mul_sum": (C.c_int, [vp, sz, sz, sz, sz]),
+        "mi355_engine_mul_sum_is_fused": (C.c_int, [vp]),
+        "mi355_engine_square_mul_bits": (C.c_int, [vp, sz, u32, C.c_char_p, sz]),
         "mi355_crt_carry": (C.c_int, [u32, sz, u32, u32, vp, vp, vp, vp, sz, dp]),
         "mi355_crt_transform_size": (sz, [u32, u32]),
         "mi355_engine_describe": (C.c_int, [vp, C.c_char_p, sz]),
@@ -104,6 +107,7 @@ EXPORTS = [
     "mi355_crt_carry", "mi355_crt_transform_size", "mi355_engine_describe", "mi355_crt_get_raw_digits", "mi355_crt_set_raw_digits",
     "mi355_engine_addsub", "mi355_engine_addsub_copy", "mi355_engine_mul_add", "mi355_engine_square_mul_copy", "mi355_engine_mul_copy", "mi355_engine_square_mul_n",
     "mi355_engine_exp_mul", "mi355_engine_exp_mul2",
+    "mi355_engine_mul_sum", "mi355_engine_mul_sum_is_fused", "mi355_engine_square_mul_bits",
 ]
 
 
@@ -205,6 +209,21 @@ class Engine:
     def exp_mul2(self, a, h, b, tmp):
         """a = a^h * b^2; b and tmp are consumed."""
         self._ok(self.L.mi355_engine_exp_mul2(self.h, a, u64_arg("h", h), b, tmp))
+
+    def mul_sum(self, dst, src_a, src_b, tmp):
+        """dst = dst * (a + b) for two multiplicand images (left intact; tmp is scratch): one product where the plan allows it."""
+        self._ok(self.L.mi355_engine_mul_sum(self.h, dst, src_a, src_b, tmp))
+
+    def mul_sum_is_fused(self):
+        """True if mul_sum runs as one product on this plan (False: the two-product composition, same result)"""
+        return bool(self.L.mi355_engine_mul_sum_is_fused(self.h))
+
+    def square_mul_bits(self, reg, factor, bits, nbits):
+        """reg = reg^(2^nbits) * factor^B, B = the nbits bits of `bits` (bytes, most significant bit first), in one engine call."""
+        bits = bytes(bits)
+        if nbits < 0 or nbits > 8 * len(bits):
+            raise ValueError("nbits = %d does not fit the %d bytes given" % (nbits, len(bits)))
+        self._ok(self.L.mi355_engine_square_mul_bits(self.h, reg, u32_arg("factor", factor), bits, nbits))
 
     def is_equal(self, lhs, rhs):
         out = C.c_int(0)
