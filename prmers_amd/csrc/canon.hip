@@ -16,12 +16,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels.hpp"
+#include "canon.hpp"
 
 namespace mi355 {
 namespace {
-
-struct CanonGeom { uint32_t p, n, logn2, r5, M1, M2, C; };   // n = r5 * 2^logn2 (r5: the odd factor 1, 3, 5 or 9); M1 = 0: natural digit order
 
 __device__ __forceinline__ uint64_t ceil_pj_n(const CanonGeom& g, uint64_t j) {
   const uint64_t x = uint64_t(g.p) * j + (g.n - 1);
@@ -267,111 +265,79 @@ void launch_pipeline(const CanonGeom& g, const T* digits, T* out, T* A, T* B, ui
   hipLaunchKernelGGL(k_apply<T>, dim3(nb), dim3(256), 0, s, gn, B, cin, flags, out);
 }
 
-CanonGeom geom_of(const DevPlan& pl, uint32_t p) {
-  CanonGeom g;
-  g.p = p; g.n = pl.n; g.r5 = pl.r5; g.M1 = pl.M1; g.M2 = pl.M2; g.C = pl.C;
-  g.logn2 = 0;
-  while ((uint64_t(pl.r5) << g.logn2) < pl.n) ++g.logn2;
-  return g;
-}
+constexpr size_t blocks_of(uint32_t n) { return (size_t(n) + kBlockDigits - 1) / kBlockDigits; }
+uint32_t word_count_of(const CanonGeom& g) { return uint32_t((uint64_t(g.p) + 31) / 32); }
 
 }  // namespace
 
-size_t canon_scratch_words(const DevPlan& pl) {
-  const size_t nb = (size_t(pl.n) + kBlockDigits - 1) / kBlockDigits;
-  return 2 * size_t(pl.n) + 2 * nb + 16;   // two digit arrays, block aggregates, block carries, flags
-}
-
-// digits: normalised register (tile-major).  out: n canonical digits, natural order.  scratch: canon_scratch_words() u32.
-// flags (device, inside scratch; the caller clears them): [0] value was 2^p - 1 (written as 0), [1] a digit was still
-// too wide for the 0/1 carry chain (sticky; the caller then uses the host carry), [2] compare result (sticky).
-hipError_t canon_launch(const DevPlan& pl, uint32_t p, const uint32_t* digits, uint32_t* out, uint32_t* scratch, hipStream_t s) {
-  const CanonGeom g = geom_of(pl, p);
-  const uint32_t n = pl.n, nb = (n + kBlockDigits - 1) / kBlockDigits;
-  uint32_t* agg = scratch + 2 * size_t(n);
-  launch_pipeline<uint32_t>(g, digits, out, scratch, scratch + n, agg, agg + nb, agg + 2 * nb, s);
-  return hipGetLastError();
-}
-uint32_t* canon_flags(const DevPlan& pl, uint32_t* scratch) {
-  const size_t nb = (size_t(pl.n) + kBlockDigits - 1) / kBlockDigits;
-  return scratch + 2 * size_t(pl.n) + 2 * nb;
-}
-hipError_t canon_relax(const DevPlan& pl, uint32_t p, const uint32_t* in, uint32_t* out, hipStream_t s) {
-  hipLaunchKernelGGL(k_relax, dim3(uint32_t((size_t(pl.n) / 2 + 255) / 256)), dim3(256), 0, s, geom_of(pl, p), in, out);
-  return hipGetLastError();
-}
-hipError_t canon_scatter(const DevPlan& pl, uint32_t p, const uint32_t* nat, uint32_t* digits, hipStream_t s) {
-  hipLaunchKernelGGL(k_scatter, dim3((pl.n + 255) / 256), dim3(256), 0, s, geom_of(pl, p), nat, digits);
-  return hipGetLastError();
-}
-hipError_t canon_set_small(const DevPlan& pl, uint32_t p, uint32_t* digits, uint32_t value, hipStream_t s) {
-  hipLaunchKernelGGL(k_set_small, dim3(1), dim3(64), 0, s, geom_of(pl, p), digits, value);
-  return hipGetLastError();
-}
-// canon: n canonical digits in natural order (canon_launch) -> words: ceil(p / 32) little-endian words of the residue
-hipError_t canon_pack_words(const DevPlan& pl, uint32_t p, const uint32_t* canon, uint32_t* words, hipStream_t s) {
-  CanonGeom g = geom_of(pl, p); g.M1 = 0;
-  const uint32_t wc = uint32_t((uint64_t(p) + 31) / 32);
-  hipLaunchKernelGGL(k_pack_words<uint32_t>, dim3((wc + 255) / 256), dim3(256), 0, s, g, canon, words, wc);
-  return hipGetLastError();
-}
-// words: ceil(p / 32) words of a value below 2^p -> the digits of a register (tile-major)
-hipError_t canon_unpack_words(const DevPlan& pl, uint32_t p, const uint32_t* words, uint32_t* digits, hipStream_t s) {
-  const uint32_t wc = uint32_t((uint64_t(p) + 31) / 32);
-  hipLaunchKernelGGL(k_unpack_words<uint32_t>, dim3((pl.n + 255) / 256), dim3(256), 0, s, geom_of(pl, p), words, wc, digits);
-  return hipGetLastError();
-}
-hipError_t canon_compare(const uint32_t* a, const uint32_t* b, uint32_t n, uint32_t* diff_flag, hipStream_t s) {
-  hipLaunchKernelGGL(k_compare<uint32_t>, dim3((n + 255) / 256), dim3(256), 0, s, a, b, n, diff_flag);
-  return hipGetLastError();
-}
-
-// ---- the same for the second field family: u64 digits in natural order, n = odd * 2^ln (crt_engine.hip) ----
-static CanonGeom geom64(uint32_t p, uint32_t n, uint32_t odd) {
+CanonGeom CanonGeom::natural(uint32_t p, uint32_t n, uint32_t odd) {
   CanonGeom g;
   g.p = p; g.n = n; g.r5 = odd; g.M1 = 0; g.M2 = 0; g.C = 0;
   g.logn2 = 0;
   while ((uint64_t(odd) << g.logn2) < n) ++g.logn2;
   return g;
 }
-size_t canon64_scratch_bytes(uint32_t n) {
-  const size_t nb = (size_t(n) + kBlockDigits - 1) / kBlockDigits;
-  return 2 * size_t(n) * 8 + (2 * nb + 16) * 4;
+CanonGeom CanonGeom::tile_major(const DevPlan& pl, uint32_t p) {
+  CanonGeom g = natural(p, pl.n, pl.r5);
+  g.M1 = pl.M1; g.M2 = pl.M2; g.C = pl.C;
+  return g;
 }
-uint32_t* canon64_flags(uint32_t n, void* scratch) {
-  const size_t nb = (size_t(n) + kBlockDigits - 1) / kBlockDigits;
-  return reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(scratch) + 2 * size_t(n) * 8) + 2 * nb;
+
+template <class T> size_t canon_scratch_bytes(const CanonGeom& g) { return 2 * size_t(g.n) * sizeof(T) + (2 * blocks_of(g.n) + 16) * 4; }
+template <class T> uint32_t* canon_flags(const CanonGeom& g, void* scratch) {
+  return reinterpret_cast<uint32_t*>(static_cast<T*>(scratch) + 2 * size_t(g.n)) + 2 * blocks_of(g.n);
 }
-// digits: weakly carried u64 digits (any excess the three local passes remove: up to ~3 w bits); out: canonical digits, 2^p - 1 -> 0
-hipError_t canon64_launch(uint32_t p, uint32_t n, uint32_t odd, const uint64_t* digits, uint64_t* out, void* scratch, hipStream_t s) {
-  const CanonGeom g = geom64(p, n, odd);
-  const size_t nb = (size_t(n) + kBlockDigits - 1) / kBlockDigits;
-  uint64_t* A = static_cast<uint64_t*>(scratch);
-  uint32_t* agg = reinterpret_cast<uint32_t*>(A + 2 * size_t(n));
-  launch_pipeline<uint64_t>(g, digits, out, A, A + n, agg, agg + nb, agg + 2 * nb, s);
+template <class T> hipError_t canon_launch(const CanonGeom& g, const T* digits, T* out, void* scratch, hipStream_t s) {
+  T* A = static_cast<T*>(scratch);
+  uint32_t* agg = reinterpret_cast<uint32_t*>(A + 2 * size_t(g.n));
+  const size_t nb = blocks_of(g.n);
+  launch_pipeline<T>(g, digits, out, A, A + g.n, agg, agg + nb, agg + 2 * nb, s);
   return hipGetLastError();
 }
-hipError_t canon64_pack_words(uint32_t p, uint32_t n, uint32_t odd, const uint64_t* canon, uint32_t* words, hipStream_t s) {
-  const uint32_t wc = uint32_t((uint64_t(p) + 31) / 32);
-  hipLaunchKernelGGL(k_pack_words<uint64_t>, dim3((wc + 255) / 256), dim3(256), 0, s, geom64(p, n, odd), canon, words, wc);
+template <class T> hipError_t canon_compare(const T* a, const T* b, uint32_t n, uint32_t* diff_flag, hipStream_t s) {
+  hipLaunchKernelGGL(k_compare<T>, dim3((n + 255) / 256), dim3(256), 0, s, a, b, n, diff_flag);
   return hipGetLastError();
 }
-hipError_t canon64_unpack_words(uint32_t p, uint32_t n, uint32_t odd, const uint32_t* words, uint64_t* digits, hipStream_t s) {
-  const uint32_t wc = uint32_t((uint64_t(p) + 31) / 32);
-  hipLaunchKernelGGL(k_unpack_words<uint64_t>, dim3((n + 255) / 256), dim3(256), 0, s, geom64(p, n, odd), words, wc, digits);
+template <class T> hipError_t canon_pack_words(const CanonGeom& g, const T* canon, uint32_t* words, hipStream_t s) {
+  CanonGeom gn = g; gn.M1 = 0;   // the canonical digits are in natural order
+  const uint32_t wc = word_count_of(g);
+  hipLaunchKernelGGL(k_pack_words<T>, dim3((wc + 255) / 256), dim3(256), 0, s, gn, canon, words, wc);
   return hipGetLastError();
 }
-hipError_t canon64_compare(const uint64_t* a, const uint64_t* b, uint32_t n, uint32_t* diff_flag, hipStream_t s) {
-  hipLaunchKernelGGL(k_compare<uint64_t>, dim3((n + 255) / 256), dim3(256), 0, s, a, b, n, diff_flag);
+template <class T> hipError_t canon_unpack_words(const CanonGeom& g, const uint32_t* words, T* digits, hipStream_t s) {
+  hipLaunchKernelGGL(k_unpack_words<T>, dim3((g.n + 255) / 256), dim3(256), 0, s, g, words, word_count_of(g), digits);
   return hipGetLastError();
 }
-// one local carry pass (in -> out): digits of up to w + e bits come out below 2^w + 2^e
-hipError_t canon64_relax(uint32_t p, uint32_t n, uint32_t odd, const uint64_t* in, uint64_t* out, hipStream_t s) {
-  hipLaunchKernelGGL(k_local<uint64_t>, dim3((n + 255) / 256), dim3(256), 0, s, geom64(p, n, odd), in, out);
+#define MI355_CANON_FOR(T)                                                                                      \
+  template size_t canon_scratch_bytes<T>(const CanonGeom&);                                                     \
+  template uint32_t* canon_flags<T>(const CanonGeom&, void*);                                                   \
+  template hipError_t canon_launch<T>(const CanonGeom&, const T*, T*, void*, hipStream_t);                      \
+  template hipError_t canon_compare<T>(const T*, const T*, uint32_t, uint32_t*, hipStream_t);                   \
+  template hipError_t canon_pack_words<T>(const CanonGeom&, const T*, uint32_t*, hipStream_t);                  \
+  template hipError_t canon_unpack_words<T>(const CanonGeom&, const uint32_t*, T*, hipStream_t);
+MI355_CANON_FOR(uint32_t)
+MI355_CANON_FOR(uint64_t)
+#undef MI355_CANON_FOR
+
+hipError_t canon_local_pass(const CanonGeom& g, const uint64_t* in, uint64_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_local<uint64_t>, dim3((g.n + 255) / 256), dim3(256), 0, s, g, in, out);
   return hipGetLastError();
 }
-hipError_t canon64_add_complement(uint32_t p, uint32_t n, uint32_t odd, uint64_t* dst, const uint64_t* canon, hipStream_t s) {
-  hipLaunchKernelGGL(k_add_complement<uint64_t>, dim3((n + 255) / 256), dim3(256), 0, s, geom64(p, n, odd), dst, canon);
+hipError_t canon_add_complement(const CanonGeom& g, uint64_t* dst, const uint64_t* canon, hipStream_t s) {
+  hipLaunchKernelGGL(k_add_complement<uint64_t>, dim3((g.n + 255) / 256), dim3(256), 0, s, g, dst, canon);
+  return hipGetLastError();
+}
+
+hipError_t canon_relax(const DevPlan& pl, uint32_t p, const uint32_t* in, uint32_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_relax, dim3(uint32_t((size_t(pl.n) / 2 + 255) / 256)), dim3(256), 0, s, CanonGeom::tile_major(pl, p), in, out);
+  return hipGetLastError();
+}
+hipError_t canon_scatter(const DevPlan& pl, uint32_t p, const uint32_t* nat, uint32_t* digits, hipStream_t s) {
+  hipLaunchKernelGGL(k_scatter, dim3((pl.n + 255) / 256), dim3(256), 0, s, CanonGeom::tile_major(pl, p), nat, digits);
+  return hipGetLastError();
+}
+hipError_t canon_set_small(const DevPlan& pl, uint32_t p, uint32_t* digits, uint32_t value, hipStream_t s) {
+  hipLaunchKernelGGL(k_set_small, dim3(1), dim3(64), 0, s, CanonGeom::tile_major(pl, p), digits, value);
   return hipGetLastError();
 }
 

@@ -12,9 +12,11 @@
 #include <string>
 #include <vector>
 
+#include "canon.hpp"
 #include "crt_arith.hpp"
 #include "crt_engine.hpp"
 #include "crt_kernels.hpp"
+#include "host_digits.hpp"
 
 namespace mi355 {
 namespace {
@@ -88,19 +90,10 @@ uint32_t crt_auto_radix(uint32_t p, size_t* words) {
   return n ? odd : 0;
 }
 
-// device-side canonical form for u64 digits in natural order (canon.hip)
-size_t canon64_scratch_bytes(uint32_t n);
-uint32_t* canon64_flags(uint32_t n, void* scratch);
-hipError_t canon64_launch(uint32_t p, uint32_t n, uint32_t odd, const uint64_t* digits, uint64_t* out, void* scratch, hipStream_t s);
-hipError_t canon64_compare(const uint64_t* a, const uint64_t* b, uint32_t n, uint32_t* diff_flag, hipStream_t s);
-hipError_t canon64_relax(uint32_t p, uint32_t n, uint32_t odd, const uint64_t* in, uint64_t* out, hipStream_t s);
-hipError_t canon64_add_complement(uint32_t p, uint32_t n, uint32_t odd, uint64_t* dst, const uint64_t* canon, hipStream_t s);
-hipError_t canon64_pack_words(uint32_t p, uint32_t n, uint32_t odd, const uint64_t* canon, uint32_t* words, hipStream_t s);
-hipError_t canon64_unpack_words(uint32_t p, uint32_t n, uint32_t odd, const uint32_t* words, uint64_t* digits, hipStream_t s);
-
 struct CrtEngine::Impl {
   crt::Geom g;
   crt::Grid gr;
+  CanonGeom cg{};                 // the digit layout as canon.hip sees it (natural order)
   crt::CrtKernels kernels{};      // chosen once from the grid, MI355_CRT_KERNELS and MI355_CRT_TUNE
   int device = 0;
   hipStream_t stream = nullptr;
@@ -148,7 +141,7 @@ struct CrtEngine::Impl {
   }
 };
 
-const char* CrtEngine::kernel_name(size_t k) {
+const char* CrtEngine::stage_name(size_t k) {
   static const char* names[kKernels] = {"k_front", "k_rows_fwd", "k_pointwise", "k_rows_inv", "k_back", "k_crt_carry"};
   return k < kKernels ? names[k] : "";
 }
@@ -229,16 +222,14 @@ CrtEngine::CrtEngine(uint32_t p, size_t reg_count, uint32_t odd, size_t n_forced
       upload(m >> 10, 1024, im.T.hi61, im.T.hi31);
     }
   }
-  im.width.resize(n);
-  uint64_t prev = 0;
-  for (size_t j = 0; j < n; ++j) { const uint64_t next = (uint64_t(p) * (j + 1) + n - 1) / n; im.width[j] = uint8_t(next - prev); prev = next; }
+  im.width = host_digits::digit_widths(p, n);
+  im.cg = CanonGeom::natural(p, uint32_t(n), odd);
   im.excess.assign(reg_count, 0);
   { const char* hc = std::getenv("MI355_HOST_CARRY"); im.host_carry = hc && hc[0] == '1'; }
 }
 CrtEngine::~CrtEngine() = default;
 
 size_t CrtEngine::size() const { return im_->g.n; }
-uint32_t CrtEngine::odd() const { return im_->g.odd; }
 uint32_t CrtEngine::exponent() const { return im_->g.p; }
 std::string CrtEngine::describe() const {
   const crt::Grid& gr = im_->gr;
@@ -309,10 +300,7 @@ void CrtEngine::launch_transform(size_t reg, int mode, size_t other, uint32_t a,
 
 size_t CrtEngine::reg_count() const { return im_->regs.size(); }
 
-void CrtEngine::check_digits(size_t reg, const char* what) const {
-  if (reg >= im_->regs.size()) throw std::runtime_error(std::string(what) + ": register index out of range");
-  if (im_->regs[reg].image) throw std::runtime_error(std::string(what) + ": register holds a multiplicand image, not a residue");
-}
+bool CrtEngine::holds_image(size_t reg) const { return im_->regs[reg].image; }
 
 // Headroom of the transform: the convolution sums stay below M61 M31 ~ 2^92 while log2(n) + 2 (w + excess) < 92 (the size rule is that
 // bound at excess 0).  A register that has been through digit-wise additions is relaxed first when it would not fit: one local carry
@@ -323,7 +311,7 @@ void CrtEngine::ensure_headroom(size_t reg) {
   if (e == 0) return;
   const double bits = std::log2(double(im.g.n)) + 2.0 * (double(im.g.q) + 1.0 + double(e));
   if (bits < 92.0 && e < 8) return;
-  chk(canon64_relax(im.g.p, im.g.n, im.gr.odd, im.regs[reg].x, im.scratch, im.stream), "relax");
+  chk(canon_local_pass(im.cg, im.regs[reg].x, im.scratch, im.stream), "relax");
   std::swap(im.regs[reg].x, im.scratch);
   im.excess[reg] = 0;
 }
@@ -333,19 +321,19 @@ uint64_t* CrtEngine::canon_digits(size_t reg, int slot) {
   Impl& im = *im_;
   chk(hipSetDevice(im.device), "hipSetDevice");
   if (!im.canon) {
-    const size_t sb = (canon64_scratch_bytes(im.g.n) + 255) & ~size_t(255);
+    const size_t sb = (canon_scratch_bytes<uint64_t>(im.cg) + 255) & ~size_t(255);
     im.canon = im.alloc<unsigned char>(sb + 2 * size_t(im.g.n) * 8);
     im.canon_out[0] = reinterpret_cast<uint64_t*>(static_cast<unsigned char*>(im.canon) + sb);
     im.canon_out[1] = im.canon_out[0] + im.g.n;
-    chk(hipMemsetAsync(canon64_flags(im.g.n, im.canon), 0, 16 * 4, im.stream), "memset");
+    chk(hipMemsetAsync(canon_flags<uint64_t>(im.cg, im.canon), 0, 16 * 4, im.stream), "memset");
   }
-  chk(canon64_launch(im.g.p, im.g.n, im.gr.odd, im.regs[reg].x, im.canon_out[slot], im.canon, im.stream), "canon");
+  chk(canon_launch(im.cg, im.regs[reg].x, im.canon_out[slot], im.canon, im.stream), "canon");
   return im.canon_out[slot];
 }
 // flags: [0] all ones, [1] a digit too wide for the 0/1 chain (fall back to the host carry), [2] compare differs; cleared for the next use
 bool CrtEngine::canon_flags_ok(uint32_t (&flags)[4]) {
   Impl& im = *im_;
-  uint32_t* df = canon64_flags(im.g.n, im.canon);
+  uint32_t* df = canon_flags<uint64_t>(im.cg, im.canon);
   chk(hipMemcpyAsync(flags, df, 16, hipMemcpyDeviceToHost, im.stream), "copy");
   chk(hipMemsetAsync(df, 0, 16 * 4, im.stream), "memset");
   chk(hipStreamSynchronize(im.stream), "sync");
@@ -353,8 +341,7 @@ bool CrtEngine::canon_flags_ok(uint32_t (&flags)[4]) {
 }
 
 void CrtEngine::square_mul(size_t reg, uint32_t a) {
-  check_digits(reg, "square_mul");
-  if (a == 0) throw std::runtime_error("square_mul: factor must be >= 1");
+  need_residue(reg, "square_mul"); need_factor(a, "square_mul");
   chk(hipSetDevice(im_->device), "hipSetDevice");
   ensure_headroom(reg);
   launch_transform(reg, 0, 0, a, false);
@@ -364,8 +351,7 @@ void CrtEngine::square_mul(size_t reg, uint32_t a) {
 // dst <- the transformed image of src (engine::set_multiplicand, engine.h:53); dst may be src
 void CrtEngine::set_multiplicand(size_t dst, size_t src) {
   Impl& im = *im_;
-  check_digits(src, "set_multiplicand");
-  if (dst >= im.regs.size()) throw std::runtime_error("set_multiplicand: register index out of range");
+  need_residue(src, "set_multiplicand"); need_register(dst, "set_multiplicand");
   chk(hipSetDevice(im.device), "hipSetDevice");
   Impl::Register& d = im.regs[dst];
   im.ensure_image(d);
@@ -377,9 +363,7 @@ void CrtEngine::set_multiplicand(size_t dst, size_t src) {
 // dst <- dst * src * a with src a multiplicand image (engine::mul, engine.h:60)
 void CrtEngine::mul(size_t dst, size_t src, uint32_t a) {
   Impl& im = *im_;
-  check_digits(dst, "mul");
-  if (src >= im.regs.size() || !im.regs[src].image) throw std::runtime_error("mul: the source register is not a multiplicand (call set_multiplicand first)");
-  if (a == 0) throw std::runtime_error("mul: factor must be >= 1");
+  need_residue(dst, "mul"); need_image(src, "mul"); need_factor(a, "mul");
   chk(hipSetDevice(im.device), "hipSetDevice");
   ensure_headroom(dst);
   launch_transform(dst, 2, src, a, false);
@@ -388,7 +372,7 @@ void CrtEngine::mul(size_t dst, size_t src, uint32_t a) {
 
 void CrtEngine::copy(size_t dst, size_t src) {
   Impl& im = *im_;
-  if (dst >= im.regs.size() || src >= im.regs.size()) throw std::runtime_error("copy: register index out of range");
+  need_register(dst, "copy"); need_register(src, "copy");
   if (dst == src) return;
   chk(hipSetDevice(im.device), "hipSetDevice");
   Impl::Register& d = im.regs[dst]; const Impl::Register& r = im.regs[src];
@@ -406,7 +390,7 @@ void CrtEngine::copy(size_t dst, size_t src) {
 // dst <- dst + src, digit-wise on weakly carried digits (engine::add, engine.h:64)
 void CrtEngine::add(size_t dst, size_t src) {
   Impl& im = *im_;
-  check_digits(dst, "add"); check_digits(src, "add");
+  need_residue(dst, "add"); need_residue(src, "add");
   chk(hipSetDevice(im.device), "hipSetDevice");
   crt::launch_add_digits(im.regs[dst].x, im.regs[src].x, im.g.n, im.stream);
   im.excess[dst] = std::max(im.excess[dst], im.excess[src]) + 1;
@@ -420,7 +404,7 @@ const uint64_t* CrtEngine::canonical_on_device(size_t src) {
   uint32_t flags[4];
   if (canon_flags_ok(flags) && !im.host_carry) return c;
   std::vector<uint64_t> d(im.g.n);
-  get_digits_host(src, d.data(), im.g.n);
+  get_digits_host(src, d.data());
   chk(hipMemcpy(im.canon_out[1], d.data(), size_t(im.g.n) * 8, hipMemcpyHostToDevice), "copy");
   return im.canon_out[1];
 }
@@ -428,9 +412,9 @@ const uint64_t* CrtEngine::canonical_on_device(size_t src) {
 // dst <- dst - src = dst + (2^p - 1 - src): the digit-wise complement of the canonical form of src, taken on the device
 void CrtEngine::sub_reg(size_t dst, size_t src) {
   Impl& im = *im_;
-  check_digits(dst, "sub_reg"); check_digits(src, "sub_reg");
+  need_residue(dst, "sub_reg"); need_residue(src, "sub_reg");
   const uint64_t* c = canonical_on_device(src);
-  chk(canon64_add_complement(im.g.p, im.g.n, im.gr.odd, im.regs[dst].x, c, im.stream), "sub_reg");
+  chk(canon_add_complement(im.cg, im.regs[dst].x, c, im.stream), "sub_reg");
   im.excess[dst] = im.excess[dst] + 1;
   if (im.excess[dst] >= 8) ensure_headroom(dst);
 }
@@ -438,7 +422,7 @@ void CrtEngine::sub_reg(size_t dst, size_t src) {
 // sum -> sum_out (and sum_copy), difference -> diff_out (and diff_copy); -1: not wanted.  a and b may be among the outputs.
 void CrtEngine::addsub(long sum_out, long sum_copy, long diff_out, long diff_copy, size_t a, size_t b) {
   Impl& im = *im_;
-  check_digits(a, "addsub"); check_digits(b, "addsub");
+  need_residue(a, "addsub"); need_residue(b, "addsub");
   const long outs[4] = {sum_out, sum_copy, diff_out, diff_copy};
   for (int i = 0; i < 4; ++i) {
     if (outs[i] >= long(im.regs.size())) throw std::runtime_error("addsub: register index out of range");
@@ -452,7 +436,7 @@ void CrtEngine::addsub(long sum_out, long sum_copy, long diff_out, long diff_cop
   if (diff_out >= 0) {
     const uint64_t* c = canonical_on_device(b);
     chk(hipMemcpyAsync(im.scratch, im.regs[a].x, bytes, hipMemcpyDeviceToDevice, im.stream), "copy");
-    chk(canon64_add_complement(im.g.p, im.g.n, im.gr.odd, im.scratch, c, im.stream), "addsub");
+    chk(canon_add_complement(im.cg, im.scratch, c, im.stream), "addsub");
   }
   if (sum_out >= 0) {
     if (size_t(sum_out) == b) {   // b + a
@@ -470,49 +454,10 @@ void CrtEngine::addsub(long sum_out, long sum_copy, long diff_out, long diff_cop
     if (diff_copy >= 0) { chk(hipMemcpyAsync(im.regs[diff_copy].x, im.scratch, bytes, hipMemcpyDeviceToDevice, im.stream), "copy"); im.regs[diff_copy].image = false; im.excess[diff_copy] = ea + 1; }
   }
 }
-void CrtEngine::mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t f) { mul(dst, mul_src, f); add(dst, add_src); }
-void CrtEngine::square_mul_copy(size_t src, size_t dst_copy, uint32_t f) { square_mul(src, f); copy(dst_copy, src); }
-void CrtEngine::mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t f) { mul(dst, src, f); copy(dst_copy, dst); }
-// a = a^h * b: set_multiplicand(tmp, a), left-to-right binary square_mul / mul over the bits of h below its top bit, set_multiplicand(b, b),
-// mul(a, b).  Checked before the first launch: a refused call leaves the registers as they were.
-void CrtEngine::exp_mul(size_t a, uint64_t h, size_t b, size_t tmp, bool square_b) {
-  check_digits(a, "exp_mul"); check_digits(b, "exp_mul");
-  if (tmp >= im_->regs.size()) throw std::runtime_error("exp_mul: register index out of range");
-  if (a == b || a == tmp || b == tmp) throw std::runtime_error("exp_mul: a, b and tmp must be three different registers");
-  if (square_b) square_mul(b, 1);
-  if (h == 0) copy(a, b);
-  set_multiplicand(tmp, a);
-  int top = 63;
-  while (top > 0 && !((h >> top) & 1)) --top;
-  for (int i = top - 1; i >= 0 && h != 0; --i) {
-    square_mul(a, 1);
-    if ((h >> i) & 1) mul(a, tmp, 1);
-  }
-  set_multiplicand(b, b);
-  if (h != 0) mul(a, b, 1);
-}
-
-// dst = dst (a + b): copy(tmp, dst); mul(dst, a); mul(tmp, b); add(dst, tmp).  Checked before the first launch.
-void CrtEngine::mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp) {
-  Impl& im = *im_;
-  check_digits(dst, "mul_sum");
-  if (src_a >= im.regs.size() || src_b >= im.regs.size() || tmp >= im.regs.size()) throw std::runtime_error("mul_sum: register index out of range");
-  if (!im.regs[src_a].image || !im.regs[src_b].image) throw std::runtime_error("mul_sum: src_a and src_b must be multiplicands (set_multiplicand)");
-  if (dst == tmp || tmp == src_a || tmp == src_b)
-    throw std::runtime_error("mul_sum: dst, tmp and the multiplicands must be different registers (src_a == src_b is allowed)");
-  copy(tmp, dst); mul(dst, src_a, 1); mul(tmp, src_b, 1); add(dst, tmp);
-}
-void CrtEngine::square_mul_bits(size_t reg, uint32_t factor, const uint8_t* bits, size_t nbits) {
-  check_digits(reg, "square_mul_bits");
-  if (factor == 0) throw std::runtime_error("square_mul_bits: factor must be >= 1");
-  if (nbits == 0) return;
-  if (!bits) throw std::runtime_error("square_mul_bits: null bit string");
-  for (size_t i = 0; i < nbits; ++i) square_mul(reg, ((bits[i >> 3] >> (7 - (i & 7))) & 1) ? factor : 1u);
-}
 
 void CrtEngine::set_u32(size_t reg, uint32_t a) {
   Impl& im = *im_;
-  if (reg >= im.regs.size()) throw std::runtime_error("set: register index out of range");
+  need_register(reg, "set");
   chk(hipSetDevice(im.device), "hipSetDevice");
   chk(hipMemsetAsync(im.regs[reg].x, 0, size_t(im.g.n) * 8, im.stream), "memset");
   if (a) crt::launch_set_small(im.g, im.regs[reg].x, a, im.stream);
@@ -520,14 +465,14 @@ void CrtEngine::set_u32(size_t reg, uint32_t a) {
 }
 void CrtEngine::sub_u32(size_t reg, uint32_t a) {
   Impl& im = *im_;
-  check_digits(reg, "sub");
+  need_residue(reg, "sub");
   chk(hipSetDevice(im.device), "hipSetDevice");
   if (a) crt::launch_sub_small(im.g, im.regs[reg].x, a, im.stream);
 }
 
-void CrtEngine::set_digits(size_t reg, const uint64_t* d, size_t count) {
+void CrtEngine::set_raw_digits(size_t reg, const uint64_t* d, size_t count) {
   Impl& im = *im_;
-  if (reg >= im.regs.size()) throw std::runtime_error("set_digits: register index out of range");
+  need_register(reg, "set_digits");
   if (count != im.g.n) throw std::runtime_error("set_digits: wrong digit count");
   for (size_t j = 0; j < count; ++j) if (d[j] >> 62) throw std::runtime_error("set_digits: digit out of range");
   chk(hipSetDevice(im.device), "hipSetDevice");
@@ -542,9 +487,9 @@ void CrtEngine::set_digits(size_t reg, const uint64_t* d, size_t count) {
 // digits as they are on the device (weakly carried) or canonical: strong carry with wrap-around, 2^p - 1 stays all ones.
 // The canonical form is made on the device (canon.hip); MI355_HOST_CARRY=1 or a device chain that reports an over-wide digit use the
 // host loop below (the reference's way: engine_gpu.h:1534-1561).
-void CrtEngine::get_digits(size_t reg, uint64_t* d, size_t count, bool canonical) {
+void CrtEngine::get_raw_digits(size_t reg, uint64_t* d, size_t count, bool canonical) {
   Impl& im = *im_;
-  check_digits(reg, "get_digits");
+  need_residue(reg, "get_digits");
   if (count != im.g.n) throw std::runtime_error("get_digits: wrong digit count");
   if (!canonical) {
     sync();
@@ -556,37 +501,28 @@ void CrtEngine::get_digits(size_t reg, uint64_t* d, size_t count, bool canonical
     chk(hipMemcpyAsync(d, c, count * 8, hipMemcpyDeviceToHost, im.stream), "copy");
     uint32_t flags[4];
     if (canon_flags_ok(flags)) {
-      if (flags[0]) for (size_t j = 0; j < count; ++j) d[j] = (uint64_t(1) << im.width[j]) - 1;
+      if (flags[0]) for (size_t j = 0; j < count; ++j) d[j] = host_digits::ones(im.width[j]);
       return;
     }
   }
-  get_digits_host(reg, d, count);
+  get_digits_host(reg, d);
 }
-void CrtEngine::get_digits_host(size_t reg, uint64_t* d, size_t count) {
+void CrtEngine::get_digits_host(size_t reg, uint64_t* d) {
   Impl& im = *im_;
   sync();
-  chk(hipMemcpy(d, im.regs[reg].x, count * 8, hipMemcpyDeviceToHost), "copy");
-  uint64_t carry = 0;
-  for (int lap = 0; lap < 4; ++lap) {
-    for (size_t j = 0; j < count; ++j) {
-      const uint64_t v = d[j] + carry;
-      d[j] = v & ((uint64_t(1) << im.width[j]) - 1);
-      carry = v >> im.width[j];
-      if (lap && !carry) break;
-    }
-    if (!carry) break;
-  }
+  chk(hipMemcpy(d, im.regs[reg].x, size_t(im.g.n) * 8, hipMemcpyDeviceToHost), "copy");
+  host_digits::strong_carry(d, im.width);
 }
 
-void CrtEngine::get_digits_encoded(size_t reg, uint64_t* d, size_t count) {
+void CrtEngine::get_digits(size_t reg, uint64_t* d, size_t count) {
   Impl& im = *im_;
-  get_digits(reg, d, count, true);
+  get_raw_digits(reg, d, count, true);
   for (size_t j = 0; j < count; ++j) {
     if (im.width[j] > 32) throw std::runtime_error("get_digits: this transform size has words of more than 32 bits, which the value | width << 32 encoding cannot hold (use get_words)");
     d[j] |= uint64_t(im.width[j]) << 32;
   }
 }
-void CrtEngine::set_digits_encoded(size_t reg, const uint64_t* d, size_t count) {
+void CrtEngine::set_digits(size_t reg, const uint64_t* d, size_t count) {
   Impl& im = *im_;
   if (count != im.g.n) throw std::runtime_error("set_digits: wrong digit count");
   std::vector<uint64_t> v(count);
@@ -594,79 +530,55 @@ void CrtEngine::set_digits_encoded(size_t reg, const uint64_t* d, size_t count) 
     if ((d[j] >> 32) != im.width[j]) throw std::runtime_error("set_digits: digit width mismatch");
     v[j] = d[j] & 0xffffffffull;
   }
-  set_digits(reg, v.data(), count);
+  set_raw_digits(reg, v.data(), count);
 }
 
 // canonical little-endian 32-bit words of the residue, 2^p - 1 -> 0 (what the plugin ABI exchanges: EngineApi.cpp:210-218).  Packed on the
 // device from the canonical digits (canon.hip k_pack_words, which sees 2^p - 1 as zeros): ceil(p / 32) words cross PCIe, not n u64 digits.
 void CrtEngine::get_words(size_t reg, uint32_t* w, size_t count) {
   Impl& im = *im_;
-  const size_t need = (size_t(im.g.p) + 31) / 32;
+  const size_t need = word_count();
   if (count < need) throw std::runtime_error("get_words: buffer too small");
-  check_digits(reg, "get_words");
+  need_residue(reg, "get_words");
   if (!im.host_carry) {
     const uint64_t* c = canon_digits(reg, 0);
     uint32_t* dw = static_cast<uint32_t*>(im.canon);   // the pipeline's first work array (8 n bytes >= the words) is free once the digits are out
-    chk(canon64_pack_words(im.g.p, im.g.n, im.gr.odd, c, dw, im.stream), "pack");
+    chk(canon_pack_words(im.cg, c, dw, im.stream), "pack");
     chk(hipMemcpyAsync(w, dw, need * 4, hipMemcpyDeviceToHost, im.stream), "copy");
     uint32_t flags[4];
     if (canon_flags_ok(flags)) { std::memset(w + need, 0, (count - need) * 4); return; }
   }
-  get_words_host(reg, w, count);
-}
-void CrtEngine::get_words_host(size_t reg, uint32_t* w, size_t count) {
-  Impl& im = *im_;
-  const size_t n = im.g.n;
-  std::vector<uint64_t> d(n);
-  get_digits_host(reg, d.data(), n);
-  bool ones = true;
-  for (size_t j = 0; j < n && ones; ++j) ones = d[j] == ((uint64_t(1) << im.width[j]) - 1);
-  std::memset(w, 0, count * 4);
-  if (ones) return;
-  size_t bit = 0;
-  for (size_t j = 0; j < n; ++j) {
-    const size_t wi = bit >> 5, sh = bit & 31;
-    const unsigned __int128 v = (unsigned __int128)d[j] << sh;
-    w[wi] |= uint32_t(v);
-    if (wi + 1 < count) w[wi + 1] |= uint32_t(v >> 32);
-    if (wi + 2 < count) w[wi + 2] |= uint32_t(v >> 64);
-    bit += im.width[j];
-  }
+  std::vector<uint64_t> d(im.g.n);
+  get_digits_host(reg, d.data());
+  host_digits::pack_words(d.data(), im.width, w, count);
 }
 // reg <- the value of `count` little-endian 32-bit words (< 2^p; bits beyond p must be zero): the words go up and are cut into digits on the
 // device (canon.hip k_unpack_words); MI355_HOST_CARRY=1 cuts them on the host
 void CrtEngine::set_words(size_t reg, const uint32_t* w, size_t count) {
   Impl& im = *im_;
-  const size_t n = im.g.n, need = (size_t(im.g.p) + 31) / 32;
+  const size_t n = im.g.n, need = word_count();
   if (count > need) for (size_t k = need; k < count; ++k) if (w[k]) throw std::runtime_error("set_words: value does not fit 2^p");
   if (count >= need && (im.g.p & 31) && (w[need - 1] >> (im.g.p & 31))) throw std::runtime_error("set_words: value does not fit 2^p");
   if (!im.host_carry) {
-    if (reg >= im.regs.size()) throw std::runtime_error("set_words: register index out of range");
+    need_register(reg, "set_words");
     chk(hipSetDevice(im.device), "hipSetDevice");
     uint32_t* dw = reinterpret_cast<uint32_t*>(im.scratch);   // 8 n bytes: room for the words of every admissible size
     if (count < need) chk(hipMemsetAsync(dw, 0, need * 4, im.stream), "memset");
     chk(hipMemcpyAsync(dw, w, std::min(count, need) * 4, hipMemcpyHostToDevice, im.stream), "copy");
-    chk(canon64_unpack_words(im.g.p, im.g.n, im.gr.odd, dw, im.regs[reg].x, im.stream), "unpack");
+    chk(canon_unpack_words(im.cg, dw, im.regs[reg].x, im.stream), "unpack");
     chk(hipStreamSynchronize(im.stream), "sync");
     im.regs[reg].image = false;
     im.excess[reg] = 0;
     return;
   }
-  std::vector<uint64_t> d(n, 0);
-  size_t bit = 0;
-  auto word = [&](size_t k) -> uint64_t { return k < count ? w[k] : 0; };
-  for (size_t j = 0; j < n; ++j) {
-    const size_t wi = bit >> 5, sh = bit & 31;
-    const unsigned __int128 v = ((unsigned __int128)word(wi) | ((unsigned __int128)word(wi + 1) << 32) | ((unsigned __int128)word(wi + 2) << 64)) >> sh;
-    d[j] = uint64_t(v) & ((uint64_t(1) << im.width[j]) - 1);
-    bit += im.width[j];
-  }
-  set_digits(reg, d.data(), n);
+  std::vector<uint64_t> d(n);
+  host_digits::unpack_words(w, count, im.width, d.data());
+  set_raw_digits(reg, d.data(), n);
 }
 // the low 64 bits of the canonical residue: canonical form on the device, the first digits cross PCIe
 uint64_t CrtEngine::res64(size_t reg) {
   Impl& im = *im_;
-  check_digits(reg, "res64");
+  need_residue(reg, "res64");
   if (!im.host_carry) {
     const uint64_t* c = canon_digits(reg, 0);
     const size_t have = std::min<size_t>(im.g.n, 8);     // widths are at least 15 bits here (constructor): 8 digits hold more than 64 bits
@@ -675,13 +587,10 @@ uint64_t CrtEngine::res64(size_t reg) {
     uint32_t flags[4];
     if (canon_flags_ok(flags)) {
       if (flags[0]) return 0;                             // 2^p - 1 = 0
-      unsigned __int128 r = 0; unsigned sh = 0;
-      for (size_t k = 0; k < have && sh < 64; ++k) { r |= (unsigned __int128)head[k] << sh; sh += im.width[k]; }
-      if (size_t(im.g.p) < 64) r &= (((unsigned __int128)1) << im.g.p) - 1;
-      return uint64_t(r);
+      return host_digits::res64_of_head(head, im.width, have);
     }
   }
-  std::vector<uint32_t> w((size_t(im.g.p) + 31) / 32 + 2, 0);
+  std::vector<uint32_t> w(word_count() + 2, 0);
   get_words(reg, w.data(), w.size());
   return uint64_t(w[0]) | (uint64_t(w[1]) << 32);
 }
@@ -689,24 +598,21 @@ uint64_t CrtEngine::res64(size_t reg) {
 // (the reference reads both registers back: engine.h:148-157)
 bool CrtEngine::equal(size_t a, size_t b) {
   Impl& im = *im_;
-  check_digits(a, "is_equal"); check_digits(b, "is_equal");
+  need_residue(a, "is_equal"); need_residue(b, "is_equal");
   if (!im.host_carry) {
     const uint64_t* ca = canon_digits(a, 0);
     const uint64_t* cb = canon_digits(b, 1);
-    chk(canon64_compare(ca, cb, im.g.n, canon64_flags(im.g.n, im.canon) + 2, im.stream), "compare");
+    chk(canon_compare(ca, cb, im.g.n, canon_flags<uint64_t>(im.cg, im.canon) + 2, im.stream), "compare");
     uint32_t flags[4];
     if (canon_flags_ok(flags)) return flags[2] == 0;      // (2^p - 1 is written as 0 by both, so 0 == 2^p - 1 holds)
   }
-  const size_t need = (size_t(im.g.p) + 31) / 32;
-  std::vector<uint32_t> wa(need), wb(need);
-  get_words(a, wa.data(), need); get_words(b, wb.data(), need);
-  return wa == wb;
+  return equal_words(a, b);
 }
 
 size_t CrtEngine::register_data_size() const { return size_t(im_->g.n) * 12 + 8; }
 void CrtEngine::get_data(size_t src, void* data, size_t size) {
   Impl& im = *im_;
-  if (src >= im.regs.size()) throw std::runtime_error("get_data: register index out of range");
+  need_register(src, "get_data");
   if (size != register_data_size()) throw std::runtime_error("get_data: size mismatch");
   sync();
   unsigned char* out = static_cast<unsigned char*>(data);
@@ -720,7 +626,7 @@ void CrtEngine::get_data(size_t src, void* data, size_t size) {
 }
 void CrtEngine::set_data(size_t dst, const void* data, size_t size) {
   Impl& im = *im_;
-  if (dst >= im.regs.size()) throw std::runtime_error("set_data: register index out of range");
+  need_register(dst, "set_data");
   if (size != register_data_size()) throw std::runtime_error("set_data: size mismatch");
   const unsigned char* in = static_cast<const unsigned char*>(data);
   const size_t n = im.g.n, slots = size_t(im.gr.odd) * im.gr.h;
@@ -741,9 +647,10 @@ void CrtEngine::set_data(size_t dst, const void* data, size_t size) {
   r.image = tag == 1;
 }
 
-void CrtEngine::time_square_mul(size_t reg, uint32_t a, size_t iters, double* total_ms, double* kernel_ms, size_t kernel_count) {
+void CrtEngine::time_square_mul(size_t reg, uint32_t a, uint32_t sub, size_t iters, double* total_ms, double* kernel_ms, size_t kernel_count) {
   Impl& im = *im_;
-  check_digits(reg, "time_square_mul");
+  if (sub) throw std::runtime_error("time_square_mul: no deferred subtraction on the crt family");
+  need_residue(reg, "time_square_mul");
   chk(hipSetDevice(im.device), "hipSetDevice");
   std::vector<double> acc(kKernels, 0.0);
   double total = 0;

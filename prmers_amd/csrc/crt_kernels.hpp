@@ -52,4 +52,9 @@ void launch_set_small(const Geom& g, uint64_t* x, uint32_t a, hipStream_t s);
 void launch_sub_small(const Geom& g, uint64_t* x, uint32_t a, hipStream_t s);
 
 }  // namespace crt
+
+// mi355_crt_carry: the carry sweep on its own, on caller-supplied residues of both fields (tests/test_gpu_crt_carry.py)
+void crt_carry_host(uint32_t p, size_t n, uint32_t odd, uint32_t a, const uint64_t* in61, const uint32_t* in31, uint64_t* digits_out,
+                    uint64_t* residual_out, int device, double* kernel_ms);
+
 }  // namespace mi355

@@ -5,6 +5,8 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "host_digits.hpp"
+
 namespace mi355 {
 
 #define HIPCHK(expr)                                                                              \
@@ -157,13 +159,8 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
     dp_.F0f = f0_; dp_.F0i = f0_ + nt; dp_.FBf = f0_ + 2 * nt; dp_.FBi = f0_ + 2 * nt + pl_.M2;
   }
 
-  // digit widths in natural order (ibdwt.h:127-132), s_j = p*j mod n kept incrementally
-  width_.resize(pl_.n);
-  uint64_t s = 0;
-  for (size_t j = 0; j < pl_.n; ++j) {
-    width_[j] = uint8_t(pl_.width_of_s(s));
-    s += pl_.t; if (s >= pl_.n) s -= pl_.n;
-  }
+  width_ = host_digits::digit_widths(p, pl_.n);   // natural order
+  cg_ = CanonGeom::tile_major(dp_, p);
   { const char* hc = std::getenv("MI355_HOST_CARRY"); host_carry_ = hc && hc[0] == '1'; }
   HIPCHK(hipStreamSynchronize(stream_));
   if (verbose_) std::fprintf(stderr, "[mi355] p=%u %s regs=%zu device=%d\n", p, pl_.describe().c_str(), nregs_, device_);
@@ -180,14 +177,6 @@ Engine::~Engine() {
   if (split_) (void)hipFree(split_);
   if (canon_) (void)hipFree(canon_);
   if (stream_) (void)hipStreamDestroy(stream_);
-}
-
-void Engine::check_reg(size_t r) const {
-  if (r >= nregs_) throw std::runtime_error("register index out of range");
-}
-void Engine::need_digits(size_t r, const char* op) const {
-  check_reg(r);
-  if (kind_[r] == kImage) throw std::runtime_error(std::string(op) + ": register holds a multiplicand image, not a residue");
 }
 
 void Engine::sync() {
@@ -258,22 +247,22 @@ void Engine::write_values(size_t dst, const std::vector<uint32_t>& natural) {
 
 // canonical digits of register r (strong carry with wrap-around, 2^p - 1 -> 0) in natural order, on the device
 uint32_t* Engine::canon_digits(size_t r, int slot) {
-  need_digits(r, "get");
+  need_residue(r, "get");
   HIPCHK(hipSetDevice(device_));
-  const size_t sw = canon_scratch_words(dp_);
+  const size_t sw = canon_scratch_bytes<uint32_t>(cg_) / 4;
   if (!canon_) {
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&canon_), (sw + 2 * pl_.n) * 4));
-    HIPCHK(hipMemsetAsync(canon_flags(dp_, canon_), 0, 16 * 4, stream_));
+    HIPCHK(hipMemsetAsync(canon_flags<uint32_t>(cg_, canon_), 0, 16 * 4, stream_));
   }
   normalize(r);
   uint32_t* out = canon_ + sw + size_t(slot) * pl_.n;
-  HIPCHK(canon_launch(dp_, pl_.p, digits(r), out, canon_, stream_));
+  HIPCHK(canon_launch(cg_, digits(r), out, canon_, stream_));
   return out;
 }
 
 // flags: [0] all ones, [1] chain too wide (fall back), [2] compare differs; clears the sticky ones for the next use
 bool Engine::canon_flags_ok(uint32_t (&flags)[4]) {
-  uint32_t* df = canon_flags(dp_, canon_);
+  uint32_t* df = canon_flags<uint32_t>(cg_, canon_);
   HIPCHK(hipMemcpyAsync(flags, df, 16, hipMemcpyDeviceToHost, stream_));
   HIPCHK(hipMemsetAsync(df, 0, 16 * 4, stream_));
   HIPCHK(hipStreamSynchronize(stream_));
@@ -289,14 +278,14 @@ void Engine::read_values(size_t src, std::vector<uint64_t>& v) {
   if (!canon_flags_ok(flags)) { read_values_host(src, v); return; }
   v.resize(pl_.n);
   if (flags[0]) {   // 2^p - 1: the reference's get() leaves the digits all ones (engine.h:188-196 maps them to 0 later)
-    for (size_t k = 0; k < pl_.n; ++k) v[k] = (uint64_t(1) << width_[k]) - 1;
+    for (size_t k = 0; k < pl_.n; ++k) v[k] = host_digits::ones(width_[k]);
   } else {
     for (size_t k = 0; k < pl_.n; ++k) v[k] = stage_[k];
   }
 }
 
 void Engine::read_values_host(size_t src, std::vector<uint64_t>& v) {
-  need_digits(src, "get");
+  need_residue(src, "get");
   stage_.resize(pl_.n);
   HIPCHK(hipSetDevice(device_));
   normalize(src);
@@ -310,25 +299,11 @@ void Engine::read_values_host(size_t src, std::vector<uint64_t>& v) {
     v[2 * i] = stage_[s];
     v[2 * i + 1] = stage_[s + 1];
   }
-  // strong carry with wrap-around (engine_gpu.h:1543-1557)
-  uint64_t c = 0;
-  for (size_t k = 0; k < pl_.n; ++k) {
-    const uint64_t t = v[k] + c;
-    v[k] = t & ((uint64_t(1) << width_[k]) - 1);
-    c = t >> width_[k];
-  }
-  while (c != 0) {
-    for (size_t k = 0; k < pl_.n; ++k) {
-      const uint64_t t = v[k] + c;
-      v[k] = t & ((uint64_t(1) << width_[k]) - 1);
-      c = t >> width_[k];
-      if (c == 0) break;
-    }
-  }
+  host_digits::strong_carry(v.data(), width_);
 }
 
 void Engine::set_u32(size_t dst, uint32_t value) {
-  check_reg(dst);
+  need_register(dst, "set");
   HIPCHK(hipSetDevice(device_));
   HIPCHK(hipMemsetAsync(digits(dst), 0, pl_.n * 4, stream_));
   // spread the constant over the first digits (the reference stores it whole in digit 0,
@@ -339,7 +314,7 @@ void Engine::set_u32(size_t dst, uint32_t value) {
 }
 
 void Engine::set_digits(size_t dst, const uint64_t* d, size_t count) {
-  check_reg(dst);
+  need_register(dst, "set_digits");
   if (count != pl_.n) throw std::runtime_error("set_digits: count must equal the transform size");
   std::vector<uint32_t> nat(pl_.n);
   for (size_t k = 0; k < pl_.n; ++k) nat[k] = uint32_t(d[k]);
@@ -365,70 +340,37 @@ uint64_t Engine::res64(size_t src) {
     uint32_t head[16], flags[4];
     HIPCHK(hipMemcpyAsync(head, d, have * 4, hipMemcpyDeviceToHost, stream_));
     if (!canon_flags_ok(flags)) { read_values_host(src, v); have = pl_.n; }
-    else { v.resize(have); for (size_t k = 0; k < have; ++k) v[k] = flags[0] ? (uint64_t(1) << width_[k]) - 1 : head[k]; }
+    else { v.resize(have); for (size_t k = 0; k < have; ++k) v[k] = flags[0] ? host_digits::ones(width_[k]) : head[k]; }
   }
-  uint64_t r64 = 0; unsigned s = 0;   // engine.h:257-269
-  for (size_t k = 0; k < have; ++k) {
-    r64 += v[k] << s;
-    s += width_[k];
-    if (s >= 64) break;
-  }
-  return r64;
+  return host_digits::res64_of_head(v.data(), width_, have);
 }
 
 // The words are packed on the device from the canonical digits (canon.hip k_pack_words; 2^p - 1 comes out as 0 there): word_count() words
-// cross PCIe instead of the n digits.  MI355_HOST_CARRY=1, or a canonical form that falls back, take the host loop (get_words_host).
+// cross PCIe instead of the n digits.  MI355_HOST_CARRY=1, or a canonical form that falls back, take the host loop (host_digits.hpp).
 void Engine::get_words(size_t src, uint32_t* w, size_t count) {
   if (count != word_count()) throw std::runtime_error("get_words: count must equal word_count()");
   if (!host_carry_) {
     uint32_t* d = canon_digits(src, 0);
     uint32_t* dw = canon_;   // the pipeline's first work array (n words >= word_count(): widths are below 32) is free once the digits are out
-    HIPCHK(canon_pack_words(dp_, pl_.p, d, dw, stream_));
+    HIPCHK(canon_pack_words(cg_, d, dw, stream_));
     HIPCHK(hipMemcpyAsync(w, dw, count * 4, hipMemcpyDeviceToHost, stream_));
     uint32_t flags[4];
     if (canon_flags_ok(flags)) return;
   }
-  get_words_host(src, w, count);
-}
-
-void Engine::get_words_host(size_t src, uint32_t* w, size_t count) {
   std::vector<uint64_t> v;
   read_values_host(src, v);
-  bool all_ones = true;   // 2^p - 1 == 0 (engine.h:188-196)
-  for (size_t k = 0; k < pl_.n && all_ones; ++k) all_ones = (v[k] == (uint64_t(1) << width_[k]) - 1);
-  std::memset(w, 0, count * 4);
-  if (all_ones) return;
-  size_t bit = 0;
-  for (size_t k = 0; k < pl_.n; ++k) {
-    const size_t i = bit / 32, s = bit % 32;
-    const uint64_t x = v[k] << s;
-    w[i] |= uint32_t(x);
-    if ((x >> 32) && i + 1 < count) w[i + 1] |= uint32_t(x >> 32);
-    bit += width_[k];
-  }
+  host_digits::pack_words(v.data(), width_, w, count);
 }
 
 void Engine::set_words(size_t dst, const uint32_t* w, size_t count) {
-  check_reg(dst);
+  need_register(dst, "set_words");
   if (count != word_count()) throw std::runtime_error("set_words: count must equal word_count()");
   // bits at and above p are folded back (2^p = 1), so any count-word value is accepted; the fold runs on the host, before the upload,
   // and only for a value that has such bits
-  const unsigned top = pl_.p % 32;
   std::vector<uint32_t> src;
-  if (host_carry_ || (top && (w[count - 1] >> top))) {
+  if (host_carry_ || ((pl_.p % 32) && (w[count - 1] >> (pl_.p % 32)))) {
     src.assign(w, w + count);
-    src.push_back(0);
-    uint64_t fold = 0;
-    if (top) { fold = src[count - 1] >> top; src[count - 1] &= (1u << top) - 1; }
-    for (size_t i = 0; fold && i < count; ++i) {  // add the folded bits at bit 0
-      const uint64_t t = uint64_t(src[i]) + (fold & 0xffffffffu);
-      src[i] = uint32_t(t);
-      fold = (fold >> 32) + (t >> 32);
-    }
-    if (top && (src[count - 1] >> top)) {  // the addition rippled past bit p once more
-      src[count - 1] &= (1u << top) - 1;
-      for (size_t i = 0; i < count; ++i) { if (++src[i] != 0) break; }
-    }
+    host_digits::fold_words_mod_mp(src.data(), count, pl_.p);
     w = src.data();
   }
   if (!host_carry_) {
@@ -436,22 +378,15 @@ void Engine::set_words(size_t dst, const uint32_t* w, size_t count) {
     HIPCHK(hipSetDevice(device_));
     uint32_t* dw = reinterpret_cast<uint32_t*>(work());
     HIPCHK(hipMemcpyAsync(dw, w, count * 4, hipMemcpyHostToDevice, stream_));
-    HIPCHK(canon_unpack_words(dp_, pl_.p, dw, digits(dst), stream_));
+    HIPCHK(canon_unpack_words(cg_, dw, digits(dst), stream_));
     HIPCHK(hipStreamSynchronize(stream_));
     kind_[dst] = kDigits;
     pending_carry_[dst] = 0;
     return;
   }
-  std::vector<uint32_t> nat(pl_.n);
-  size_t bit = 0;
-  for (size_t k = 0; k < pl_.n; ++k) {   // engine.h:206-232
-    const size_t i = bit / 32, s = bit % 32;
-    uint64_t u = src[i] >> s;
-    if (s != 0) u |= uint64_t(src[i + 1]) << (32 - s);
-    nat[k] = uint32_t(u & ((uint64_t(1) << width_[k]) - 1));
-    bit += width_[k];
-  }
-  write_values(dst, nat);
+  std::vector<uint64_t> v(pl_.n);
+  host_digits::unpack_words(w, count, width_, v.data());
+  write_values(dst, std::vector<uint32_t>(v.begin(), v.end()));
 }
 
 bool Engine::equal(size_t lhs, size_t rhs) {
@@ -460,26 +395,17 @@ bool Engine::equal(size_t lhs, size_t rhs) {
     // registers back and carries them on the host: engine.h:148-157 via engine_gpu.h:1534-1561)
     uint32_t* a = canon_digits(lhs, 0);
     uint32_t* b = canon_digits(rhs, 1);
-    HIPCHK(canon_compare(a, b, uint32_t(pl_.n), canon_flags(dp_, canon_) + 2, stream_));
+    HIPCHK(canon_compare(a, b, uint32_t(pl_.n), canon_flags<uint32_t>(cg_, canon_) + 2, stream_));
     uint32_t flags[4];
     if (canon_flags_ok(flags)) return flags[2] == 0;
   }
-  std::vector<uint64_t> a, b;
-  read_values_host(lhs, a);
-  read_values_host(rhs, b);
-  auto all_ones = [&](const std::vector<uint64_t>& v) {
-    for (size_t k = 0; k < pl_.n; ++k) if (v[k] != (uint64_t(1) << width_[k]) - 1) return false;
-    return true;
-  };
-  if (all_ones(a)) std::fill(a.begin(), a.end(), 0);   // 2^p - 1 == 0
-  if (all_ones(b)) std::fill(b.begin(), b.end(), 0);
-  return a == b;
+  return equal_words(lhs, rhs);
 }
 
 // ---- register operations -------------------------------------------------------------------
 
 void Engine::copy(size_t dst, size_t src) {
-  check_reg(dst); check_reg(src);
+  need_register(dst, "copy"); need_register(src, "copy");
   if (dst == src) return;
   HIPCHK(hipSetDevice(device_));
   // the register is copied as it stands: digits with their pending run carries (no carry sweep),
@@ -503,23 +429,20 @@ void Engine::square_chain(size_t r, uint32_t a, hipEvent_t* ev) {
 }
 
 void Engine::square_mul(size_t r, uint32_t a) {
-  need_digits(r, "square_mul");
-  if (a == 0) throw std::runtime_error("square_mul: factor must be >= 1");
+  need_residue(r, "square_mul"); need_factor(a, "square_mul");
   HIPCHK(hipSetDevice(device_));
   square_chain(r, a, nullptr);
 }
 
 void Engine::square_mul_n(size_t r, uint32_t a, size_t count, uint32_t sub) {
-  need_digits(r, "square_mul_n");
-  if (a == 0) throw std::runtime_error("square_mul_n: factor must be >= 1");
+  need_residue(r, "square_mul_n"); need_factor(a, "square_mul_n");
   if (count == 0) return;
   HIPCHK(hipSetDevice(device_));
   for (size_t i = 0; i < count; ++i) { square_chain(r, a, nullptr); if (sub) sub_u32(r, sub); }
 }
 
-void Engine::prepare(size_t dst, size_t src) {
-  need_digits(src, "set_multiplicand");
-  check_reg(dst);
+void Engine::set_multiplicand(size_t dst, size_t src) {
+  need_residue(src, "set_multiplicand"); need_register(dst, "set_multiplicand");
   HIPCHK(hipSetDevice(device_));
   run_front(src);
   run_middle(work(), nullptr, image(dst), 2);
@@ -528,11 +451,7 @@ void Engine::prepare(size_t dst, size_t src) {
 }
 
 void Engine::mul(size_t dst, size_t src, uint32_t a) {
-  need_digits(dst, "mul");
-  check_reg(src);
-  if (kind_[src] != kImage) throw std::runtime_error("mul: src must be a multiplicand (set_multiplicand)");
-  if (dst == src) throw std::runtime_error("mul: dst and src must differ");
-  if (a == 0) throw std::runtime_error("mul: factor must be >= 1");
+  need_residue(dst, "mul"); need_image(src, "mul"); need_factor(a, "mul");
   HIPCHK(hipSetDevice(device_));
   run_front(dst);
   run_middle(work(), image(src), work(), 1);
@@ -542,7 +461,7 @@ void Engine::mul(size_t dst, size_t src, uint32_t a) {
 
 // r = r x a, run-wise (kernels.hip k_scale): the factors above the plan's fused bound follow the operation with factor 1
 void Engine::scale(size_t r, uint32_t a) {
-  need_digits(r, "scale");
+  need_residue(r, "scale");
   uint64_t* fresh = take_spare_cbuf();
   HIPCHK(launch_scale(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, digits(r), fresh, a, stream_));
   adopt_cbuf(r, fresh);
@@ -564,12 +483,12 @@ void Engine::adopt_cbuf(size_t r, uint64_t* fresh) {
 
 // sum -> s1 (and s2), difference -> d1 (and d2); -1: not wanted.  One run-wise sweep on pending-carry digits
 // (kernels.hip k_linear); the results leave their run carries pending for the next front sweep.
-void Engine::linear(long s1, long s2, long d1, long d2, size_t a, size_t b) {
+void Engine::addsub(long s1, long s2, long d1, long d2, size_t a, size_t b) {
   HIPCHK(hipSetDevice(device_));
-  need_digits(a, "add/sub"); need_digits(b, "add/sub");
+  need_residue(a, "addsub"); need_residue(b, "addsub");
   const long outs[4] = {s1, s2, d1, d2};
   for (int i = 0; i < 4; ++i)
-    if (outs[i] >= 0) { check_reg(size_t(outs[i])); for (int j = 0; j < i; ++j) if (outs[j] == outs[i]) throw std::runtime_error("addsub: output registers must differ"); }
+    if (outs[i] >= 0) { need_register(size_t(outs[i]), "addsub"); for (int j = 0; j < i; ++j) if (outs[j] == outs[i]) throw std::runtime_error("addsub: output registers must differ"); }
   LinArgs la;
   la.a = digits(a); la.ca = pending_carry_[a] ? cbuf(a) : nullptr;
   la.b = digits(b); la.cb = pending_carry_[b] ? cbuf(b) : nullptr;
@@ -590,30 +509,13 @@ void Engine::linear(long s1, long s2, long d1, long d2, size_t a, size_t b) {
     }
 }
 
-void Engine::add(size_t dst, size_t src) {
-  need_digits(dst, "add"); need_digits(src, "add");
-  linear(long(dst), -1, -1, -1, dst, src);
-}
-
-void Engine::sub_reg(size_t dst, size_t src) {
-  need_digits(dst, "sub_reg"); need_digits(src, "sub_reg");
-  linear(-1, -1, long(dst), -1, dst, src);
-}
-
-void Engine::addsub(size_t sum_out, size_t diff_out, size_t a, size_t b) {
-  need_digits(a, "addsub"); need_digits(b, "addsub");
-  linear(long(sum_out), -1, long(diff_out), -1, a, b);
-}
-
-void Engine::addsub_copy(size_t sum, size_t diff, size_t sum_copy, size_t diff_copy, size_t a, size_t b) {
-  need_digits(a, "addsub_copy"); need_digits(b, "addsub_copy");
-  linear(long(sum), long(sum_copy), long(diff), long(diff_copy), a, b);
-}
+void Engine::add(size_t dst, size_t src) { addsub(long(dst), -1, -1, -1, dst, src); }
+void Engine::sub_reg(size_t dst, size_t src) { addsub(-1, -1, long(dst), -1, dst, src); }
 
 // back sweep of work() into dst with the extras of kernels.hpp BackExt
 void Engine::back_ext(size_t dst, uint32_t a, long copy_to, long add_src) {
   BackExt x;
-  if (copy_to >= 0 && size_t(copy_to) != dst) { check_reg(size_t(copy_to)); x.digits2 = digits(size_t(copy_to)); x.cbuf2 = cbuf(size_t(copy_to)); }
+  if (copy_to >= 0 && size_t(copy_to) != dst) { x.digits2 = digits(size_t(copy_to)); x.cbuf2 = cbuf(size_t(copy_to)); }
   if (add_src >= 0) { x.add_digits = digits(size_t(add_src)); x.add_cbuf = pending_carry_[size_t(add_src)] ? cbuf(size_t(add_src)) : nullptr; }
   uint64_t* fresh = take_spare_cbuf();   // the addend may be dst itself: its pending carries are read while the new ones are written
   HIPCHK(cols_.back_ext(dp_, work(), digits(dst), fresh, a, x, stream_));
@@ -627,89 +529,56 @@ void Engine::back_ext(size_t dst, uint32_t a, long copy_to, long add_src) {
 }
 
 void Engine::square_mul_copy(size_t src, size_t dst_copy, uint32_t a) {
-  need_digits(src, "square_mul_copy"); check_reg(dst_copy);
-  if (a == 0) throw std::runtime_error("square_mul_copy: factor must be >= 1");
+  need_residue(src, "square_mul_copy"); need_register(dst_copy, "square_mul_copy"); need_factor(a, "square_mul_copy");
   HIPCHK(hipSetDevice(device_));
-  if (dst_copy == src || !kc_.fused_back() || a > pl_.a_fast) { square_mul(src, a); copy(dst_copy, src); return; }
+  if (dst_copy == src || !kc_.fused_back() || a > pl_.a_fast) { RegisterMachine::square_mul_copy(src, dst_copy, a); return; }
   run_front(src);
   run_middle(work(), nullptr, work(), 0);
   back_ext(src, a, long(dst_copy), -1);
 }
 
 void Engine::mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t a) {
-  need_digits(dst, "mul_copy"); check_reg(src); check_reg(dst_copy);
-  if (kind_[src] != kImage) throw std::runtime_error("mul_copy: src must be a multiplicand (set_multiplicand)");
-  if (dst == src || dst_copy == src) throw std::runtime_error("mul_copy: the multiplicand must differ from the outputs");
-  if (a == 0) throw std::runtime_error("mul_copy: factor must be >= 1");
+  need_residue(dst, "mul_copy"); need_image(src, "mul_copy"); need_register(dst_copy, "mul_copy"); need_factor(a, "mul_copy");
+  if (dst_copy == src) throw std::runtime_error("mul_copy: the multiplicand must differ from the outputs");
   HIPCHK(hipSetDevice(device_));
-  if (dst_copy == dst || !kc_.fused_back() || a > pl_.a_fast) { mul(dst, src, a); copy(dst_copy, dst); return; }
+  if (dst_copy == dst || !kc_.fused_back() || a > pl_.a_fast) { RegisterMachine::mul_copy(dst, src, dst_copy, a); return; }
   run_front(dst);
   run_middle(work(), image(src), work(), 1);
   back_ext(dst, a, long(dst_copy), -1);
 }
 
 void Engine::mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t a) {
-  need_digits(dst, "mul_add"); check_reg(mul_src); need_digits(add_src, "mul_add");
-  if (kind_[mul_src] != kImage) throw std::runtime_error("mul_add: mul_src must be a multiplicand (set_multiplicand)");
-  if (dst == mul_src) throw std::runtime_error("mul_add: dst and mul_src must differ");
-  if (a == 0) throw std::runtime_error("mul_add: factor must be >= 1");
+  need_residue(dst, "mul_add"); need_image(mul_src, "mul_add"); need_residue(add_src, "mul_add"); need_factor(a, "mul_add");
   HIPCHK(hipSetDevice(device_));
   if (!kc_.fused_back() || a > pl_.a_fast) {   // no fused sweep (split sweeps; factors above the fused bound): the base-class composition (engine.h:65-70)
     if (add_src == dst)
       throw std::runtime_error(!kc_.fused_back() ? "mul_add: add_src == dst needs the fused sweep, which this transform size does not have"
                                           : "mul_add: add_src == dst needs the fused sweep, which takes factors up to the plan's fused bound only (mi355_engine.h)");
-    mul(dst, mul_src, a); add(dst, add_src); return;
+    RegisterMachine::mul_add(dst, mul_src, add_src, a); return;
   }
   run_front(dst);   // reads digits(dst) (+ pending carries) and leaves them in place
   run_middle(work(), image(mul_src), work(), 1);
   back_ext(dst, a, -1, long(add_src));
 }
 
-// a = a^h * b: prepare(tmp, a), left-to-right binary square_mul / mul over the bits of h below its top bit, prepare(b, b), mul(a, b).
-// Everything is checked before the first launch, so a refused call leaves the registers as they were.
-void Engine::exp_mul(size_t a, uint64_t h, size_t b, size_t tmp, bool square_b) {
-  need_digits(a, "exp_mul"); need_digits(b, "exp_mul"); check_reg(tmp);
-  if (a == b || a == tmp || b == tmp) throw std::runtime_error("exp_mul: a, b and tmp must be three different registers");
-  if (square_b) square_mul(b, 1);
-  if (h == 0) copy(a, b);
-  prepare(tmp, a);
-  int top = 63;
-  while (top > 0 && !((h >> top) & 1)) --top;
-  for (int i = top - 1; i >= 0 && h != 0; --i) {
-    square_mul(a, 1);
-    if ((h >> i) & 1) mul(a, tmp, 1);
-  }
-  prepare(b, b);
-  if (h != 0) mul(a, b, 1);
-}
-
 // dst = dst (a + b).  Everything is checked before the first launch, so a refused call leaves the registers as they were.
 void Engine::mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp) {
-  need_digits(dst, "mul_sum"); check_reg(src_a); check_reg(src_b); check_reg(tmp);
-  if (kind_[src_a] != kImage || kind_[src_b] != kImage) throw std::runtime_error("mul_sum: src_a and src_b must be multiplicands (set_multiplicand)");
-  if (dst == tmp || dst == src_a || dst == src_b || tmp == src_a || tmp == src_b)
-    throw std::runtime_error("mul_sum: dst, tmp and the multiplicands must be different registers (src_a == src_b is allowed)");
+  if (!pl_.sum_fast) { RegisterMachine::mul_sum(dst, src_a, src_b, tmp); return; }   // the summed operand is beyond the plan's capacity (plan.hpp sum_product_ok)
+  check_mul_sum(dst, src_a, src_b, tmp);
   HIPCHK(hipSetDevice(device_));
-  if (!pl_.sum_fast) {   // the summed operand is beyond the plan's capacity (plan.hpp sum_product_ok): two products, exact for every plan
-    copy(tmp, dst); mul(dst, src_a, 1); mul(tmp, src_b, 1); add(dst, tmp);
-    return;
-  }
   run_front(dst);   // pending run carries (and a borrowed-through sub) of dst go in exactly as in mul
   run_middle(work(), image(src_a), work(), 3, image(src_b));
   run_back(dst, 1);
 }
 
 void Engine::square_mul_bits(size_t r, uint32_t factor, const uint8_t* bits, size_t nbits) {
-  need_digits(r, "square_mul_bits");
-  if (factor == 0) throw std::runtime_error("square_mul_bits: factor must be >= 1");
-  if (nbits == 0) return;
-  if (!bits) throw std::runtime_error("square_mul_bits: null bit string");
+  if (!check_square_mul_bits(r, factor, bits, nbits)) return;
   HIPCHK(hipSetDevice(device_));
-  for (size_t i = 0; i < nbits; ++i) square_chain(r, ((bits[i >> 3] >> (7 - (i & 7))) & 1) ? factor : 1u, nullptr);
+  for (size_t i = 0; i < nbits; ++i) square_chain(r, bit_of(bits, i) ? factor : 1u, nullptr);
 }
 
 void Engine::sub_u32(size_t r, uint32_t v) {
-  need_digits(r, "sub");
+  need_residue(r, "sub");
   if (v == 0) return;
   HIPCHK(hipSetDevice(device_));
   // (not deferred into the next front sweep as a field element: digit 0 plus its carry may be below v, and the sums of a sparse register
@@ -722,7 +591,7 @@ void Engine::sub_u32(size_t r, uint32_t v) {
 // ---- raw images -----------------------------------------------------------------------------
 
 void Engine::get_data(size_t src, void* data, size_t size) {
-  check_reg(src);
+  need_register(src, "get_data");
   if (size != register_data_size()) throw std::runtime_error("get_data: size mismatch");
   HIPCHK(hipSetDevice(device_));
   normalize(src);
@@ -733,7 +602,7 @@ void Engine::get_data(size_t src, void* data, size_t size) {
 }
 
 void Engine::set_data(size_t dst, const void* data, size_t size) {
-  check_reg(dst);
+  need_register(dst, "set_data");
   if (size != register_data_size()) throw std::runtime_error("set_data: size mismatch");
   uint64_t tag = 0;
   std::memcpy(&tag, static_cast<const unsigned char*>(data) + reg_bytes_, 8);
@@ -743,16 +612,6 @@ void Engine::set_data(size_t dst, const void* data, size_t size) {
   HIPCHK(hipMemcpy(slot_[dst], data, reg_bytes_, hipMemcpyHostToDevice));
   kind_[dst] = uint8_t(tag);
   pending_carry_[dst] = 0;
-}
-
-void Engine::get_checkpoint(void* data, size_t size) {
-  if (size != checkpoint_size()) throw std::runtime_error("get_checkpoint: size mismatch");
-  for (size_t r = 0; r < nregs_; ++r) get_data(r, static_cast<unsigned char*>(data) + r * register_data_size(), register_data_size());
-}
-
-void Engine::set_checkpoint(const void* data, size_t size) {
-  if (size != checkpoint_size()) throw std::runtime_error("set_checkpoint: size mismatch");
-  for (size_t r = 0; r < nregs_; ++r) set_data(r, static_cast<const unsigned char*>(data) + r * register_data_size(), register_data_size());
 }
 
 // ---- measurement ----------------------------------------------------------------------------
@@ -770,7 +629,7 @@ struct EventPool {   // HIP events owned for the length of one measurement
 };
 }  // namespace
 
-const char* Engine::kernel_name(size_t k) {
+const char* Engine::stage_name(size_t k) {
   static const char* names[kKernels] = {"k_front", "k_middle", "k_back", "k_carry_fix", "k_sub_small", "event_overhead"};
   return k < kKernels ? names[k] : "";
 }
@@ -780,7 +639,7 @@ const char* Engine::kernel_name(size_t k) {
 // (kernel_ms[5], measured as the spacing of back-to-back records on the same stream: without the subtraction every
 // interval carries one record, ~4-5 us, and a path that launches no kernel between two records shows it as a kernel).
 void Engine::time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, double* total_ms, double* kernel_ms, size_t kcount) {
-  need_digits(r, "time_square_mul");
+  need_residue(r, "time_square_mul");
   if (a == 0 || iters == 0) throw std::runtime_error("time_square_mul: factor and iters must be >= 1");
   HIPCHK(hipSetDevice(device_));
   EventPool pool;   // destroys its events on every way out (a HIPCHK that throws mid-batch used to leak them)

@@ -10,71 +10,66 @@
 #include <string>
 #include <vector>
 
+#include "canon.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
+#include "register_machine.hpp"
 
 namespace mi355 {
 
-class Engine {
+class Engine final : public RegisterMachine {
  public:
   Engine(uint32_t p, size_t reg_count, int device, bool verbose, const char* spec);
-  ~Engine();
+  ~Engine() override;
   Engine(const Engine&) = delete;
   Engine& operator=(const Engine&) = delete;
 
-  const Plan& plan() const { return pl_; }
-  std::string describe() const { return pl_.describe(); }
-  size_t n() const { return pl_.n; }
-  size_t word_count() const { return (size_t(pl_.p) + 31) / 32; }
-  size_t reg_count() const { return nregs_; }
+  uint32_t exponent() const override { return pl_.p; }
+  std::string describe() const override { return pl_.describe(); }
+  size_t size() const override { return pl_.n; }
+  size_t reg_count() const override { return nregs_; }
 
-  void sync();
-  void set_u32(size_t dst, uint32_t v);
-  void set_digits(size_t dst, const uint64_t* d, size_t count);
-  void get_digits(size_t src, uint64_t* d, size_t count);
-  void set_words(size_t dst, const uint32_t* w, size_t count);
-  void get_words(size_t src, uint32_t* w, size_t count);
-  uint64_t res64(size_t src);
-  void copy(size_t dst, size_t src);
-  void prepare(size_t dst, size_t src);
-  void square_mul(size_t r, uint32_t a);
-  // count x { square_mul(r, a); sub(r, sub) } -- the inner loop of a PRP (sub = 0) or Lucas-Lehmer (sub = 2) run between two checks,
-  // in one call: three launches per squaring (square_chain).
-  void square_mul_n(size_t r, uint32_t a, size_t count, uint32_t sub);
-  void mul(size_t dst, size_t src, uint32_t a);
-  void add(size_t dst, size_t src);
-  void sub_reg(size_t dst, size_t src);
-  void sub_u32(size_t r, uint32_t v);
-  bool equal(size_t lhs, size_t rhs);
-  // fused variants of the reference's engine (include/marin/engine.h:65-131; kernels/marin.cl:1856-2365): one sweep each
-  void addsub(size_t sum_out, size_t diff_out, size_t a, size_t b);
-  void addsub_copy(size_t sum, size_t diff, size_t sum_copy, size_t diff_copy, size_t a, size_t b);
-  void mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t a);
-  void square_mul_copy(size_t src, size_t dst_copy, uint32_t a);
-  void mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t a);
-  // a = a^h * b (b squared first when square_b): the fold of a PRP proof (PRPLL's expMul / expMul2).  b and tmp end as multiplicand images.
-  void exp_mul(size_t a, uint64_t h, size_t b, size_t tmp, bool square_b);
-  // dst = dst * (a + b): src_a, src_b multiplicand images (left intact, may be the same register), tmp scratch.  One product through the row
-  // sweep's mode 3 where the plan's capacity allows it (plan.hpp sum_product_ok), else copy(tmp, dst); mul(dst, a); mul(tmp, b); add(dst, tmp).
-  // The inner step of P-1 stage 2, A <- A (X_k - Y_j), with the table stored as images of Mp - Y_j.
-  void mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp);
-  bool mul_sum_is_fused() const { return pl_.sum_fast; }
-  // reg = reg^(2^nbits) * factor^B, B the nbits-bit integer in `bits` (most significant bit first, packed in bytes, bit 7 of a byte first):
-  // one square_mul(reg, bit ? factor : 1) per bit -- square_mul_n with a per-step factor (stage 1 of P-1: 3^E)
-  void square_mul_bits(size_t r, uint32_t factor, const uint8_t* bits, size_t nbits);
+  void sync() override;
+  void set_u32(size_t dst, uint32_t v) override;
+  void set_digits(size_t dst, const uint64_t* d, size_t count) override;
+  void get_digits(size_t src, uint64_t* d, size_t count) override;
+  void set_words(size_t dst, const uint32_t* w, size_t count) override;
+  void get_words(size_t src, uint32_t* w, size_t count) override;
+  uint64_t res64(size_t src) override;
+  void copy(size_t dst, size_t src) override;
+  void set_multiplicand(size_t dst, size_t src) override;
+  void square_mul(size_t r, uint32_t a) override;
+  void mul(size_t dst, size_t src, uint32_t a) override;
+  void add(size_t dst, size_t src) override;
+  void sub_reg(size_t dst, size_t src) override;
+  void sub_u32(size_t r, uint32_t v) override;
+  bool equal(size_t lhs, size_t rhs) override;
+  // one run-wise sweep (the reference's fused variants: include/marin/engine.h:65-131; kernels/marin.cl:1856-1947)
+  void addsub(long sum, long sum_copy, long diff, long diff_copy, size_t a, size_t b) override;
+  // What this family fuses (kernels/marin.cl:2160-2365): the copy or the addend goes into the back sweep's carry chain where the plan has the
+  // fused back sweep and the factor is within its bound, else the base composition
+  void mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t a) override;
+  void square_mul_copy(size_t src, size_t dst_copy, uint32_t a) override;
+  void mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t a) override;
+  // three launches per squaring, straight down square_chain (the benchmark's path)
+  void square_mul_n(size_t r, uint32_t a, size_t count, uint32_t sub) override;
+  void square_mul_bits(size_t r, uint32_t factor, const uint8_t* bits, size_t nbits) override;
+  // one product through the row sweep's mode 3 where the plan's capacity allows it (plan.hpp sum_product_ok), else the base's two products;
+  // for P-1 stage 2, A <- A (X_k - Y_j), the table is stored as images of Mp - Y_j
+  void mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp) override;
+  bool mul_sum_is_fused() const override { return pl_.sum_fast; }
 
-  size_t register_data_size() const { return reg_bytes_ + 8; }
-  void get_data(size_t src, void* data, size_t size);
-  void set_data(size_t dst, const void* data, size_t size);
-  size_t checkpoint_size() const { return nregs_ * register_data_size(); }
-  void get_checkpoint(void* data, size_t size);
-  void set_checkpoint(const void* data, size_t size);
+  size_t register_data_size() const override { return reg_bytes_ + 8; }
+  void get_data(size_t src, void* data, size_t size) override;
+  void set_data(size_t dst, const void* data, size_t size) override;
 
   // measurement
   static constexpr size_t kKernels = 6;   // five kernel slots of a squaring + the measured cost of an event record
-  static const char* kernel_name(size_t k);
-  void time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, double* total_ms, double* kernel_ms, size_t kcount);
-  size_t algorithmic_bytes() const { return 48 * pl_.n; }
+  static const char* stage_name(size_t k);
+  size_t kernel_count() const override { return kKernels; }
+  const char* kernel_name(size_t k) const override { return stage_name(k); }
+  void time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, double* total_ms, double* kernel_ms, size_t kcount) override;
+  size_t algorithmic_bytes() const override { return 48 * pl_.n; }
 #if defined(MI355_PROBE)
   // diagnostics build only: `iters` timed launches of one sweep (kind 0 front, 1 rows, 2 back) over grid_mult x its grid with
   // extra_lds bytes of padding LDS (forces fewer groups per CU), then one launch with the timeline probe on (8 words per group -> tl)
@@ -84,15 +79,13 @@ class Engine {
  private:
   // kDigits: unweighted u32 digits (+ deferred run carries); kImage: multiplicand
   enum Kind : uint8_t { kDigits = 0, kImage = 1 };
-  void check_reg(size_t r) const;
-  void need_digits(size_t r, const char* op) const;
+  bool holds_image(size_t r) const override { return kind_[r] == kImage; }
   uint32_t* digits(size_t r) { return reinterpret_cast<uint32_t*>(slot_[r]); }
   uint64_t* image(size_t r) { return reinterpret_cast<uint64_t*>(slot_[r]); }
   uint64_t* work() { return reinterpret_cast<uint64_t*>(slot_[nregs_]); }
   void swap_with_work(size_t r) { std::swap(slot_[r], slot_[nregs_]); }
   void read_values(size_t src, std::vector<uint64_t>& v);   // natural order, strongly carried digits
-  void read_values_host(size_t src, std::vector<uint64_t>& v);   // the same through D2H + host carry (reference's way)
-  void get_words_host(size_t src, uint32_t* w, size_t count);    // words packed by the host loop (fallback, MI355_HOST_CARRY=1)
+  void read_values_host(size_t src, std::vector<uint64_t>& v);   // the same through D2H + host carry (reference's way: host_digits.hpp)
   uint32_t* canon_digits(size_t r, int slot);   // device: canonical digits of r in natural order (canon.hip), slot 0 / 1
   bool canon_flags_ok(uint32_t (&flags)[4]);    // reads the flag words; false: fall back to the host carry
   void write_values(size_t dst, const std::vector<uint32_t>& natural);
@@ -100,7 +93,6 @@ class Engine {
   uint64_t* cbuf(size_t r) { return cb_[r]; }
   uint64_t* take_spare_cbuf();                      // carry-word buffers are handed around like the register slots
   void adopt_cbuf(size_t r, uint64_t* fresh);       // r's pending carries are now in `fresh`; its old buffer becomes spare
-  void linear(long s1, long s2, long d1, long d2, size_t a, size_t b);
   void back_ext(size_t dst, uint32_t a, long copy_to, long add_src);
   void normalize(size_t r);          // apply deferred run carries
   void carry_fix_now(size_t r, int excess = -1);   // run carries into the digits right away (plans with runs of two digits cannot defer
@@ -112,6 +104,7 @@ class Engine {
 
   Plan pl_;
   DevPlan dp_{};
+  CanonGeom cg_{};           // dp_ as canon.hip sees it (tile-major registers)
   int device_ = 0;
   bool verbose_ = false;
   hipStream_t stream_ = nullptr;

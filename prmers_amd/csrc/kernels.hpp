@@ -114,17 +114,4 @@ hipError_t v2_probe_launch(const DevPlan& pl, int kind, int grid_mult, int extra
 hipError_t v5_probe_launch(const DevPlan& pl, int kind, int grid_mult, int extra_lds, const uint32_t* digits, uint64_t* cbuf, uint64_t* W, uint32_t* dout, hipStream_t s);
 #endif
 
-// device-side canonical form (canon.hip): strong carry with wrap-around into natural order, compare, scatter
-size_t canon_scratch_words(const DevPlan& pl);
-hipError_t canon_launch(const DevPlan& pl, uint32_t p, const uint32_t* digits, uint32_t* out, uint32_t* scratch, hipStream_t s);
-uint32_t* canon_flags(const DevPlan& pl, uint32_t* scratch);
-hipError_t canon_compare(const uint32_t* a, const uint32_t* b, uint32_t n, uint32_t* diff_flag, hipStream_t s);
-hipError_t canon_relax(const DevPlan& pl, uint32_t p, const uint32_t* in, uint32_t* out, hipStream_t s);   // one local carry pass, tile-major both sides
-hipError_t canon_scatter(const DevPlan& pl, uint32_t p, const uint32_t* nat, uint32_t* digits, hipStream_t s);
-hipError_t canon_set_small(const DevPlan& pl, uint32_t p, uint32_t* digits, uint32_t value, hipStream_t s);
-// residue words (ceil(p / 32), little-endian, value below 2^p) <-> digits, on the device: canonical digits in natural order -> words;
-// words -> the digits of a register in tile-major order
-hipError_t canon_pack_words(const DevPlan& pl, uint32_t p, const uint32_t* canon, uint32_t* words, hipStream_t s);
-hipError_t canon_unpack_words(const DevPlan& pl, uint32_t p, const uint32_t* words, uint32_t* digits, hipStream_t s);
-
 }  // namespace mi355

@@ -17,6 +17,9 @@
 #include "gfdft.hpp"
 
 namespace mi355 {
+
+void selftest_primitives(int device);   // selftest.hip: every family below on the GPU, one lane per case; throws on the first mismatch
+
 namespace cases {
 
 typedef unsigned __int128 u128;
