@@ -240,7 +240,7 @@ def test_edge_values():
 @pytest.mark.parametrize("p", [9815459, 19000013, 50000017, 100000007, 136279841, 205271257, 250000013, 332000003])
 def test_extreme_digits_full_size(p):
     """Every digit at its maximum (x = Mp - 1 = -1: the largest convolution sums and the longest carry chains the transform can see) at the
-    full-size shapes of every register-resident kernel set: (-1)^2 = 1, (-1)^2 * 3 = 3, then 3^2 - 2 through the deferred subtraction; digit
+    full-size shapes of every register-resident kernel set: (-1)^2 = 1, (-1)^2 * 3 = 3, then 3^2 - 2 through sub (a borrow through the digits); digit
     vectors against the oracle and the values by hand."""
     o = orc.Oracle(p, 2)
     w = o.widths().astype(np.uint64)
@@ -276,19 +276,25 @@ def test_c2_9815459_first_iterations():
                 assert np.array_equal(e.digits(0), o.digits(0)), it
 
 
-@pytest.mark.parametrize("p,n", [(9815459, 1 << 19), (4800007, 1 << 18), (50000017, 5 << 19), (19000013, 1 << 20)])
-def test_radix4_set_full_size_operations(p, n):
+RADIX4_FULL = [(9815459, 1 << 19, None), (4800007, 1 << 18, None), (50000017, 5 << 19, None), (19000013, 1 << 20, None), (30402457, 1 << 21, "m2=4096")]
+
+
+@pytest.mark.parametrize("p,n,plan", RADIX4_FULL, ids=["%d-%d%s" % (p, n, "-" + plan if plan else "") for p, n, plan in RADIX4_FULL])
+def test_radix4_set_full_size_operations(p, n, plan):
     """The shapes of the register-resident radix-4 kernels at full-size digits (kernels_v3.hip): C2 (columns of 256 x 4 + rows of 1024),
-    n = 2^18 (rows of 1024 over generic columns of 128), n = 5 2^19 (rows of 1024 under the radix-5 columns) and n = 2^20 (columns of
-    256 x 4 around the plane-per-thread rows of 2048, kernels_v2.hip k2_rows2048_planes): squarings with a factor,
-    the LL step with the subtraction deferred into the next sweep, set_multiplicand / mul (forward-only and multiply modes of the row
+    n = 2^18 (rows of 1024 over generic columns of 128), n = 5 2^19 (rows of 1024 under the radix-5 columns), n = 2^20 (columns of
+    256 x 4 around the plane-per-thread rows of 2048, kernels_v2.hip k2_rows2048_planes) and n = 2^21 forced to columns of 256 x 4 under
+    rows of 4096 (the smallest shape that selects the pair-per-thread form of the column kernels: more than 512 tiles): squarings with a
+    factor, the LL step (sub between two squarings), set_multiplicand / mul (forward-only and multiply modes of the row
     kernel), the fused back sweeps (mul_add, square_mul_copy) -- digit vectors against the oracle."""
     o = orc.Oracle(p, 4)
     rng = np.random.default_rng(p)
     w = o.widths().astype(np.uint64)
     d0 = (rng.integers(0, 1 << 62, o.n, dtype=np.uint64) & ((np.uint64(1) << w) - np.uint64(1))) | (w << np.uint64(32))
-    with Engine(p, 4) as e:
+    with Engine(p, 4, plan=plan) as e:
         assert e.n == n == o.n
+        if plan:   # 1024 tiles of 256 x 4: above the 512 up to which plan.hpp choose_kernels takes the plane form (test_host_logic.py pins that choice)
+            assert "m1=256:m2=4096:c=4" in e.describe(), e.describe()
         e.set_digits(0, d0); o.set_digits(0, d0)
         for it in range(3):
             e.square_mul(0); o.square_mul(0)
@@ -325,7 +331,7 @@ def test_c3_136279841_full_size():
             e.square_mul(0); o.square_mul(0)
         assert np.array_equal(e.digits(0), o.digits(0))
         e.square_mul(0, 3); o.square_mul(0, 3)
-        e.sub(0, 2); o.sub(0, 2)                       # LL step with the subtraction deferred into the next sweep
+        e.sub(0, 2); o.sub(0, 2)                       # LL step: sub borrows through the digits before the next squaring
         e.square_mul(0); o.square_mul(0)
         assert np.array_equal(e.digits(0), o.digits(0))
         e.copy(1, 0); o.copy(1, 0)

@@ -30,7 +30,7 @@ def Engine(*a, **k):
 
 def reference_run(p):
     """the oracle's digit vectors after a short chain that exercises every sweep variant: squarings with and without a factor, the LL
-    step folded into the next load, a multiplicand image and a mul"""
+    step (sub borrows through the digits before the next squaring), a multiplicand image and a mul"""
     o = orc.Oracle(p, 3)
     rng = np.random.default_rng(p)
     x0 = int.from_bytes(rng.bytes((p + 7) // 8), "little") % ((1 << p) - 1)
