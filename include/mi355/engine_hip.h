@@ -65,6 +65,8 @@ class engine_hip final : public engine {
     int (*mul_sum)(void*, size_t, size_t, size_t, size_t) = nullptr;
     int (*mul_sum_is_fused)(void*) = nullptr;
     int (*square_mul_bits)(void*, size_t, uint32_t, const uint8_t*, size_t) = nullptr;
+    int (*square_mul_prepare)(void*, size_t, size_t, uint32_t) = nullptr;
+    int (*square_mul_prepare_is_fused)(void*) = nullptr;
 
     template <class F> void bind(F& f, const char* name) {
       f = reinterpret_cast<F>(dlsym(so, name));
@@ -104,6 +106,8 @@ class engine_hip final : public engine {
       mul_sum = reinterpret_cast<decltype(mul_sum)>(dlsym(so, "mi355_engine_mul_sum"));
       mul_sum_is_fused = reinterpret_cast<decltype(mul_sum_is_fused)>(dlsym(so, "mi355_engine_mul_sum_is_fused"));
       square_mul_bits = reinterpret_cast<decltype(square_mul_bits)>(dlsym(so, "mi355_engine_square_mul_bits"));
+      square_mul_prepare = reinterpret_cast<decltype(square_mul_prepare)>(dlsym(so, "mi355_engine_square_mul_prepare"));
+      square_mul_prepare_is_fused = reinterpret_cast<decltype(square_mul_prepare_is_fused)>(dlsym(so, "mi355_engine_square_mul_prepare_is_fused"));
     }
     ~Api() { if (so) dlclose(so); }
   };
@@ -180,6 +184,14 @@ class engine_hip final : public engine {
     if (_api.square_mul_bits) { ok(_api.square_mul_bits(_h, src, a, bits, nbits), "square_mul_bits"); return; }
     for (size_t i = 0; i < nbits; ++i) square_mul(src, ((bits[i >> 3] >> (7 - (i & 7))) & 1) ? a : 1u);
   }
+  // The ECM operation (prmers_amd/ecm.py): img_out = the multiplicand image of src, then src = src^2 * a -- one squaring whose row sweep
+  // keeps the transform of its operand; set_multiplicand + square_mul when the library does not export it
+  void square_mul_prepare(const Reg src, const Reg img_out, const uint32_t a = 1) const {
+    if (_api.square_mul_prepare) { ok(_api.square_mul_prepare(_h, src, img_out, a), "square_mul_prepare"); return; }
+    if (src == img_out) throw std::runtime_error("MI355 square_mul_prepare failed: img_out must differ from src");
+    set_multiplicand(img_out, src); square_mul(src, a);
+  }
+  bool square_mul_prepare_is_fused() const { return _api.square_mul_prepare_is_fused && _api.square_mul_prepare_is_fused(_h) != 0; }
   // the canonical residue as ceil(p / 32) little-endian words (2^p - 1 reads as 0) / a register from such words: packed and cut on the
   // device by the library, through the digit vector when it does not export the word entry points
   std::vector<uint32_t> get_words(const Reg src) const {

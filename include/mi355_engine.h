@@ -6,8 +6,9 @@
  * pattern binds it unchanged; the C++ adapter that serves `-engine-marin` is include/mi355/engine_hip.h
  * (hook: src/marin/gpu.cpp:149).
  *
- * 49 symbols: the 19 shapes of that ABI, digit I/O, raw images, the fused register operations, the proof fold (exp_mul / exp_mul2), the
- * P-1 operations (mul_sum / mul_sum_is_fused / square_mul_bits), timing hooks, the device self-test and the mi355_crt_* entry points.
+ * 51 symbols: the 19 shapes of that ABI, digit I/O, raw images, the fused register operations, the proof fold (exp_mul / exp_mul2), the
+ * P-1 operations (mul_sum / mul_sum_is_fused / square_mul_bits), the ECM operation (square_mul_prepare / square_mul_prepare_is_fused),
+ * timing hooks, the device self-test and the mi355_crt_* entry points.
  *
  * Conventions (same as the reference ABI, EngineApi.cpp:447-517):
  *   - int results: 1 = ok, 0 = failure; the message is in mi355_engine_last_error() (thread-local,
@@ -108,6 +109,19 @@ MI355_ENGINE_API int mi355_engine_mul_sum_is_fused(mi355_engine_handle handle);
    factor (stage 1 of P-1 is 3^E with about 1.44 B1 bits).  A factor above the plan's fused bound follows the rule of square_mul.
    nbits = 0: nothing happens.  Both families. */
 MI355_ENGINE_API int mi355_engine_square_mul_bits(mi355_engine_handle handle, size_t reg, uint32_t factor, const uint8_t* bits, size_t nbits);
+
+/* ---- ECM on Montgomery curves (prmers_amd/ecm.py; the reference: src/modes/RunEcm.cpp) ---- */
+/* img_out = the multiplicand image of src, then src = src^2 * factor.  src holds a residue, img_out is any other register (whatever it held
+   is overwritten), factor >= 1; everything is checked before the first launch, so a refused call changes nothing.  Afterwards
+   mul(dst, img_out) multiplies by the value src had BEFORE the call (its pending run carries and small subtractions included), exactly as
+   after set_multiplicand(img_out, src).  A Montgomery ladder step squares X + Z and X - Z and also multiplies by both: the row sweep of a
+   squaring holds the forward transform that set_multiplicand would compute, so it stores it on the way (row-sweep mode 4): three sweeps
+   and one more store of 8n bytes instead of five sweeps.  The image bytes need not equal set_multiplicand's (both are valid
+   representatives of the same field elements).  A factor above the plan's fused bound follows the rule of square_mul.  On a crt handle the
+   same result comes from the composition set_multiplicand(img_out, src); square_mul(src, factor). */
+MI355_ENGINE_API int mi355_engine_square_mul_prepare(mi355_engine_handle handle, size_t src, size_t img_out, uint32_t factor);
+/* 1: square_mul_prepare runs as one squaring (three sweeps) on this handle; 0: as the composition (or the handle is not valid) */
+MI355_ENGINE_API int mi355_engine_square_mul_prepare_is_fused(mi355_engine_handle handle);
 
 /* ---- rest of the engine surface the Marin callers use ---- */
 /* engine::get / engine::set(Reg, uint64*) (engine.h:24-25): n digits, value | width << 32, strongly

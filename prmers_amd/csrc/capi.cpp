@@ -149,6 +149,8 @@ int mi355_engine_exp_mul(mi355_engine_handle h, size_t a, uint64_t e, size_t b, 
 int mi355_engine_exp_mul2(mi355_engine_handle h, size_t a, uint64_t e, size_t b, size_t tmp) { return guarded([&] { m(h)->exp_mul(a, e, b, tmp, true); }); }
 int mi355_engine_mul_sum(mi355_engine_handle h, size_t dst, size_t a, size_t b, size_t tmp) { return guarded([&] { m(h)->mul_sum(dst, a, b, tmp); }); }
 int mi355_engine_mul_sum_is_fused(mi355_engine_handle h) { int r = 0; guarded([&] { r = m(h)->mul_sum_is_fused() ? 1 : 0; }); return r; }
+int mi355_engine_square_mul_prepare(mi355_engine_handle h, size_t src, size_t img, uint32_t f) { return guarded([&] { m(h)->square_mul_prepare(src, img, f); }); }
+int mi355_engine_square_mul_prepare_is_fused(mi355_engine_handle h) { int r = 0; guarded([&] { r = m(h)->square_mul_prepare_is_fused() ? 1 : 0; }); return r; }
 int mi355_engine_square_mul_bits(mi355_engine_handle h, size_t r, uint32_t f, const uint8_t* bits, size_t nbits) {
   return guarded([&] { m(h)->square_mul_bits(r, f, bits, nbits); });
 }

@@ -216,8 +216,8 @@ void Engine::run_front(size_t r) {
   else HIPCHK(cols_.front(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, work(), stream_));
 }
 
-void Engine::run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, const uint64_t* y2) {
-  HIPCHK(rows_(dp_, in, y, y2, out, mode, stream_));
+void Engine::run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, const uint64_t* y2, uint64_t* img) {
+  HIPCHK(rows_(dp_, in, y, y2, img, out, mode, stream_));
 }
 
 // work() -> digits(r) + run carries in cbuf(r): runs of 2C >= 4 digits leave them to the next sweep, which folds them in, runs of two
@@ -569,6 +569,19 @@ void Engine::mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp) {
   run_front(dst);   // pending run carries (and a borrowed-through sub) of dst go in exactly as in mul
   run_middle(work(), image(src_a), work(), 3, image(src_b));
   run_back(dst, 1);
+}
+
+// img_out = the multiplicand image of src, src = src^2 a: a squaring whose row sweep (mode 4) also stores the forward transform it squares.
+// The front sweep has taken src's pending run carries in by then, so the image is the one set_multiplicand(img_out, src) would write now.
+void Engine::square_mul_prepare(size_t src, size_t img_out, uint32_t a) {
+  check_square_mul_prepare(src, img_out, a);
+  HIPCHK(hipSetDevice(device_));
+  run_front(src);
+  run_middle(work(), nullptr, work(), 4, nullptr, image(img_out));
+  kind_[img_out] = kImage;
+  pending_carry_[img_out] = 0;
+  run_back(src, a > pl_.a_fast ? 1u : a);
+  if (a > pl_.a_fast) scale(src, a);   // beyond the fused carry's bound: the rule of square_mul
 }
 
 void Engine::square_mul_bits(size_t r, uint32_t factor, const uint8_t* bits, size_t nbits) {

@@ -58,6 +58,10 @@ class Engine final : public RegisterMachine {
   // for P-1 stage 2, A <- A (X_k - Y_j), the table is stored as images of Mp - Y_j
   void mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp) override;
   bool mul_sum_is_fused() const override { return pl_.sum_fast; }
+  // front sweep, rows in mode 4 (a squaring that stores the forward transform of its operand to img_out), back sweep: the two sweeps of
+  // set_multiplicand(img_out, src) become one more store of 8n bytes.  Every plan has it.
+  void square_mul_prepare(size_t src, size_t img_out, uint32_t a) override;
+  bool square_mul_prepare_is_fused() const override { return true; }
 
   size_t register_data_size() const override { return reg_bytes_ + 8; }
   void get_data(size_t src, void* data, size_t size) override;
@@ -99,7 +103,7 @@ class Engine final : public RegisterMachine {
                                                    // them); excess: bits of a carry word above the first digit's width (-1: a <= 15)
   void scale(size_t r, uint32_t a);   // r x a, run-wise (k_scale): factors above pl_.a_fast
   void run_front(size_t r);          // digits(r) (+ pending run carries) -> work_
-  void run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, const uint64_t* y2 = nullptr);
+  void run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, const uint64_t* y2 = nullptr, uint64_t* img = nullptr);
   void run_back(size_t r, uint32_t a, hipEvent_t* ev = nullptr);
 
   Plan pl_;

@@ -327,9 +327,11 @@ __global__ void __launch_bounds__(1024) k_front(DevPlan pl, const uint32_t* __re
 
 // ---------------------------------------------------------------------------------------------
 // middle: one work-group per row.  mode 0: square, 1: multiply by image Y, 2: forward only, 3: multiply by the sum of the images Y and Y2.
+// mode 4 (KEEP, k_middle_keep): mode 0 that also stores the forward transform of the operand to Wimg, as mode 2 would store it.
 // ---------------------------------------------------------------------------------------------
+template <bool KEEP = false>
 __device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* Win, const uint64_t* Yimg, const uint64_t* Yimg2, uint64_t* Wout, int mode, uint32_t sub, uint32_t row,
-                                            P2* X, uint32_t tid, uint32_t nthr) {
+                                            P2* X, uint32_t tid, uint32_t nthr, uint64_t* Wimg = nullptr) {
   const uint32_t M2 = pl.M2;
   const P2* in = reinterpret_cast<const P2*>(Win) + size_t(row) * M2;
   P2* out = reinterpret_cast<P2*>(Wout) + size_t(row) * M2;
@@ -350,6 +352,10 @@ __device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* W
   if (mode == 2) {
     for (uint32_t e = tid; e < M2; e += nthr) out[e] = X[e];
     return;
+  }
+  if constexpr (KEEP) {   // every thread stores the elements it squares next: no barrier between the two
+    P2* img = reinterpret_cast<P2*>(Wimg) + size_t(row) * M2;
+    for (uint32_t e = tid; e < M2; e += nthr) img[e] = X[e];
   }
   const P2* Y = reinterpret_cast<const P2*>(Yimg) + size_t(row) * M2;
   for (uint32_t e = tid; e < M2; e += nthr) {
@@ -378,6 +384,9 @@ __device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* W
 __global__ void __launch_bounds__(1024) k_middle(DevPlan pl, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Yimg,
                                                 const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout, int mode, uint32_t sub) {
   middle_body(pl, Win, Yimg, Yimg2, Wout, mode, sub, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
+}
+__global__ void __launch_bounds__(1024) k_middle_keep(DevPlan pl, const uint64_t* __restrict__ Win, uint64_t* __restrict__ Wimg, uint64_t* __restrict__ Wout, uint32_t sub) {
+  middle_body<true>(pl, Win, nullptr, nullptr, Wout, 0, sub, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x, Wimg);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -737,8 +746,10 @@ hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_
   hipLaunchKernelGGL(k_front, dim3(pl.M2 / pl.C), dim3(block_for_small(pl, tile)), tile * 16, s, pl, digits, cbuf_in, W);
   return hipGetLastError();
 }
-hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) {
-  hipLaunchKernelGGL(k_middle, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Y, Y2, Wout, mode, 0u);
+hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s) {
+  if (mode < 0 || mode > 4) return hipErrorInvalidValue;
+  if (mode == 4) hipLaunchKernelGGL(k_middle_keep, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Wimg, Wout, 0u);
+  else hipLaunchKernelGGL(k_middle, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Y, Y2, Wout, mode, 0u);
   return hipGetLastError();
 }
 hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s) {
@@ -805,8 +816,11 @@ hipError_t configure_kernels(size_t lds_front, size_t lds_mid) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_back<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_front));
     if (e != hipSuccess) return e;
   }
-  if (lds_mid > 48 * 1024)
+  if (lds_mid > 48 * 1024) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_middle), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_mid));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_middle_keep), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_mid));
+  }
   return e;
 }
 

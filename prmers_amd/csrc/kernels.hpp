@@ -76,18 +76,20 @@ hipError_t launch_sub_small(const DevPlan& pl, uint32_t* digits, uint32_t a, hip
 //   build_fourstep (register-resident columns): the chain starts and ratios of their four-step twiddles (tiles x threads x 2 + M2 x 2 words)
 //   rows: Win -> Wout (mode 0: squaring, 1: times the multiplicand image Y, 2: forward only, Wout a multiplicand image,
 //         3: times the SUM of the images Y and Y2, added word by word in the field: the forward transform is linear, so that is the image of
-//         the sum of the two residues; Y2 is read in mode 3 only)
+//         the sum of the two residues; Y2 is read in mode 3 only,
+//         4: squaring that also stores the forward transform of its operand to Wimg, in the form in which the same kernel's mode 2 stores
+//         it: Wimg is then a multiplicand image of the operand; written in mode 4 only)
 typedef hipError_t (*FrontFn)(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s);
 typedef hipError_t (*BackFn)(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s);
 typedef hipError_t (*BackExtFn)(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
 typedef hipError_t (*FourStepFn)(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i, uint64_t* fbf, uint64_t* fbi, hipStream_t s);
-typedef hipError_t (*RowsFn)(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s);
+typedef hipError_t (*RowsFn)(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
 struct ColSweeps { FrontFn front; BackFn back; BackExtFn back_ext; FourStepFn build_fourstep; };
 
 // generic set (kernels.hip): tiles in LDS, any shape
 hipError_t configure_kernels(size_t lds_front, size_t lds_mid);
 hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s);
-hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
 hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s);
 hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
 // columns of 5 L1 pairs that do not fit LDS (n = 5 * 2^26): the radix-5 stage through a second work buffer U (8 n bytes), C = 1
@@ -101,12 +103,12 @@ ColSweeps v2_cols(uint32_t R);    // radix-8 columns of 512 R, R = 1, 2, 4 (kern
 ColSweeps v3_cols(bool planes);   // radix-4 columns of 256 x 4, a pair or a plane per thread (kernels_v3.hip)
 ColSweeps v5_cols(bool j1);       // radix-5 columns of 1280 x 4 or (j1) 2560 x 2 (kernels_v5.hip)
 void v5_pfa(bool j1, uint32_t* u, uint32_t* v);   // the frequency map of their prime-factor form (DevPlan.lab_u / lab_v)
-hipError_t v2_rows4096(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s);
-hipError_t v2_rows8192(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s);
-hipError_t v2_rows2048_one(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s);
-hipError_t v2_rows2048_two(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s);
-hipError_t v3_rows1024_pairs(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s);
-hipError_t v3_rows1024_planes(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t v2_rows4096(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t v2_rows8192(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t v2_rows2048_one(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t v2_rows2048_two(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t v3_rows1024_pairs(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
+hipError_t v3_rows1024_planes(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
 #if defined(MI355_PROBE)
 // one launch of sweep `kind` (0 front, 1 rows, 2 back) over grid_mult x the normal grid with extra_lds bytes of padding LDS:
 // the rows of 4096 and the columns of 1024 x 4 (v2), the columns of 1280 x 4 (v5)

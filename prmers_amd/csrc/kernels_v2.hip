@@ -39,7 +39,8 @@ namespace v2 {
 //   S4 thread (k3|k1|k2) regs d4 -> k4 ; X[k], k = k1 + 8 k2 + 64 k3 + 512 k4
 // pointwise in registers, then the mirror image back to natural order.
 // mode 0: square, 1: multiply by image Y, 2: forward only (writes the image), 3: multiply by the word-wise sum of the images Y and Y2
-// (mode 1 with y = Y[i] + Y2[i]: both are un-folded mode-2 outputs, gf::add_lazy_any).
+// (mode 1 with y = Y[i] + Y2[i]: both are un-folded mode-2 outputs, gf::add_lazy_any), 4: mode 0 that first stores what mode 2 would
+// store to Wimg (the image of the operand, straight from the registers the pointwise stage reads next).
 // ---------------------------------------------------------------------------------------------
 // H = 2 serves rows of 8192 with 1024 threads: one radix-2 level on top (element i and i + 4096; thread group
 // h = 0 forms the sums, h = 1 the differences times omega_8192^i, each group loads both halves), then each
@@ -85,7 +86,7 @@ __device__ __forceinline__ void dft_rows_first(P2 (&x)[8]) {   // the first-stag
 
 template <int mode, int H, int RL = 0>
 __global__ void __launch_bounds__(512 * H, 4) k2_rows4096(DevPlan pl, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Yimg,
-                                                          const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout, uint32_t sub) {
+                                                          const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wimg, uint64_t* __restrict__ Wout, uint32_t sub) {
   static_assert(RL == 0 || (RL == 1 && H == 1), "two rows to a tile only with one tile per work-group");
   constexpr bool HALF = (RL > 0);
   constexpr int HH = H;                 // 4096-pair tiles per work-group
@@ -160,6 +161,11 @@ __global__ void __launch_bounds__(512 * H, 4) k2_rows4096(DevPlan pl, const uint
     for (int j = 0; j < 8; ++j) out[512 * j + t] = x[j];
     return;
   }
+  if (mode == 4) {
+    P2* img = reinterpret_cast<P2*>(Wimg) + size_t(tile) * (4096 * HH) + h * 4096;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) img[512 * j + t] = x[j];
+  }
 
   PROBE_MID(pl)
   // ---- pointwise: reg k4 holds X[kb + 512 k4]; rho = omega_m^(k1row + M1 k) = rho0 * omega_8^k4 ----
@@ -173,7 +179,7 @@ __global__ void __launch_bounds__(512 * H, 4) k2_rows4096(DevPlan pl, const uint
       const bool neg = (k4 == 1) || (k4 == 3) || (k4 == 4) || (k4 == 6);
       const P2 u = x[k4];
       P2 r;
-      if (mode == 0) {   // (u0 + u1 t)^2 mod (t^2 - rho), marin.cl:379-384
+      if (mode == 0 || mode == 4) {   // (u0 + u1 t)^2 mod (t^2 - rho), marin.cl:379-384
         const uint64_t q = gf::mul_pow2(gf::mul(gf::sqr(u.b), rho0), sh);
         const uint64_t s0 = gf::sqr(u.a);
         r.a = neg ? gf::sub(s0, q) : gf::add(s0, q);
@@ -318,7 +324,7 @@ constexpr uint32_t kLdsBytesPlanes = 4096 * 8;
 
 template <int mode>
 __global__ void __launch_bounds__(512, 4) k2_rows2048_planes(DevPlan pl, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Yimg,
-                                                             const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout, uint32_t sub) {
+                                                             const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wimg, uint64_t* __restrict__ Wout, uint32_t sub) {
   uint64_t* X = reinterpret_cast<uint64_t*>(smem_v2);
   const uint32_t t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t row = blockIdx.x;
@@ -367,6 +373,11 @@ __global__ void __launch_bounds__(512, 4) k2_rows2048_planes(DevPlan pl, const u
     for (int j = 0; j < 8; ++j) img[512 * j + t] = x[j];   // (un-folded sums: a multiplication reads them)
     return;
   }
+  if (mode == 4) {
+    uint64_t* img = Wimg + size_t(row) * 4096;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) img[512 * j + t] = x[j];
+  }
 
   // ---- pointwise: (a + b t)^2 or (a + b t)(ya + yb t) mod (t^2 - rho), rho = rho0 omega_8^k4; plane a computes and keeps the t^0 word ----
   {
@@ -378,7 +389,7 @@ __global__ void __launch_bounds__(512, 4) k2_rows2048_planes(DevPlan pl, const u
       const bool neg = (k4 == 1) || (k4 == 3) || (k4 == 4) || (k4 == 6);
       const uint64_t w = x[k4];
       uint64_t keep, send;
-      if (mode == 0) {
+      if (mode == 0 || mode == 4) {
         const uint64_t o = swap32(w, partner);
         keep = gf::sqr(w);                                            // a^2 | b^2
         send = gf::mul(pln ? keep : w, pln ? rho0 : o);               // a b | b^2 rho0
@@ -394,7 +405,7 @@ __global__ void __launch_bounds__(512, 4) k2_rows2048_planes(DevPlan pl, const u
         if (pln) { const uint64_t q = gf::mul_pow2(gf::mul(keep, rho0), sh); keep = send; send = q; }   // plane b keeps b ya, sends b yb rho
       }
       const uint64_t recv = swap32(send, partner);
-      if (mode == 0) x[k4] = pln ? gf::dbl(recv) : (neg ? gf::sub(keep, recv) : gf::add(keep, recv));
+      if (mode == 0 || mode == 4) x[k4] = pln ? gf::dbl(recv) : (neg ? gf::sub(keep, recv) : gf::add(keep, recv));
       else x[k4] = pln ? gf::add(keep, recv) : (neg ? gf::sub(keep, recv) : gf::add(keep, recv));
     }
   }
@@ -822,27 +833,29 @@ ColSweeps v2_cols(uint32_t R) { return R == 1 ? cols<1>() : R == 2 ? cols<2>() :
 // rows: one instantiation per mode (the squaring kernel carries no multiply / image code); H = 2: rows of 8192 (1024 threads),
 // RL = 1: rows of 2048 two to a tile
 template <int H, int RL>
-static hipError_t rows(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) {
+static hipError_t rows(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s) {
   const dim3 grid(RL ? pl.M1 / 2 : pl.M1), block(512 * H);
   switch (mode) {
-    case 0: hipLaunchKernelGGL((v2::k2_rows4096<0, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Y2, Wout, 0u); break;
-    case 1: hipLaunchKernelGGL((v2::k2_rows4096<1, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Y2, Wout, 0u); break;
-    case 2: hipLaunchKernelGGL((v2::k2_rows4096<2, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Y2, Wout, 0u); break;
-    case 3: hipLaunchKernelGGL((v2::k2_rows4096<3, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Y2, Wout, 0u); break;
+    case 0: hipLaunchKernelGGL((v2::k2_rows4096<0, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Y2, Wimg, Wout, 0u); break;
+    case 1: hipLaunchKernelGGL((v2::k2_rows4096<1, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Y2, Wimg, Wout, 0u); break;
+    case 2: hipLaunchKernelGGL((v2::k2_rows4096<2, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Y2, Wimg, Wout, 0u); break;
+    case 3: hipLaunchKernelGGL((v2::k2_rows4096<3, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Y2, Wimg, Wout, 0u); break;
+    case 4: hipLaunchKernelGGL((v2::k2_rows4096<4, H, RL>), grid, block, H * v2::kLdsBytes, s, pl, Win, Y, Y2, Wimg, Wout, 0u); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
-hipError_t v2_rows4096(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) { return rows<1, 0>(pl, Win, Y, Y2, Wout, mode, s); }
-hipError_t v2_rows8192(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) { return rows<2, 0>(pl, Win, Y, Y2, Wout, mode, s); }
-hipError_t v2_rows2048_two(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) { return rows<1, 1>(pl, Win, Y, Y2, Wout, mode, s); }
+hipError_t v2_rows4096(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s) { return rows<1, 0>(pl, Win, Y, Y2, Wimg, Wout, mode, s); }
+hipError_t v2_rows8192(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s) { return rows<2, 0>(pl, Win, Y, Y2, Wimg, Wout, mode, s); }
+hipError_t v2_rows2048_two(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s) { return rows<1, 1>(pl, Win, Y, Y2, Wimg, Wout, mode, s); }
 // rows of 2048, one row per tile with one plane per thread
-hipError_t v2_rows2048_one(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) {
+hipError_t v2_rows2048_one(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s) {
   switch (mode) {
-    case 0: hipLaunchKernelGGL((v2::k2_rows2048_planes<0>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Y2, Wout, 0u); break;
-    case 1: hipLaunchKernelGGL((v2::k2_rows2048_planes<1>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Y2, Wout, 0u); break;
-    case 2: hipLaunchKernelGGL((v2::k2_rows2048_planes<2>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Y2, Wout, 0u); break;
-    case 3: hipLaunchKernelGGL((v2::k2_rows2048_planes<3>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Y2, Wout, 0u); break;
+    case 0: hipLaunchKernelGGL((v2::k2_rows2048_planes<0>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Y2, Wimg, Wout, 0u); break;
+    case 1: hipLaunchKernelGGL((v2::k2_rows2048_planes<1>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Y2, Wimg, Wout, 0u); break;
+    case 2: hipLaunchKernelGGL((v2::k2_rows2048_planes<2>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Y2, Wimg, Wout, 0u); break;
+    case 3: hipLaunchKernelGGL((v2::k2_rows2048_planes<3>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Y2, Wimg, Wout, 0u); break;
+    case 4: hipLaunchKernelGGL((v2::k2_rows2048_planes<4>), dim3(pl.M1), dim3(512), v2::kLdsBytesPlanes, s, pl, Win, Y, Y2, Wimg, Wout, 0u); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -852,9 +865,9 @@ hipError_t v2_rows2048_one(const DevPlan& pl, const uint64_t* Win, const uint64_
   { hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, int(BYTES)); \
     if (e_ != hipSuccess) return e_; }
 hipError_t v2_configure() {
-  MI355_SET_LDS((v2::k2_rows4096<0, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<1, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<2, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<3, 1>), v2::kLdsBytes)
-  MI355_SET_LDS((v2::k2_rows4096<0, 2>), 2 * v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<1, 2>), 2 * v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<2, 2>), 2 * v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<3, 2>), 2 * v2::kLdsBytes)
-  MI355_SET_LDS((v2::k2_rows4096<0, 1, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<1, 1, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<2, 1, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<3, 1, 1>), v2::kLdsBytes)
+  MI355_SET_LDS((v2::k2_rows4096<0, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<1, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<2, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<3, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<4, 1>), v2::kLdsBytes)
+  MI355_SET_LDS((v2::k2_rows4096<0, 2>), 2 * v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<1, 2>), 2 * v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<2, 2>), 2 * v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<3, 2>), 2 * v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<4, 2>), 2 * v2::kLdsBytes)
+  MI355_SET_LDS((v2::k2_rows4096<0, 1, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<1, 1, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<2, 1, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<3, 1, 1>), v2::kLdsBytes) MI355_SET_LDS((v2::k2_rows4096<4, 1, 1>), v2::kLdsBytes)
   MI355_SET_LDS(v2::k1_cols<1>, v2::kLdsBytes) MI355_SET_LDS(v2::k1_cols<2>, v2::kLdsBytes) MI355_SET_LDS(v2::k1_cols<4>, v2::kLdsBytes)
   MI355_SET_LDS(v2::k3_cols<1>, v2::kLdsBytes) MI355_SET_LDS(v2::k3_cols<2>, v2::kLdsBytes) MI355_SET_LDS(v2::k3_cols<4>, v2::kLdsBytes)
   { hipError_t e5 = v5_configure(); if (e5 != hipSuccess) return e5; }
@@ -869,7 +882,7 @@ hipError_t v2_probe_launch(const DevPlan& pl, int kind, int grid_mult, int extra
   if (kind == 1) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(v2::k2_rows4096<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((v2::k2_rows4096<0, 1>), dim3(pl.M1 * grid_mult), dim3(512), lds, s, pl, W, nullptr, nullptr, W, 0u);
+    hipLaunchKernelGGL((v2::k2_rows4096<0, 1>), dim3(pl.M1 * grid_mult), dim3(512), lds, s, pl, W, nullptr, nullptr, nullptr, W, 0u);
     return hipGetLastError();
   }
   const dim3 grid((pl.M2 / pl.C) * grid_mult), block(512);

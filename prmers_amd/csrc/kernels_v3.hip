@@ -130,7 +130,8 @@ __device__ __forceinline__ void inverse3(const Form& f, typename Form::E (&x)[4]
 //   S5 d5 (k1, k2, k3, k4 = t1..0)         -> k5 ; X[k], k = k1 + 4 k2 + 16 k3 + 64 k4 + 256 k5
 // pointwise in registers (rho = rho0 omega_4^k5), then the mirror image back to natural order.
 // mode 0: square, 1: multiply by image Y, 2: forward only (writes the image: register j of thread t at pair 256 j + t),
-// 3: multiply by the word-wise sum of the images Y and Y2 (mode 1 with y = Y[i] + Y2[i], gf::add_lazy_any).
+// 3: multiply by the word-wise sum of the images Y and Y2 (mode 1 with y = Y[i] + Y2[i], gf::add_lazy_any),
+// 4: mode 0 that first stores what mode 2 would store to Wimg (the image of the operand, from the registers the pointwise stage reads next).
 // ---------------------------------------------------------------------------------------------
 struct RowWords { uint64_t w[4][3], v[4][3]; };   // omega_1024^e after S1 .. S4, and their inverses
 // every table word of the kernel is requested at its entry: nothing after the first exchange waits for memory again
@@ -214,7 +215,7 @@ __device__ __forceinline__ void pointwise(const Planes& f, uint64_t (&x)[4], uin
 
 template <class Form, int mode>
 __global__ void __launch_bounds__(Form::kBlock) k2_rows1024(DevPlan pl, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Yimg,
-                                                            const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout) {
+                                                            const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wimg, uint64_t* __restrict__ Wout) {
   using E = typename Form::E;
   const Form f;
   const uint32_t t = f.t, row = blockIdx.x;
@@ -235,8 +236,13 @@ __global__ void __launch_bounds__(Form::kBlock) k2_rows1024(DevPlan pl, const ui
   if (mode != 2) { rho_lo = pl.TWlo[erho & ((1u << pl.twh) - 1)]; rho_hi = pl.TWhi[erho >> pl.twh]; }
 
   rows_forward(f, x, tw);
+  if (mode == 4) {
+    E* img = reinterpret_cast<E*>(Wimg + base);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) img[f.at(256 * j + t)] = x[j];
+  }
   if (mode != 2) {
-    pointwise<mode>(f, x, gf::mul(rho_lo, rho_hi), Yimg, Yimg2, base);
+    pointwise<(mode == 4 ? 0 : mode)>(f, x, gf::mul(rho_lo, rho_hi), Yimg, Yimg2, base);
     rows_inverse(f, x, tw);
   }
 #pragma unroll
@@ -445,19 +451,20 @@ __global__ void __launch_bounds__(kThreads) k_build_f0(DevPlan pl, uint64_t* __r
 
 // ------------------------------- launchers ---------------------------------------------------
 template <class Form>
-static hipError_t rows1024(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) {
+static hipError_t rows1024(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s) {
   const dim3 grid(pl.M1), block(Form::kBlock);
   switch (mode) {
-    case 0: hipLaunchKernelGGL((v3::k2_rows1024<Form, 0>), grid, block, v3::kLdsBytes, s, pl, Win, Y, Y2, Wout); break;
-    case 1: hipLaunchKernelGGL((v3::k2_rows1024<Form, 1>), grid, block, v3::kLdsBytes, s, pl, Win, Y, Y2, Wout); break;
-    case 2: hipLaunchKernelGGL((v3::k2_rows1024<Form, 2>), grid, block, v3::kLdsBytes, s, pl, Win, Y, Y2, Wout); break;
-    case 3: hipLaunchKernelGGL((v3::k2_rows1024<Form, 3>), grid, block, v3::kLdsBytes, s, pl, Win, Y, Y2, Wout); break;
+    case 0: hipLaunchKernelGGL((v3::k2_rows1024<Form, 0>), grid, block, v3::kLdsBytes, s, pl, Win, Y, Y2, Wimg, Wout); break;
+    case 1: hipLaunchKernelGGL((v3::k2_rows1024<Form, 1>), grid, block, v3::kLdsBytes, s, pl, Win, Y, Y2, Wimg, Wout); break;
+    case 2: hipLaunchKernelGGL((v3::k2_rows1024<Form, 2>), grid, block, v3::kLdsBytes, s, pl, Win, Y, Y2, Wimg, Wout); break;
+    case 3: hipLaunchKernelGGL((v3::k2_rows1024<Form, 3>), grid, block, v3::kLdsBytes, s, pl, Win, Y, Y2, Wimg, Wout); break;
+    case 4: hipLaunchKernelGGL((v3::k2_rows1024<Form, 4>), grid, block, v3::kLdsBytes, s, pl, Win, Y, Y2, Wimg, Wout); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
-hipError_t v3_rows1024_pairs(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) { return rows1024<v3::Pairs>(pl, Win, Y, Y2, Wout, mode, s); }
-hipError_t v3_rows1024_planes(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wout, int mode, hipStream_t s) { return rows1024<v3::Planes>(pl, Win, Y, Y2, Wout, mode, s); }
+hipError_t v3_rows1024_pairs(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s) { return rows1024<v3::Pairs>(pl, Win, Y, Y2, Wimg, Wout, mode, s); }
+hipError_t v3_rows1024_planes(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s) { return rows1024<v3::Planes>(pl, Win, Y, Y2, Wimg, Wout, mode, s); }
 
 template <class Form>
 static hipError_t cols_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s) {

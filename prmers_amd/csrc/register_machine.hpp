@@ -96,6 +96,14 @@ class RegisterMachine {
   }
   virtual bool mul_sum_is_fused() const { return false; }
 
+  // img_out = the multiplicand image of src, then src = src^2 * factor: the two values of a Montgomery ladder step (X + Z and X - Z) that are
+  // both squared and multiplied by.  img_out must not be src; checked before the first launch.
+  virtual void square_mul_prepare(size_t src, size_t img_out, uint32_t factor) {
+    check_square_mul_prepare(src, img_out, factor);
+    set_multiplicand(img_out, src); square_mul(src, factor);
+  }
+  virtual bool square_mul_prepare_is_fused() const { return false; }
+
   // reg = reg^(2^nbits) * factor^B, B the nbits-bit integer in `bits` (most significant bit first, packed in bytes, bit 7 of a byte first):
   // one square_mul(reg, bit ? factor : 1) per bit (stage 1 of P-1: 3^E)
   virtual void square_mul_bits(size_t reg, uint32_t factor, const uint8_t* bits, size_t nbits) {
@@ -139,6 +147,10 @@ class RegisterMachine {
     need_residue(dst, "mul_sum"); need_image(src_a, "mul_sum"); need_image(src_b, "mul_sum"); need_register(tmp, "mul_sum");
     if (dst == tmp || tmp == src_a || tmp == src_b)
       throw std::runtime_error("mul_sum: dst, tmp and the multiplicands must be different registers (src_a == src_b is allowed)");
+  }
+  void check_square_mul_prepare(size_t src, size_t img_out, uint32_t factor) const {
+    need_residue(src, "square_mul_prepare"); need_register(img_out, "square_mul_prepare"); need_factor(factor, "square_mul_prepare");
+    if (img_out == src) throw std::runtime_error("square_mul_prepare: img_out must differ from src");
   }
   bool check_square_mul_bits(size_t reg, uint32_t factor, const uint8_t* bits, size_t nbits) const {   // false: nothing to do
     need_residue(reg, "square_mul_bits");

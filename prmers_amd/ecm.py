@@ -1,0 +1,371 @@
+"""ECM factoring of a Mersenne number 2^p - 1 on the engine: Montgomery curves, stages 1 and 2 (the reference: src/modes/RunEcm.cpp).
+
+    python -m prmers_amd.ecm P B1 [B2] [--sigma S] [--curves N] [--D 30|210|2310] [--plan SPEC] [--device N]
+
+Curve:    Suyama's parametrisation from sigma: u = sigma^2 - 5, v = 4 sigma, the point (u^3 : v^3) on B y^2 = x^3 + A x^2 + x with
+          a24 = (A + 2) / 4 = (v - u)^3 (3 u + v) / (16 u^3 v).  The start is taken affine, x0 = u^3 / v^3 and Z = 1: one modular inversion
+          on the host (libgmp, or pow(x, -1, N) below 2^22 bits); an inversion that fails has found a factor.
+Stage 1:  Q = E P, E = prod_{q <= B1 prime} q^floor(log_q B1), by one Montgomery ladder on x-coordinates; g1 = gcd(Z_Q, Mp).  A ladder
+          step doubles (X2 : Z2) and adds (X3 : Z3), whose difference is the start point:
+              s = X2 + Z2, d = X2 - Z2, ss = s^2, dd = d^2, t = ss - dd
+              X2' = ss dd, Z2' = t (dd + a24 t)
+              a = (X3 - Z3) s, b = (X3 + Z3) d, X3' = (a + b)^2, Z3' = x0 (a - b)^2
+          4 squarings, 6 products, and multiplicand images of s, d, dd and dd + a24 t.  s and d are both squared and multiplied by:
+          Engine.square_mul_prepare squares them and keeps the image the squaring's row sweep passes through, which saves the two
+          sweeps of a set_multiplicand for each (38 -> 34 sweeps per step; include/mi355_engine.h).  a24 and x0 stay images throughout.
+Stage 2:  the standard continuation on x-coordinates over the wheel D: every prime q in (B1, B2] is k D +- j with j in
+          J = {1 <= j < D/2, gcd(j, D) = 1} (pm1.stage2_pairs: the same cover as P-1, k = 0 included), and q | ord(Q) exactly when
+          x(k D Q) = x(j Q), so  A <- A (X_k Z_j - X_j Z_k)  with (X_j : Z_j) = j Q and (X_k : Z_k) = k D Q, all projective (no inversion);
+          g2 = gcd(A, Mp) with g1 divided out.  Baby points: the odd multiples of Q by differential addition of 2 Q; the table keeps
+          multiplicand images of X_j and of Z_j.  Giant steps: D Q and k0 D Q by short ladders on Q, then (k + 1) D Q = k D Q + D Q with
+          difference (k - 1) D Q.  Per pair: 3 products and one set_multiplicand (X_k Z_j, Z_k X_j, the image of the difference, A times
+          it).  0 Q = (1 : 0) is a valid giant point: the k = 0 terms are Z_j.
+
+The driver works on anything with the interface of prmers_amd.Engine; addsub and square_mul_prepare are used when the object has them
+and replaced by the compositions they stand for when it has not.  Not here: twisted Edwards curves, PRAC chains,
+checkpoints, ECM= worktodo lines, the PrimeNet JSON, a C++ twin.
+"""
+import argparse
+import ctypes
+import json
+import random
+import sys
+
+from .pm1 import D_CHOICES, DEFAULT_BUDGET, SLOW_GCD_BITS, big_gcd, load_gmp, primes_upto, residues, stage2_pairs
+
+# ladder points a and b, the stage-1 result Q, 2 Q, D Q, three giant points, temporaries, images, the accumulator
+(R_XA, R_ZA, R_XB, R_ZB, R_XQ, R_ZQ, R_X2, R_Z2, R_XD, R_ZD, R_XG0, R_ZG0, R_XG1, R_ZG1, R_XG2, R_ZG2,
+ R_S, R_D, R_U, R_V, R_W, R_T, R_IS, R_ID, R_IT, R_A24, R_X0, R_A) = range(28)
+FIXED_REGISTERS = 28
+SIGMA_MIN = 6                 # sigma in {0, 1, 3, 5} and a few more give degenerate curves; the customary range starts here
+
+
+# ---- integers ---------------------------------------------------------------------------------------------------------------------
+
+def stage1_exponent(b1):
+    """E = prod_{q <= B1 prime} q^floor(log_q B1)"""
+    e = 1
+    for q in primes_upto(b1):
+        qq = q
+        while qq * q <= b1:
+            qq *= q
+        e *= qq
+    return e
+
+
+def registers_needed(D):
+    """registers of an engine that runs stage 2 with this D: images of X_j and Z_j for every j in J plus FIXED_REGISTERS"""
+    if D not in D_CHOICES:
+        raise ValueError("D must be one of %s" % (D_CHOICES,))
+    return 2 * len(residues(D)) + FIXED_REGISTERS
+
+
+def choose_D(n, b1, b2, budget=DEFAULT_BUDGET):
+    """the largest D whose register file (registers_needed(D) + the engine's work buffer, 8 n bytes each) fits `budget` bytes and that is
+    not wider than the interval (B1, B2] itself"""
+    best = D_CHOICES[0]
+    for D in D_CHOICES[1:]:
+        if (registers_needed(D) + 1) * 8 * n <= budget and D <= max(b2 - b1, D_CHOICES[0]):
+            best = D
+    return best
+
+
+def mod_inverse(x, n, use_gmp=None):
+    """x^-1 mod n, or 0 when gcd(x, n) != 1: libgmp when it loads (use_gmp=None) or is asked for (True), pow(x, -1, n) otherwise -- which
+    is refused above about 2^22 bits, where it would run for hours without a word."""
+    G = load_gmp() if use_gmp in (None, True) else None
+    if use_gmp and G is None:
+        raise RuntimeError("libgmp does not load")
+    if G is None:
+        if int(n).bit_length() > SLOW_GCD_BITS:
+            raise RuntimeError("inversion modulo a %d-bit number needs libgmp (it did not load); pow(x, -1, n) would take hours at this size"
+                               % int(n).bit_length())
+        try:
+            return pow(int(x) % n, -1, n)
+        except ValueError:
+            return 0
+    P = ctypes.POINTER(G.Mpz)
+    G.__gmpz_invert.argtypes = [P, P, P]
+    G.__gmpz_invert.restype = ctypes.c_int
+    zx, zn, zr = G.Mpz(), G.Mpz(), G.Mpz()
+    for z in (zx, zn, zr):
+        G.__gmpz_init(ctypes.byref(z))
+    try:
+        for z, v in ((zx, int(x) % n), (zn, n)):
+            raw = int(v).to_bytes((int(v).bit_length() + 7) // 8 or 1, "little")
+            G.__gmpz_import(ctypes.byref(z), len(raw), -1, 1, -1, 0, raw)
+        if not G.__gmpz_invert(ctypes.byref(zr), ctypes.byref(zx), ctypes.byref(zn)):
+            return 0
+        size = (G.__gmpz_sizeinbase(ctypes.byref(zr), 2) + 7) // 8
+        buf = ctypes.create_string_buffer(size or 1)
+        count = ctypes.c_size_t(0)
+        G.__gmpz_export(buf, ctypes.byref(count), -1, 1, -1, 0, ctypes.byref(zr))
+        return int.from_bytes(buf.raw[:count.value], "little")
+    finally:
+        for z in (zx, zn, zr):
+            G.__gmpz_clear(ctypes.byref(z))
+
+
+def suyama(sigma, n, use_gmp=None):
+    """(x0, a24, 1) of the curve of `sigma` modulo n with the start point affine, or (0, 0, g) when the one inversion fails: g = gcd of
+    its argument and n, a factor of n (n itself for a degenerate sigma)"""
+    u = (sigma * sigma - 5) % n
+    v = 4 * sigma % n
+    u3, v3 = u * u * u % n, v * v * v % n
+    den = 16 * u3 * v % n                       # a24's denominator; the inverted value is den v^3
+    inv = mod_inverse(den * v3 % n, n, use_gmp)
+    if inv == 0:
+        return 0, 0, big_gcd(den * v3 % n, n, use_gmp)
+    x0 = u3 * den % n * inv % n
+    a24 = pow(v - u, 3, n) * (3 * u + v) % n * v3 % n * inv % n
+    return x0, a24, 1
+
+
+# ---- engine operations, with the compositions for objects that lack the fused ones ---------------------------------------------------
+
+class _Ops:
+    def __init__(self, eng, use_fused=True):
+        self.e = eng
+        self.squarings = self.products = self.prepares = 0
+        self.has_prepare = bool(use_fused and getattr(eng, "square_mul_prepare", None))
+        self.fused = bool(self.has_prepare and getattr(eng, "square_mul_prepare_is_fused", lambda: False)())
+        self.has_addsub = getattr(eng, "addsub", None) is not None
+
+    def sq(self, r):
+        self.e.square_mul(r)
+        self.squarings += 1
+
+    def mul(self, dst, img):
+        self.e.mul(dst, img)
+        self.products += 1
+
+    def prep(self, dst, src):
+        self.e.set_multiplicand(dst, src)
+        self.prepares += 1
+
+    def sq_prep(self, src, img):
+        """img = the image of src, src = src^2"""
+        if self.has_prepare:
+            self.e.square_mul_prepare(src, img)
+        else:
+            self.prep(img, src)
+            self.e.square_mul(src)
+        self.squarings += 1
+
+    def addsub(self, s, d, a, b):
+        """s = a + b, d = a - b; s, d, a, b four different registers"""
+        if self.has_addsub:
+            self.e.addsub(s, d, a, b)
+        else:
+            self.e.copy(s, a); self.e.add(s, b)
+            self.e.copy(d, a); self.e.sub_reg(d, b)
+
+    def sub_to(self, dst, a, b):
+        self.e.copy(dst, a); self.e.sub_reg(dst, b)
+
+
+class _Curve:
+    """x-only arithmetic on the curve whose a24 is the image in R_A24; a point is a pair of registers (X, Z)"""
+
+    def __init__(self, ops):
+        self.o, self.e = ops, ops.e
+
+    def dbl_tail(self, out):
+        """out = the double of the point whose (X + Z)^2 is in R_S and (X - Z)^2 in R_D"""
+        o, e = self.o, self.e
+        X, Z = out
+        o.sub_to(Z, R_S, R_D)                   # t = ss - dd
+        o.prep(R_IT, R_D)
+        e.copy(X, R_S); o.mul(X, R_IT)          # X' = ss dd
+        e.copy(R_W, Z); o.mul(R_W, R_A24); e.add(R_W, R_D)
+        o.prep(R_W, R_W)
+        o.mul(Z, R_W)                           # Z' = t (dd + a24 t)
+
+    def dbl(self, out, pt):
+        o = self.o
+        o.addsub(R_S, R_D, pt[0], pt[1])
+        o.sq(R_S); o.sq(R_D)
+        self.dbl_tail(out)
+
+    def add(self, out, p1, p2, diff):
+        """out = p1 + p2 where diff = p1 - p2, all projective; out may be any of them"""
+        o, e = self.o, self.e
+        o.addsub(R_U, R_V, p1[0], p1[1])
+        o.addsub(R_S, R_D, p2[0], p2[1])
+        o.prep(R_IS, R_S); o.prep(R_ID, R_D)
+        o.mul(R_V, R_IS); o.mul(R_U, R_ID)      # a = (X1 - Z1)(X2 + Z2), b = (X1 + Z1)(X2 - Z2)
+        o.addsub(R_S, R_D, R_V, R_U)
+        o.sq(R_S); o.sq(R_D)
+        o.prep(R_IT, diff[1]); o.mul(R_S, R_IT)  # X' = Zd (a + b)^2
+        o.prep(R_IT, diff[0]); o.mul(R_D, R_IT)  # Z' = Xd (a - b)^2
+        e.copy(out[0], R_S); e.copy(out[1], R_D)
+
+    def ladder_step(self, a, b):
+        """a = 2 a, b = a + b, where b - a is the start point (x0 : 1) whose x0 is the image in R_X0"""
+        o = self.o
+        o.addsub(R_S, R_D, a[0], a[1])
+        o.addsub(R_U, R_V, b[0], b[1])
+        o.sq_prep(R_S, R_IS); o.sq_prep(R_D, R_ID)
+        o.mul(R_V, R_IS); o.mul(R_U, R_ID)
+        o.addsub(b[0], b[1], R_V, R_U)
+        o.sq(b[0]); o.sq(b[1]); o.mul(b[1], R_X0)
+        self.dbl_tail(a)
+
+    def small_ladder(self, r0, r1, m, pt):
+        """(r0, r1) = (m pt, (m + 1) pt), m >= 1, pt projective and none of r0, r1"""
+        self.e.copy(r0[0], pt[0]); self.e.copy(r0[1], pt[1])
+        self.dbl(r1, pt)
+        for i in range(m.bit_length() - 2, -1, -1):
+            if (m >> i) & 1:
+                self.add(r0, r0, r1, pt); self.dbl(r1, r1)
+            else:
+                self.add(r1, r0, r1, pt); self.dbl(r0, r0)
+
+
+def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None):
+    """One curve of ECM on 2^p - 1 with bounds B1 and B2 (B2 <= B1: stage 1 only) on `eng`, an engine for exponent p with at least
+    FIXED_REGISTERS registers (stage 1) or registers_needed(D) (stage 2).  use_fused=False forces set_multiplicand + square_mul in
+    place of square_mul_prepare.  Afterwards registers R_XQ, R_ZQ hold the stage-1 point.
+    -> {p, b1, b2, D, sigma, factors, g1, g2, squarings, products, prepares, fused}"""
+    if b1 < 2:
+        raise ValueError("B1 must be at least 2")
+    if sigma < SIGMA_MIN:
+        raise ValueError("sigma must be at least %d" % SIGMA_MIN)
+    mp = (1 << p) - 1
+    have = getattr(eng, "reg_count", None)
+    stage2 = b2 > b1
+    if stage2:
+        if D is None:
+            D = max([d for d in D_CHOICES if have is None or registers_needed(d) <= have] or [0])
+            D = min(D, choose_D(eng.n, b1, b2)) if D else 0
+        if D not in D_CHOICES:
+            raise ValueError("stage 2 needs D in %s and an engine with registers_needed(D) registers" % (D_CHOICES,))
+    need = registers_needed(D) if stage2 else FIXED_REGISTERS
+    if have is not None and have < need:
+        raise ValueError("the engine has %d registers, ECM with D = %s needs %d" % (have, D if stage2 else None, need))
+    ops = _Ops(eng, use_fused)
+    cv = _Curve(ops)
+
+    def result(g1, g2):
+        return {"p": p, "b1": b1, "b2": b2 if stage2 else 0, "D": D if stage2 else None, "sigma": sigma,
+                "factors": [f for f in (g1, g2) if 1 < f < mp], "g1": g1, "g2": g2,
+                "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused}
+
+    x0, a24, g = suyama(sigma, mp, use_gmp)
+    if g != 1:
+        return result(g, 1)      # the inversion failed: its argument shares g with Mp
+
+    # ---- stage 1 ----
+    e = stage1_exponent(b1)
+    if stage2:   # the primes in (B1, B2] that divide D have no residue class in stage 2
+        for q in (2, 3, 5, 7, 11):
+            if D % q == 0 and b1 < q <= b2:
+                e *= q
+    eng.set_int(R_A24, a24); ops.prep(R_A24, R_A24)
+    eng.set_int(R_X0, x0); ops.prep(R_X0, R_X0)
+    a, b = (R_XA, R_ZA), (R_XB, R_ZB)
+    eng.set_int(R_XA, x0); eng.set(R_ZA, 1)
+    cv.dbl(b, a)                                 # (a, b) = (P, 2 P)
+    for i in range(e.bit_length() - 2, -1, -1):
+        if (e >> i) & 1:
+            cv.ladder_step(b, a)
+        else:
+            cv.ladder_step(a, b)
+    Q = (R_XQ, R_ZQ)
+    eng.copy(R_XQ, a[0]); eng.copy(R_ZQ, a[1])
+    z = eng.get_int(R_ZQ)
+    g1 = mp if z == 0 else big_gcd(z, mp, use_gmp)
+    g2 = 1
+
+    # ---- stage 2 ----
+    if stage2 and g1 != mp:
+        J = residues(D)
+        slot = {j: (FIXED_REGISTERS + 2 * i, FIXED_REGISTERS + 2 * i + 1) for i, j in enumerate(J)}
+        pairs = stage2_pairs(b1, b2, D)
+        if pairs:
+            two = (R_X2, R_Z2)
+            cv.dbl(two, Q)
+            # baby points: the odd multiples of Q; cur = j Q, prev = (j - 2) Q ((-1) Q has the x of Q)
+            prev, cur, nxt = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
+            for r in (0, 1):
+                eng.copy(prev[r], Q[r]); eng.copy(cur[r], Q[r])
+            for j in range(1, J[-1] + 1, 2):
+                if j in slot:
+                    ops.prep(slot[j][0], cur[0]); ops.prep(slot[j][1], cur[1])
+                if j + 2 <= J[-1]:
+                    cv.add(nxt, cur, two, prev)
+                    prev, cur, nxt = cur, nxt, prev
+            # giant steps: cur = k D Q, nxt = (k + 1) D Q
+            DQ = (R_XD, R_ZD)
+            cv.small_ladder(DQ, (R_XG0, R_ZG0), D, Q)
+            k0, k1 = min(pairs), max(pairs)
+            cur, nxt, spare = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
+            if k0 == 0:
+                eng.set(cur[0], 1); eng.set(cur[1], 0)
+                eng.copy(nxt[0], DQ[0]); eng.copy(nxt[1], DQ[1])
+            else:
+                cv.small_ladder(cur, nxt, k0, DQ)
+            eng.set(R_A, 1)
+            for k in range(k0, k1 + 1):
+                for j in pairs.get(k, ()):
+                    eng.copy(R_T, cur[0]); ops.mul(R_T, slot[j][1])      # X_k Z_j
+                    eng.copy(R_W, cur[1]); ops.mul(R_W, slot[j][0])      # Z_k X_j
+                    eng.sub_reg(R_T, R_W)
+                    ops.prep(R_T, R_T)
+                    ops.mul(R_A, R_T)
+                if k + 1 < k1:
+                    if k == 0:
+                        cv.dbl(spare, DQ)        # the difference would be 0 Q
+                    else:
+                        cv.add(spare, nxt, DQ, cur)
+                    cur, nxt, spare = nxt, spare, cur
+                else:
+                    cur, nxt = nxt, cur
+            acc = eng.get_int(R_A)
+            g = mp if acc == 0 else big_gcd(acc, mp, use_gmp)
+            g2 = g // big_gcd(g, g1, use_gmp)
+    return result(g1, g2)
+
+
+def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0):
+    """`curves` curves of run() on a fresh prmers_amd.Engine sized for the chosen D, until one finds a factor.  sigma: the first curve's
+    (None: drawn like the others, from random.Random(seed)).  -> the result of the last curve run, with "sigmas": every sigma used."""
+    from .engine import Engine, resolve_plan
+    if b2 > b1 and D is None:
+        n = int(resolve_plan(p, plan).split("n=")[1].split(":")[0])
+        D = choose_D(n, b1, b2, budget)
+    regs = registers_needed(D) if b2 > b1 else FIXED_REGISTERS
+    rng = random.Random(seed)
+    sigmas = []
+    res = None
+    with Engine(p, regs, device=device, plan=plan) as eng:
+        for c in range(max(1, curves)):
+            s = sigma if (c == 0 and sigma is not None) else rng.randrange(SIGMA_MIN, 1 << 32)
+            sigmas.append(s)
+            res = run(eng, p, b1, b2, s, D)
+            if res["factors"]:
+                break
+    res["sigmas"] = sigmas
+    return res
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m prmers_amd.ecm", description="ECM factoring of 2^P - 1 (Montgomery curves, stages 1 and 2) on an MI355X")
+    ap.add_argument("p", type=int)
+    ap.add_argument("b1", type=int)
+    ap.add_argument("b2", type=int, nargs="?", default=0)
+    ap.add_argument("--sigma", type=int, default=None, help="Suyama parameter of the first curve (default: drawn from the seeded generator)")
+    ap.add_argument("--curves", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--D", type=int, choices=D_CHOICES, default=None, help="stage-2 wheel (default: the largest whose register file fits --budget-gib)")
+    ap.add_argument("--budget-gib", type=float, default=DEFAULT_BUDGET / 2**30)
+    ap.add_argument("--plan", default=None)
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed)
+    print(json.dumps(res))
+    return 0 if res["factors"] else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -81,6 +81,8 @@ def load_library():
         "mi355_engine_mul_sum": (C.c_int, [vp, sz, sz, sz, sz]),
         "mi355_engine_mul_sum_is_fused": (C.c_int, [vp]),
         "mi355_engine_square_mul_bits": (C.c_int, [vp, sz, u32, C.c_char_p, sz]),
+        "mi355_engine_square_mul_prepare": (C.c_int, [vp, sz, sz, u32]),
+        "mi355_engine_square_mul_prepare_is_fused": (C.c_int, [vp]),
         "mi355_crt_carry": (C.c_int, [u32, sz, u32, u32, vp, vp, vp, vp, sz, dp]),
         "mi355_crt_transform_size": (sz, [u32, u32]),
         "mi355_engine_describe": (C.c_int, [vp, C.c_char_p, sz]),
@@ -108,6 +110,7 @@ EXPORTS = [
     "mi355_engine_addsub", "mi355_engine_addsub_copy", "mi355_engine_mul_add", "mi355_engine_square_mul_copy", "mi355_engine_mul_copy", "mi355_engine_square_mul_n",
     "mi355_engine_exp_mul", "mi355_engine_exp_mul2",
     "mi355_engine_mul_sum", "mi355_engine_mul_sum_is_fused", "mi355_engine_square_mul_bits",
+    "mi355_engine_square_mul_prepare", "mi355_engine_square_mul_prepare_is_fused",
 ]
 
 
@@ -224,6 +227,14 @@ class Engine:
         if nbits < 0 or nbits > 8 * len(bits):
             raise ValueError("nbits = %d does not fit the %d bytes given" % (nbits, len(bits)))
         self._ok(self.L.mi355_engine_square_mul_bits(self.h, reg, u32_arg("factor", factor), bits, nbits))
+
+    def square_mul_prepare(self, src, img_out, a=1):
+        """img_out = the multiplicand image of src, then src = src^2 * a: one squaring whose row sweep keeps the transform of its operand."""
+        self._ok(self.L.mi355_engine_square_mul_prepare(self.h, src, img_out, u32_arg("factor", a)))
+
+    def square_mul_prepare_is_fused(self):
+        """True if square_mul_prepare runs as one squaring (False: set_multiplicand + square_mul, same result)"""
+        return bool(self.L.mi355_engine_square_mul_prepare_is_fused(self.h))
 
     def is_equal(self, lhs, rhs):
         out = C.c_int(0)
