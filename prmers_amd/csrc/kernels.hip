@@ -330,16 +330,13 @@ __global__ void __launch_bounds__(1024) k_front(DevPlan pl, const uint32_t* __re
 // mode 4 (KEEP, k_middle_keep): mode 0 that also stores the forward transform of the operand to Wimg, as mode 2 would store it.
 // ---------------------------------------------------------------------------------------------
 template <bool KEEP = false>
-__device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* Win, const uint64_t* Yimg, const uint64_t* Yimg2, uint64_t* Wout, int mode, uint32_t sub, uint32_t row,
+__device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* Win, const uint64_t* Yimg, const uint64_t* Yimg2, uint64_t* Wout, int mode, uint32_t row,
                                             P2* X, uint32_t tid, uint32_t nthr, uint64_t* Wimg = nullptr) {
   const uint32_t M2 = pl.M2;
   const P2* in = reinterpret_cast<const P2*>(Win) + size_t(row) * M2;
   P2* out = reinterpret_cast<P2*>(Wout) + size_t(row) * M2;
 
   for (uint32_t e = tid; e < M2; e += nthr) X[e] = in[e];
-  __syncthreads();
-  // deferred small subtraction on a front image (digit 0 -> column 0, plane a of every row, weight 1)
-  if (sub != 0 && tid == 0) X[0].a = gf::sub(X[0].a, uint64_t(sub));
   __syncthreads();
   const uint32_t k1 = freq1(pl, row);
   const bool one = M2 <= nthr;   // one element per thread: its twiddle words are requested before the transform (see k_front)
@@ -382,11 +379,11 @@ __device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* W
   for (uint32_t e = tid; e < M2; e += nthr) out[e] = X[e];
 }
 __global__ void __launch_bounds__(1024) k_middle(DevPlan pl, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Yimg,
-                                                const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout, int mode, uint32_t sub) {
-  middle_body(pl, Win, Yimg, Yimg2, Wout, mode, sub, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
+                                                const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout, int mode) {
+  middle_body(pl, Win, Yimg, Yimg2, Wout, mode, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
 }
-__global__ void __launch_bounds__(1024) k_middle_keep(DevPlan pl, const uint64_t* __restrict__ Win, uint64_t* __restrict__ Wimg, uint64_t* __restrict__ Wout, uint32_t sub) {
-  middle_body<true>(pl, Win, nullptr, nullptr, Wout, 0, sub, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x, Wimg);
+__global__ void __launch_bounds__(1024) k_middle_keep(DevPlan pl, const uint64_t* __restrict__ Win, uint64_t* __restrict__ Wimg, uint64_t* __restrict__ Wout) {
+  middle_body<true>(pl, Win, nullptr, nullptr, Wout, 0, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x, Wimg);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -748,8 +745,8 @@ hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_
 }
 hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s) {
   if (mode < 0 || mode > 4) return hipErrorInvalidValue;
-  if (mode == 4) hipLaunchKernelGGL(k_middle_keep, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Wimg, Wout, 0u);
-  else hipLaunchKernelGGL(k_middle, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Y, Y2, Wout, mode, 0u);
+  if (mode == 4) hipLaunchKernelGGL(k_middle_keep, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Wimg, Wout);
+  else hipLaunchKernelGGL(k_middle, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Y, Y2, Wout, mode);
   return hipGetLastError();
 }
 hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s) {

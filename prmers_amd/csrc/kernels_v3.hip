@@ -29,6 +29,7 @@ namespace mi355 {
 namespace v3 {
 using v2::P2;
 using v2::lds_barrier;
+using v2::mulw;
 
 constexpr uint32_t kThreads = 256;   // thread indices t of a tile (lanes: see the forms)
 constexpr uint32_t kLdsBytes = 1024 * 16;
@@ -71,8 +72,6 @@ __device__ __forceinline__ void dft4(P2 (&x)[4]) {
 }
 template <bool INV>
 __device__ __forceinline__ void dft4(uint64_t (&x)[4]) { v2::dft4<INV>(x[0], x[1], x[2], x[3]); }
-__device__ __forceinline__ P2 mulw(P2 x, uint64_t w) { return v2::p2_mul(x, w); }
-__device__ __forceinline__ uint64_t mulw(uint64_t x, uint64_t w) { return gf::mul(x, w); }
 template <class E>
 __device__ __forceinline__ void twiddle3(E (&x)[4], const uint64_t (&w)[3]) {
 #pragma unroll
@@ -288,12 +287,6 @@ __device__ __forceinline__ void cols_inverse(const Form& f, typename Form::E (&x
   inverse3(f, x, v);
   exchange<idx_a, idx_e, Form::edge>(f, x);
 }
-// the eight digits of run t of tile T
-__device__ __forceinline__ void load_run(const uint32_t* __restrict__ digits, uint32_t T, uint32_t t, uint32_t (&dg)[8]) {
-  const uint4* src = reinterpret_cast<const uint4*>(digits) + (size_t(T) * 256 + t) * 2;
-  const uint4 a = src[0], b = src[1];
-  dg[0] = a.x; dg[1] = a.y; dg[2] = a.z; dg[3] = a.w; dg[4] = b.x; dg[5] = b.y; dg[6] = b.z; dg[7] = b.w;
-}
 // the four-step chain over the thread's four rows: x[j] *= ca ratio^j
 template <class E>
 __device__ __forceinline__ void chain4(E (&x)[4], uint64_t ca, uint64_t ratio) {
@@ -304,13 +297,8 @@ __device__ __forceinline__ void chain4(E (&x)[4], uint64_t ca, uint64_t ratio) {
   }
 }
 
-// digits -> weighted elements.  Weight TA*TB, halved when the exponents wrap: the halving sits on TA (tah: odd digits with the exponent
-// split SA[M1 + i1] + SB[2 i2], plan.hpp) and the un-wrapped digits are doubled instead (bit 2 idx + 1 of ~nowrap: digit idx wrapped)
-__device__ __forceinline__ void weigh(const Pairs&, P2 tah, uint32_t nowrap, const uint32_t (&dg)[8], P2 (&x)[4]) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-    x[c] = {gf::mul_u32(tah.a, dg[2 * c] << ((nowrap >> (4 * c + 1)) & 1u)), gf::mul_u32(tah.b, dg[2 * c + 1] << ((nowrap >> (4 * c + 3)) & 1u))};
-}
+// digits -> weighted elements (v2::weigh_run; Planes: the same weights, this lane's plane of each pair)
+__device__ __forceinline__ void weigh(const Pairs&, P2 tah, uint32_t nowrap, const uint32_t (&dg)[8], P2 (&x)[4]) { v2::weigh_run<8>(tah.a, tah.b, nowrap, 0, dg, x); }
 __device__ __forceinline__ void weigh(const Planes& f, uint64_t tah, uint32_t nowrap, const uint32_t (&dg)[8], uint64_t (&x)[4]) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -334,7 +322,7 @@ __global__ void __launch_bounds__(Form::kBlock) k1_cols256(DevPlan pl, const uin
   const uint32_t di = pl.DI[size_t(T) * kThreads + t];
   const E tah = f.halves(pl.TAh);
   uint32_t dg[8];
-  load_run(digits, T, t, dg);
+  v2::load_run(digits, size_t(T) * kThreads + t, dg);
   // compiler fence: the requests above stay at the kernel's entry (otherwise the table words move below the carry-in branch, behind the
   // wait for the digits, and the weights cost a second memory round trip)
   asm volatile("" ::: "memory");
@@ -371,23 +359,9 @@ __device__ __forceinline__ void unweigh(const Planes& f, uint32_t di, uint64_t t
 #pragma unroll
   for (int k = 0; k < 8; ++k) u[k] = ((k & 1) == int(f.pln)) ? own[k >> 1] : oth[k >> 1];
 }
-// one digit of the carry chain: u a + addend + carry -> digit of `width` bits, carry (adc_mul, marin.cl:194-201)
-__device__ __forceinline__ uint32_t adc_mul(uint64_t u, uint32_t a, uint32_t addend, uint32_t width, uint64_t& carry) {
-  if (a == 1) {
-    const uint64_t r = u + carry + addend;
-    carry = r >> width;
-    return __builtin_amdgcn_ubfe(uint32_t(r), 0u, width);
-  }
-  const uint64_t mask = (uint64_t(1) << width) - 1;
-  const uint64_t dlo = u & mask, chi = u >> width;
-  const uint64_t r = dlo * a + carry + addend;
-  carry = (r >> width) + chi * a;
-  return uint32_t(r & mask);
-}
 // digits and carry word of run `run`; Planes: lane a stores the first four digits (and the carry word), lane b the last four
 __device__ __forceinline__ void store_run(const Pairs&, uint32_t* __restrict__ digits, uint64_t* __restrict__ cbuf, size_t run, const uint32_t (&dg)[8], uint64_t carry) {
-  uint4* dst = reinterpret_cast<uint4*>(digits) + run * 2;
-  dst[0] = make_uint4(dg[0], dg[1], dg[2], dg[3]); dst[1] = make_uint4(dg[4], dg[5], dg[6], dg[7]);
+  v2::store_run(digits, run, dg);
   cbuf[run] = carry;
 }
 __device__ __forceinline__ void store_run(const Planes& f, uint32_t* __restrict__ digits, uint64_t* __restrict__ cbuf, size_t run, const uint32_t (&dg)[8], uint64_t carry) {
@@ -415,7 +389,7 @@ __global__ void __launch_bounds__(Form::kBlock) k3_cols256(DevPlan pl, const uin
   for (int j = 0; j < 4; ++j) x[j] = W[f.at(size_t(row0 + rev2(j)) * pl.M2 + i2)];
   uint32_t ad[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (EXT && ext.add_digits) {
-    load_run(ext.add_digits, T, t, ad);
+    v2::load_run(ext.add_digits, size_t(T) * kThreads + t, ad);
     if (ext.add_cbuf) v2::apply_carry_in<8>(pl, di, 0, v2::carry_in_of(pl, ext.add_cbuf, T, t), ad);
   }
   chain4(x, ca, B);
@@ -426,7 +400,7 @@ __global__ void __launch_bounds__(Form::kBlock) k3_cols256(DevPlan pl, const uin
   uint64_t carry = 0;
   uint32_t dg[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) dg[k] = adc_mul(u[k], a, EXT ? ad[k] : 0u, pl.q + ((di >> (2 * k)) & 1u), carry);
+  for (int k = 0; k < 8; ++k) dg[k] = v2::adc_mul(u[k], a, EXT ? ad[k] : 0u, pl.q + ((di >> (2 * k)) & 1u), carry);
   store_run(f, digits, cbuf, size_t(T) * 256 + t, dg, carry);
   if (EXT && ext.digits2) store_run(f, ext.digits2, ext.cbuf2, size_t(T) * 256 + t, dg, carry);
 }

@@ -154,16 +154,16 @@ inline bool sum_product_ok(uint32_t q, size_t n, uint32_t C) { return carry_chai
 enum class ColKernels : uint8_t {
   kGeneric,                      // kernels.hip k_front, k_back<EXT>: every shape whose columns fit LDS
   kSplit,                        // kernels.hip k_front_split_a/b, k_back_split_a/b: columns of 5 L1 pairs beyond LDS (split5)
-  kRadix8R1, kRadix8R2, kRadix8R4,   // kernels_v2.hip k1_cols<R>, k3_cols<R>, k3_cols_ext<R>: M1 = 512 R, M1 C = 4096
+  kRadix8R1, kRadix8R2, kRadix8R4,   // kernels_v2.hip k1_cols<R>, k3_cols<R, EXT>: M1 = 512 R, M1 C = 4096
   kRadix4Pairs, kRadix4Planes,   // kernels_v3.hip k1_cols256<Form>, k3_cols256<Form, EXT>: 256 x 4
   kRadix5, kRadix5J1,            // kernels_v5.hip k1_cols5<J>, k3_cols5<J, EXT>: 1280 x 4 (J = 0), 2560 x 2 (J = 1)
 };
 enum class RowKernels : uint8_t {
   kGeneric,                      // kernels.hip k_middle
   kRadix4Pairs, kRadix4Planes,   // kernels_v3.hip k2_rows1024<Form, mode>: rows of 1024
-  kRadix8,                       // kernels_v2.hip k2_rows4096<mode, 1>: rows of 4096
-  kRadix8Wide,                   // k2_rows4096<mode, 2>: rows of 8192 as two 4096-point halves, 1024 threads
-  kRows2048One, kRows2048Two,    // k2_rows2048_planes<mode> (one row per tile), k2_rows4096<mode, 1, 1> (two rows per tile)
+  kRadix8,                       // kernels_v2.hip k2_rows<Pairs, mode, 1, 0>: rows of 4096
+  kRadix8Wide,                   // k2_rows<Pairs, mode, 2, 0>: rows of 8192 as two 4096-point halves, 1024 threads
+  kRows2048One, kRows2048Two,    // k2_rows<Planes, mode, 1, 1> (one row per tile), k2_rows<Pairs, mode, 1, 1> (two rows per tile)
 };
 
 struct KernelChoice {

@@ -1,5 +1,5 @@
 // Device self-test of the arithmetic the kernels are built from: the GF(P) primitives (gf.hpp, gfdft.hpp), their consumers in the radix-8 kernels
-// (kernels_v2_common.hpp: dft8p, seam64, p2_mul, dft4) and the second field family (crt_field.hpp, crt_arith.hpp).  The device code paths differ
+// (kernels_v2_common.hpp: dft8p, seam, p2_mul, dft4) and the second field family (crt_field.hpp, crt_arith.hpp).  The device code paths differ
 // from the host ones (inline-assembly reductions, borrow-reusing sub, P left for a negated zero; intrinsics and 64-bit shifts in the second family),
 // so the case families of selftest_cases.hpp are evaluated on the GPU itself, one lane per case, and checked against 128-bit host arithmetic --
 // the second family also word for word against the host evaluation of the same templates.  Reached through mi355_engine_selftest().
@@ -34,7 +34,7 @@ __global__ void k_selftest_dft4(const uint64_t* __restrict__ in, uint64_t* __res
   for (int j = 0; j < 4; ++j) { out[size_t(i) * 8 + j] = f[j]; out[size_t(i) * 8 + 4 + j] = g[j]; }
 }
 
-// eight waves to a work-group, the wave index made scalar as the kernels do, so that seam64's switch is taken wave-uniformly
+// eight waves to a work-group, the wave index made scalar as the kernels do, so that the switch of seam is taken wave-uniformly
 __global__ void __launch_bounds__(512) k_selftest_chain(const uint64_t* __restrict__ tuples, size_t ntuples, const uint64_t* __restrict__ fac, uint64_t* __restrict__ out) {
   const int g = blockIdx.x * 512 + threadIdx.x;
   const uint32_t wave = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) & 7);
@@ -45,12 +45,12 @@ __global__ void __launch_bounds__(512) k_selftest_chain(const uint64_t* __restri
   uint64_t sw[8];
   for (int k = 0; k < 8; ++k) { x[k] = y[k] = {ta[k], tb[k]}; sw[k] = fac[size_t(g) * 8 + k]; }
   v2::dft8p<false, 1>(x);
-  v2::seam64<false, true>(x, wave);
+  v2::seam<6, false, true>(x, wave);
   for (int k = 0; k < 8; ++k) { o[k] = x[k].a; o[8 + k] = x[k].b; }
   v2::dft8p<false, 2>(x);
   for (int k = 0; k < 8; ++k) { x[k] = v2::p2_mul(x[k], sw[k]); o[16 + k] = x[k].a; o[24 + k] = x[k].b; }
   v2::dft8p<true>(y);
-  v2::seam64<true>(y, wave);
+  v2::seam<6, true>(y, wave);
   v2::dft8p<true, 2>(y);
   for (int k = 0; k < 8; ++k) { y[k] = v2::p2_mul(y[k], sw[k]); o[32 + k] = y[k].a; o[40 + k] = y[k].b; }
 }

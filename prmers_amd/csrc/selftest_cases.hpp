@@ -267,11 +267,11 @@ struct GfDft4 {
   }
 };
 
-// The consumers of the lazy butterfly outputs, as the radix-8 kernels chain them (kernels_v2.hip, k2_rows4096; device only, evaluated by selftest.hip
+// The consumers of the lazy butterfly outputs, as the radix-8 kernels chain them (kernels_v2.hip, k2_rows; device only, evaluated by selftest.hip
 // with eight waves to a work-group).  Thread g (wave w = g / 64 mod 8) takes the tuples tuple_of(g, 0) (plane a) and tuple_of(g, 1) (plane b) of GfDft8's list and
 // eight factors (table-like: canonical) and returns, plane a then plane b, eight slots each:
-//   forward:  dft8p<false, 1>, seam64<false, true>(w)  -> out[0..15];   then dft8p<false, 2>, p2_mul by the factors -> out[16..31]
-//   inverse:  dft8p<true>, seam64<true>(w), dft8p<true, 2>, p2_mul by the factors -> out[32..47]
+//   forward:  dft8p<false, 1>, seam<6, false, true>(w)  -> out[0..15];   then dft8p<false, 2>, p2_mul by the factors -> out[16..31]
+//   inverse:  dft8p<true>, seam<6, true>(w), dft8p<true, 2>, p2_mul by the factors -> out[32..47]
 struct GfChain {
   static constexpr int OUT = 48, kThreads = 512 * 8;
   static void factors(std::vector<uint64_t>& f) {
@@ -302,7 +302,7 @@ struct GfChain {
             if (!inv) {
               const uint64_t s1 = o[8 * plane + k];   // after the seam every slot is folded: shifted (<= P), or folded by FOLD0 at wave 0
               if (s1 % P != b[k] || s1 > P)
-                return msg("gf chain forward, after seam64 at wave %d, slot %d: got %016llx want %016llx (tuple %zu)", w, k, MI355_X(s1), MI355_X(b[k]), tu);
+                return msg("gf chain forward, after seam<6> at wave %d, slot %d: got %016llx want %016llx (tuple %zu)", w, k, MI355_X(s1), MI355_X(b[k]), tu);
             }
             const uint64_t r = o[(inv ? 32 : 16) + 8 * plane + k];
             if (r != want) return msg("gf chain %s, after the multiplication, wave %d slot %d: got %016llx want %016llx (tuple %zu)", inv ? "inverse" : "forward", w, k, MI355_X(r), MI355_X(want), tu);
@@ -312,7 +312,7 @@ struct GfChain {
       }
     }
     for (int k : {1, 2, 3, 5})
-      if (!folded[k]) return msg("gf chain: wave 0 (the FOLD0 case of seam64) met no value above P in slot %d", k);
+      if (!folded[k]) return msg("gf chain: wave 0 (the FOLD0 case of seam<6>) met no value above P in slot %d", k);
     return "";
   }
 };

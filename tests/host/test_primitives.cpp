@@ -71,12 +71,12 @@ int main(){
     if (!e1.empty()) { bad++; printf("%s\n", e1.c_str()); }
     if (!e2.empty()) { bad++; printf("%s\n", e2.c_str()); }
     // v2::dft4 is device-only; its direct sums are checked by the self-test.  mul_pow2(a, 0) is the one call that passes its operand through
-    // un-folded: among the shifts of seam64_const (slot k = 1..7 at wave w, both directions) a zero occurs for wave 0 only -- the case that
-    // seam64's FOLD0 folds by hand
+    // un-folded: among the shifts of seam_const<6> (slot k = 1..7 at wave w, both directions) a zero occurs for wave 0 only -- the case that
+    // seam<6>'s FOLD0 folds by hand
     for (int w = 0; w < 8; ++w) for (int k = 1; k < 8; ++k) for (int inv = 0; inv < 2; ++inv) {
       const unsigned s = GfChain::seam_shift(k, w, inv != 0);
-      if (s >= 192 || (s == 0) != (w == 0)) { bad++; printf("seam64 shift of slot %d at wave %d is %u\n", k, w, s); }
-      if (gf::pow(2, s) != gf::pow(gf::root_of_unity(64), inv ? 64 - (k * w) % 64 : (k * w) % 64)) { bad++; printf("seam64 shift of slot %d at wave %d is not omega_64^(k w)\n", k, w); }
+      if (s >= 192 || (s == 0) != (w == 0)) { bad++; printf("seam<6> shift of slot %d at wave %d is %u\n", k, w, s); }
+      if (gf::pow(2, s) != gf::pow(gf::root_of_unity(64), inv ? 64 - (k * w) % 64 : (k * w) % 64)) { bad++; printf("seam<6> shift of slot %d at wave %d is not omega_64^(k w)\n", k, w); }
     }
   }
   printf(bad? "FAIL %d\n":"OK %d\n", bad); return bad!=0;

@@ -36,7 +36,7 @@ SMALL_CASES = [
     # their own rows of 1024: p = 9815459 below), rows of 1024 over generic columns of 8 .. 64
     (86243, "m2=8,c=4"), (132049, "m2=16,c=4"), (300007, "m2=32,c=4"), (756839, "m2=64,c=4"),
     (300007, "m2=1024"), (600011, "m2=1024"), (1200007, "m2=1024,c=4"), (2976221, "m2=1024"),
-    # rows of 2048 with one plane per thread (kernels_v2.hip k2_rows2048_planes: fewer than 512 rows) over generic and radix-4 columns
+    # rows of 2048 with one plane per thread (kernels_v2.hip k2_rows<Planes>: fewer than 512 rows) over generic and radix-4 columns
     (300007, "m2=2048"), (600011, "m2=2048"), (1200007, "m2=2048,c=4"), (2976221, "m2=2048"), (4800007, "m2=2048,c=4"),
     # columns of 1280 = 5 x 256 on the register-resident radix-5 kernels (640 threads per tile), generic and radix-8 rows
     (400063, "m2=8,c=4"), (800283, "m2=16,c=4"), (1600589, "m2=32,c=4"),
@@ -283,7 +283,7 @@ RADIX4_FULL = [(9815459, 1 << 19, None), (4800007, 1 << 18, None), (50000017, 5 
 def test_radix4_set_full_size_operations(p, n, plan):
     """The shapes of the register-resident radix-4 kernels at full-size digits (kernels_v3.hip): C2 (columns of 256 x 4 + rows of 1024),
     n = 2^18 (rows of 1024 over generic columns of 128), n = 5 2^19 (rows of 1024 under the radix-5 columns), n = 2^20 (columns of
-    256 x 4 around the plane-per-thread rows of 2048, kernels_v2.hip k2_rows2048_planes) and n = 2^21 forced to columns of 256 x 4 under
+    256 x 4 around the plane-per-thread rows of 2048, kernels_v2.hip k2_rows<Planes>) and n = 2^21 forced to columns of 256 x 4 under
     rows of 4096 (the smallest shape that selects the pair-per-thread form of the column kernels: more than 512 tiles): squarings with a
     factor, the LL step (sub between two squarings), set_multiplicand / mul (forward-only and multiply modes of the row
     kernel), the fused back sweeps (mul_add, square_mul_copy) -- digit vectors against the oracle."""
@@ -346,7 +346,7 @@ def test_c3_136279841_full_size():
 def test_rows_of_2048_two_to_a_tile(p, plan, shape, monkeypatch):
     """rows of 2048 on the register-resident row kernels: n = 2^21 with register-resident and with generic columns, two rows per 4096-pair
     tile (kernels_v2.hip, RL = 1; the reference's forward1024 / sqr512 shapes, kernels/marin.cl:1190,1517), and n = 5 2^20 (p ~ 100 M,
-    M1 = 1280) with the radix-5 columns, one row per tile (k2_rows2048_planes) -- squarings, x a, the LL step, multiplicand and mul
+    M1 = 1280) with the radix-5 columns, one row per tile (k2_rows<Planes>) -- squarings, x a, the LL step, multiplicand and mul
     against the oracle's digits, and against the generic rows (MI355_KERNELS=v2cols: the same columns) on the same inputs."""
     o = orc.Oracle(p, 3)
     rng = np.random.default_rng(p)
@@ -562,11 +562,11 @@ def test_device_selftest_of_field_primitives():
     - dft8<INV, LAZY> for both directions and LAZY = 0, 1, 2 on tuples over an alphabet of values around 0, 2^32, 2^63, P (and P itself)
       against the direct 8-point sums; slots that gfdft.hpp calls canonical are <= P, and for every slot that may be lazy at least one device
       output was above P, else the self-test fails naming the slot;
-    - the consumers as k2_rows4096 chains them, with eight waves: dft8p<false, 1>, seam64<false, true> (folded at wave 0), dft8p<false, 2>,
-      p2_mul; dft8p<true>, seam64<true>, dft8p<true, 2>, p2_mul -- products are canonical; v2::dft4 on every 4-tuple of the alphabet;
+    - the consumers as k2_rows chains them, with eight waves: dft8p<false, 1>, seam<6, false, true> (folded at wave 0), dft8p<false, 2>,
+      p2_mul; dft8p<true>, seam<6, true>, dft8p<true, 2>, p2_mul -- products are canonical; v2::dft4 on every 4-tuple of the alphabet;
     - the second field family: scalars, cmul61 / cmul31, bfly61 and bfly<F, R, INV>, dft_odd, DigitWalk -- the cases of
       tests/host/test_crt_primitives.cpp, compared with the host evaluation word for word and with the 128-bit sums.
-    Out of scope: the file-local dft5 / dft5p, seam_rows*, seam64w*, seam32w* of the kernel sources (moving them into headers is a refactor of
+    Out of scope: the file-local dft5 / dft5p of the kernel sources and the word and 32-point forms of seam (moving them here is a refactor of
     its own); they are covered by the whole-engine tests only."""
     from prmers_amd.engine import load_library
     L = load_library()

@@ -21,7 +21,7 @@ def _build_and_run(src, args=()):
 def test_field_primitives_and_dft8():
     """gf::mul / mul_u32 / mul_pow2 (all 192 shifts) / dft8 against 128-bit reference arithmetic; every function over its documented operand
     domain (lazy operands anywhere in [0, 2^64)), dft8<INV, LAZY> on tuples over the edge alphabet with an un-folded value seen in every slot
-    that may hold one, and the shifts of seam64 (zero for wave 0 only)."""
+    that may hold one, and the shifts of seam<6> (zero for wave 0 only)."""
     out = _build_and_run("test_primitives.cpp")
     assert out.strip().startswith("OK"), out
 

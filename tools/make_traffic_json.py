@@ -11,7 +11,7 @@ crt = len(sys.argv) > 3 and sys.argv[3] == "crt"
 d = json.load(open(src))
 tr = d["traffic"]
 if not crt:
-    slot = {"k_front": "k1_cols", "k_middle": "k2_rows4096", "k_back": "k3_cols"}
+    slot = {"k_front": "k1_cols", "k_middle": "k2_rows<", "k_back": "k3_cols"}
     out = {}
     for s, sub in slot.items():
         hits = [v["hbm_bytes_per_launch"] for k, v in tr.items() if sub in k]

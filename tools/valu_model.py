@@ -18,8 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 V2_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]   # the flags prmers_amd/csrc/Makefile builds kernels_v2.hip with (V2FLAGS)
 KERNELS = {   # slot of Engine::kernel_name -> (mangled-name substring, what it is)
     "k_front": ("7k1_colsILi2E", "v2::k1_cols<2>"),
-    "k_middle": ("11k2_rows4096ILi0ELi1E", "v2::k2_rows4096<0,1>"),
-    "k_back": ("7k3_colsILi2E", "v2::k3_cols<2>"),
+    "k_middle": ("7k2_rowsINS0_5PairsELi0ELi1ELi0E", "v2::k2_rows<Pairs,0,1,0>"),
+    "k_back": ("7k3_colsILi2ELb0E", "v2::k3_cols<2,false>"),
 }
 
 
