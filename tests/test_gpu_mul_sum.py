@@ -101,28 +101,35 @@ def test_mul_sum_at_the_operand_edges(p, plan):
         assert e.get_int(0) == 2 * x % Mp
 
 
+def mul_sum_script(e, p):
+    """mul_sum on pending run carries and a small subtraction, the same image twice, a squaring on the state that leaves, and every
+    digit at its largest value on all three operands (registers 0 .. 5 of e), against Python integers"""
+    Mp = (1 << p) - 1
+    red = lambda v: orc.mers_reduce(v, p)            # (Python's % is quadratic at a million bits)
+    rng = np.random.default_rng(3)
+    x, y, z = (rand_residue(rng, p) for _ in range(3))
+    e.set_int(0, x); e.set_int(1, y); e.set_int(2, z)
+    e.square_mul(0, 3); e.sub(0, 2); e.square_mul(1); e.square_mul(2, 3)
+    e.set_multiplicand(3, 1); e.set_multiplicand(4, 2)
+    e.mul_sum(0, 3, 4, 5)
+    want = red(red(3 * x * x + Mp - 2) * red(y * y + 3 * z * z))
+    assert e.get_int(0) == want
+    e.mul_sum(0, 4, 4, 5)
+    e.square_mul(0)
+    assert e.get_int(0) == red(red(red(want * 6) * red(z * z)) ** 2)
+    for r in (0, 1, 2):
+        e.set_int(r, Mp - 1)
+    e.set_multiplicand(1, 1); e.set_multiplicand(2, 2)
+    e.mul_sum(0, 1, 2, 3)
+    assert e.get_int(0) == 2
+
+
 def test_mul_sum_on_the_second_family():
     from prmers_amd import CrtEngine
     p = 9941
-    Mp = (1 << p) - 1
-    rng = np.random.default_rng(3)
-    x, y, z = (rand_residue(rng, p) for _ in range(3))
     with CrtEngine(p, 3, reg_count=8) as e:
         assert not e.mul_sum_is_fused()
-        e.set_int(0, x); e.set_int(1, y); e.set_int(2, z)
-        e.square_mul(0, 3); e.sub(0, 2); e.square_mul(1); e.square_mul(2, 3)
-        e.set_multiplicand(3, 1); e.set_multiplicand(4, 2)
-        e.mul_sum(0, 3, 4, 5)
-        want = (3 * x * x - 2) * (y * y + 3 * z * z) % Mp
-        assert e.get_int(0) == want
-        e.mul_sum(0, 4, 4, 5)
-        e.square_mul(0)
-        assert e.get_int(0) == pow(want * 6 * z * z, 2, Mp)
-        for r in (0, 1, 2):
-            e.set_int(r, Mp - 1)
-        e.set_multiplicand(1, 1); e.set_multiplicand(2, 2)
-        e.mul_sum(0, 1, 2, 3)
-        assert e.get_int(0) == 2
+        mul_sum_script(e, p)
 
 
 def _bits(value, nbits):
