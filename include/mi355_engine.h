@@ -131,7 +131,12 @@ MI355_ENGINE_API int mi355_engine_set_digits(mi355_engine_handle handle, size_t 
 /* engine::digit::res64 (engine.h:257-269) */
 MI355_ENGINE_API int mi355_engine_res64(mi355_engine_handle handle, size_t src, uint64_t* res64_out);
 /* raw register images: get_register_data_size / get_data / set_data / *checkpoint (engine.h:134-146).
-   Images are implementation-defined (as in the reference); sizes must match exactly or the call fails. */
+   Images are implementation-defined (as in the reference); sizes must match exactly or the call fails.
+   The size is the same for every plan of an exponent, so the last 8 bytes of a register image are a tag: bit 0 = what the register holds
+   (0 digits, 1 multiplicand image), bits 1..63 = a fingerprint, never zero, of the layout the bytes are in (field family, exponent,
+   transform size, M1, M2, C, split5; for a multiplicand image also the kernels that define its form).  set_data fails on any other tag
+   than the engine's own -- another plan, exponent or family, another kernel set for a multiplicand image, a tag without a fingerprint --
+   and set_checkpoint then loads no register at all: what is loaded is exactly what was written, or nothing. */
 MI355_ENGINE_API size_t mi355_engine_register_data_size(mi355_engine_handle handle);
 MI355_ENGINE_API int mi355_engine_get_data(mi355_engine_handle handle, size_t src, void* data, size_t size);
 MI355_ENGINE_API int mi355_engine_set_data(mi355_engine_handle handle, size_t dst, const void* data, size_t size);

@@ -17,6 +17,7 @@
 #include "crt_engine.hpp"
 #include "crt_kernels.hpp"
 #include "host_digits.hpp"
+#include "plan.hpp"
 
 namespace mi355 {
 namespace {
@@ -621,18 +622,33 @@ void CrtEngine::get_data(size_t src, void* data, size_t size) {
   const Impl::Register& r = im.regs[src];
   if (r.image) { chk(hipMemcpy(out, r.i61, slots * 16, hipMemcpyDeviceToHost), "copy"); chk(hipMemcpy(out + slots * 16, r.i31, slots * 8, hipMemcpyDeviceToHost), "copy"); }
   else chk(hipMemcpy(out, r.x, n * 8, hipMemcpyDeviceToHost), "copy");
-  const uint64_t tag = r.image ? 1 : 0;
+  const uint64_t tag = data_tag(r.image);
   std::memcpy(out + n * 12, &tag, 8);
+}
+// Digits lie in logical order: (p, n, odd) say everything.  A multiplicand image is the packed spectrum as the row stage leaves it -- the
+// radix-8 row kernel (crt_rows.hpp) or the generic passes, on the H1 x H2 split of this engine -- so those belong to an image's tag.
+uint64_t CrtEngine::data_tag(bool image) const {
+  const crt::Grid& gr = im_->gr;
+  return layout_tag(image, kFamilyCrt, im_->g.p, im_->g.n, gr.odd, image ? gr.logH1 : 0u, image ? gr.logH2 : 0u, 0u,
+                    image ? (im_->kernels.radix8 ? 2u : 1u) : 0u);
+}
+void CrtEngine::check_data(const void* data, size_t size) const {
+  if (size != register_data_size()) throw std::runtime_error("set_data: size mismatch");
+  uint64_t tag = 0;
+  std::memcpy(&tag, static_cast<const unsigned char*>(data) + size_t(im_->g.n) * 12, 8);
+  if (tag <= 1) throw std::runtime_error("set_data: the image carries no layout fingerprint (written by an earlier version of the library)");
+  if (tag != data_tag((tag & 1) != 0))
+    throw std::runtime_error(std::string("set_data: ") + ((tag & 1) ? "multiplicand image of another exponent, size or kernel set (" : "register image of another exponent or size (") + describe() + " here)");
 }
 void CrtEngine::set_data(size_t dst, const void* data, size_t size) {
   Impl& im = *im_;
   need_register(dst, "set_data");
-  if (size != register_data_size()) throw std::runtime_error("set_data: size mismatch");
+  check_data(data, size);
   const unsigned char* in = static_cast<const unsigned char*>(data);
   const size_t n = im.g.n, slots = size_t(im.gr.odd) * im.gr.h;
   uint64_t tag = 0;
   std::memcpy(&tag, in + n * 12, 8);
-  if (tag > 1) throw std::runtime_error("set_data: not an image written by this engine");
+  tag &= 1;   // what the register holds; the rest is the fingerprint check_data has just compared
   sync();
   Impl::Register& r = im.regs[dst];
   if (tag == 1) {

@@ -53,11 +53,12 @@ class CrtEngine final : public RegisterMachine {
   void set_words(size_t reg, const uint32_t* w, size_t count) override;
   void get_words(size_t reg, uint32_t* w, size_t count) override;
   uint64_t res64(size_t reg) override;
-  // raw register images (engine.h:134-146): 12 bytes per word + an 8-byte kind tag; a residue uses the first 8 n bytes (digits), a
+  // raw register images (engine.h:134-146): 12 bytes per word + an 8-byte tag (kind + layout fingerprint); a residue uses the first 8 n bytes (digits), a
   // multiplicand all 12 n (its packed spectrum).  Implementation-defined, as the reference's images are.
   size_t register_data_size() const override;
   void get_data(size_t src, void* data, size_t size) override;
   void set_data(size_t dst, const void* data, size_t size) override;
+  void check_data(const void* data, size_t size) const override;
   void sync() override;
   // every iteration is bracketed by events; this family has no deferred subtraction (sub must be 0)
   void time_square_mul(size_t reg, uint32_t a, uint32_t sub, size_t iters, double* total_ms, double* kernel_ms, size_t kernel_count) override;
@@ -68,6 +69,7 @@ class CrtEngine final : public RegisterMachine {
   struct Impl;
   std::unique_ptr<Impl> im_;
   bool holds_image(size_t reg) const override;
+  uint64_t data_tag(bool image) const;                    // the tag word of this engine's raw images (plan.hpp layout_tag)
   void ensure_headroom(size_t reg);                       // relax a register whose additions would overflow the next transform
   uint64_t* canon_digits(size_t reg, int slot);           // device-side canonical form (canon.hip), slot 0 / 1
   bool canon_flags_ok(uint32_t (&flags)[4]);

@@ -610,20 +610,31 @@ void Engine::get_data(size_t src, void* data, size_t size) {
   normalize(src);
   HIPCHK(hipStreamSynchronize(stream_));
   HIPCHK(hipMemcpy(data, slot_[src], reg_bytes_, hipMemcpyDeviceToHost));
-  const uint64_t tag = kind_[src];
+  const uint64_t tag = register_tag(pl_, kc_, kind_[src] == kImage);
   std::memcpy(static_cast<unsigned char*>(data) + reg_bytes_, &tag, 8);
+}
+
+// the tag must be this engine's own for digits or for an image (plan.hpp register_tag): the size alone is the same for every plan of an
+// exponent, and the bytes of another plan would load as a permutation of the digits
+void Engine::check_data(const void* data, size_t size) const {
+  if (size != register_data_size()) throw std::runtime_error("set_data: size mismatch");
+  uint64_t tag = 0;
+  std::memcpy(&tag, static_cast<const unsigned char*>(data) + reg_bytes_, 8);
+  if (tag <= 1) throw std::runtime_error("set_data: the image carries no layout fingerprint (written by an earlier version of the library)");
+  if (tag != register_tag(pl_, kc_, (tag & 1) != 0))
+    throw std::runtime_error((tag & 1) ? "set_data: multiplicand image of another exponent, plan or kernel set (" + pl_.describe() + " here)"
+                                       : "set_data: register image of another exponent or plan (" + pl_.describe() + " here)");
 }
 
 void Engine::set_data(size_t dst, const void* data, size_t size) {
   need_register(dst, "set_data");
-  if (size != register_data_size()) throw std::runtime_error("set_data: size mismatch");
+  check_data(data, size);
   uint64_t tag = 0;
   std::memcpy(&tag, static_cast<const unsigned char*>(data) + reg_bytes_, 8);
-  if (tag > 1) throw std::runtime_error("set_data: not an image written by this engine");
   HIPCHK(hipSetDevice(device_));
   HIPCHK(hipStreamSynchronize(stream_));
   HIPCHK(hipMemcpy(slot_[dst], data, reg_bytes_, hipMemcpyHostToDevice));
-  kind_[dst] = uint8_t(tag);
+  kind_[dst] = (tag & 1) ? kImage : kDigits;
   pending_carry_[dst] = 0;
 }
 

@@ -66,6 +66,7 @@ class Engine final : public RegisterMachine {
   size_t register_data_size() const override { return reg_bytes_ + 8; }
   void get_data(size_t src, void* data, size_t size) override;
   void set_data(size_t dst, const void* data, size_t size) override;
+  void check_data(const void* data, size_t size) const override;
 
   // measurement
   static constexpr size_t kKernels = 6;   // five kernel slots of a squaring + the measured cost of an event record

@@ -405,4 +405,30 @@ inline KernelChoice choose_kernels(const Plan& pl, const char* mi355_kernels) {
   return k;
 }
 
+// The tag word that closes a raw register image (get_data / set_data / checkpoints; register_machine.hpp).  Bit 0 says what the register
+// holds (0: digits, 1: a multiplicand image); bits 1 .. 63 are a fingerprint of everything the bytes in front of it depend on, so that an
+// engine loads only what an engine of the same layout wrote: set_data refuses any other tag, a bare 0 / 1 of earlier versions included
+// (bit 63 is always set: a fingerprint is never zero).  Switches that change neither the order nor the form of the stored words
+// (MI355_TUNE, MI355_HOST_CARRY, and MI355_KERNELS for digits) are not part of it.
+constexpr uint32_t kFamilyGoldilocks = 1, kFamilyCrt = 2;
+inline uint64_t layout_tag(bool image, uint32_t family, uint32_t p, uint64_t n, uint32_t d1, uint32_t d2, uint32_t d3, uint32_t flags, uint32_t form) {
+  const uint64_t words[8] = {family, p, n, d1, d2, d3, flags, form};
+  uint64_t h = 0x6d69333535746167ull;
+  for (uint64_t w : words) {   // splitmix64's finaliser, chained over the fields: every field reaches every bit
+    uint64_t z = (h ^ w) + 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    h = z ^ (z >> 31);
+  }
+  return ((h | (uint64_t(1) << 63)) & ~uint64_t(1)) | (image ? 1u : 0u);
+}
+// Goldilocks registers.  Digits lie in tile-major order (Plan::pos): a function of (n, M1, M2, C); split5 decides C.  A multiplicand image
+// is the work buffer as the row kernel's mode 2 leaves it: its words are in the form of that row kernel, and its rows in the order of the
+// column sweeps' frequency labels (kernels.hpp col_label).  Every column kernel of a power-of-two transform leaves the rows bit-reversed;
+// with a radix-5 stage each column variant has a label map of its own (Engine::Engine), so there the column variant belongs to the form.
+inline uint64_t register_tag(const Plan& pl, const KernelChoice& kc, bool image) {
+  const uint32_t form = image ? 1u + uint32_t(kc.rows) + (pl.r5 == 5 ? 8u * (1u + uint32_t(kc.cols)) : 0u) : 0u;
+  return layout_tag(image, kFamilyGoldilocks, pl.p, pl.n, pl.M1, pl.M2, pl.C, pl.split5 ? 1u : 0u, form);
+}
+
 }  // namespace mi355

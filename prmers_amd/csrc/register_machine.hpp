@@ -52,6 +52,12 @@ class RegisterMachine {
   virtual size_t register_data_size() const = 0;                              // raw register images (engine.h:134-146)
   virtual void get_data(size_t src, void* data, size_t size) = 0;
   virtual void set_data(size_t dst, const void* data, size_t size) = 0;
+  // throws unless `data` is an image this engine can load.  The base checks the size; both engines add the tag word (plan.hpp layout_tag)
+  // of their own layout -- an image of another plan, exponent, family or (for a multiplicand) kernel set is refused, never loaded as
+  // something else.  set_data runs it first; set_checkpoint runs it on every register before it loads one.
+  virtual void check_data(const void* /*data*/, size_t size) const {
+    if (size != register_data_size()) throw std::runtime_error("set_data: size mismatch");
+  }
 
   // `iters` squarings (each followed by sub_u32(reg, sub) when sub != 0) under HIP events: total and per-stage times
   virtual void time_square_mul(size_t reg, uint32_t factor, uint32_t sub, size_t iters, double* total_ms, double* kernel_ms, size_t kernel_count) = 0;
@@ -122,6 +128,7 @@ class RegisterMachine {
   void set_checkpoint(const void* data, size_t size) {
     if (size != checkpoint_size()) throw std::runtime_error("set_checkpoint: size mismatch");
     const size_t rs = register_data_size();
+    for (size_t r = 0; r < reg_count(); ++r) check_data(static_cast<const unsigned char*>(data) + r * rs, rs);   // all or nothing
     for (size_t r = 0; r < reg_count(); ++r) set_data(r, static_cast<const unsigned char*>(data) + r * rs, rs);
   }
 

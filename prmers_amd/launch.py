@@ -72,7 +72,8 @@ def run_sharded(worktodo_lines, make_engine, device="cpu", max_iters=None, check
     it reduces once per FIRST visit of a boundary (a failed check rolls the entry back and meets the same boundaries
     again: those visits do not reduce), and an entry that ends early -- exception, interrupt -- issues the reductions it
     still owes before the rank moves on, so the collectives of all ranks stay matched.
-    per_gpu > 1 runs that many entries of the rank concurrently (threads, one engine and stream each).
+    per_gpu > 1 runs that many entries of the rank concurrently (threads, one engine and stream each; make_engine and should_stop
+    are called from those threads, log and on_status from one of them at a time).
     sync_checks: True / False / "auto" (reduce at check boundaries when every rank has the same number of them,
     per_gpu == 1 and no checkpoint directory is in play: a resumed entry has fewer boundaries left than a fresh one);
     on_status(status) is called on every rank after each reduction.
@@ -89,20 +90,27 @@ def run_sharded(worktodo_lines, make_engine, device="cpu", max_iters=None, check
     lockstep = (sync_checks is True) or (sync_checks == "auto" and per_gpu == 1 and max_iters is None and checklevel > 0 and
                                          ckpt_dir is None and dist.is_initialized() and len(set(per_rank_checks)) == 1)
     state = {"ok": 1, "errors": 0, "iters": 0}
-    state_lock = threading.Lock()
+    state_lock = threading.Lock()      # guards state and results; never held across a reduction or a callback
+    callback_lock = threading.Lock()   # per_gpu > 1: the caller's log and on_status see one call at a time
     results = []
+    entry_log = log
+    if log is not None and per_gpu > 1:
+        def entry_log(msg):
+            with callback_lock:
+                log(msg)
+
+    def reduce_now():
+        with state_lock:
+            snap = dict(state)
+        st = reducer.reduce(snap["ok"], snap["errors"], snap["iters"])
+        if on_status:
+            with callback_lock:
+                on_status(st)
 
     def one(mode, p):
         base_iters = [0]
         owed = check_boundaries([(mode, p)], checklevel)[0] if lockstep else 0   # boundary reductions of this entry
         visited = [0]                                                             # highest boundary already reduced
-
-        def reduce_now():
-            with state_lock:
-                snap = dict(state)
-            st = reducer.reduce(snap["ok"], snap["errors"], snap["iters"])
-            if on_status:
-                on_status(st)
 
         def on_check(passed, it):
             nonlocal owed
@@ -124,7 +132,7 @@ def run_sharded(worktodo_lines, make_engine, device="cpu", max_iters=None, check
                 kw = dict(run_kwargs)
                 if ckpt_dir is not None:
                     kw.update(ckpt_path=prp.checkpoint_name(p, mode, ckpt_dir), backup_interval_s=backup_interval_s)
-                r = prp.run_prp_or_ll(eng, p, mode, max_iters=max_iters, checklevel=checklevel, log=log, on_check=on_check,
+                r = prp.run_prp_or_ll(eng, p, mode, max_iters=max_iters, checklevel=checklevel, log=entry_log, on_check=on_check,
                                       should_stop=should_stop, **kw)
             finally:
                 eng.close()
@@ -142,10 +150,11 @@ def run_sharded(worktodo_lines, make_engine, device="cpu", max_iters=None, check
             reduce_now()
 
     def skipped(mode, p):   # entries a rank does not start after an interrupt: they keep their place in the worktodo
-        results.append({"exponent": p, "mode": mode, "is_prime": False, "res64": "", "res2048": "", "iterations": 0, "gerbicz_checks": 0,
-                        "gerbicz_errors": 0, "complete": False, "state": None, "interrupted": True, "rank": rank})
-        for _ in range(check_boundaries([(mode, p)], checklevel)[0] if lockstep else 0):
-            reducer.reduce(state["ok"], state["errors"], state["iters"])
+        with state_lock:
+            results.append({"exponent": p, "mode": mode, "is_prime": False, "res64": "", "res2048": "", "iterations": 0, "gerbicz_checks": 0,
+                            "gerbicz_errors": 0, "complete": False, "state": None, "interrupted": True, "rank": rank})
+        for _ in range(check_boundaries([(mode, p)], checklevel)[0] if lockstep else 0):   # the reductions the peers still expect
+            reduce_now()
 
     if per_gpu <= 1:
         for mode, p in mine:
@@ -164,8 +173,7 @@ def run_sharded(worktodo_lines, make_engine, device="cpu", max_iters=None, check
                         return
                     mode, p = queue.pop(0)
                 if should_stop is not None and should_stop():
-                    with state_lock:
-                        skipped(mode, p)
+                    skipped(mode, p)
                 else:
                     one(mode, p)
         threads = [threading.Thread(target=worker) for _ in range(min(per_gpu, max(len(mine), 1)))]

@@ -11,6 +11,7 @@ import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKTODO = ["PRP=1,2,127,-1", "PRP=1,2,521,-1", "Test=607", "PRP=1,2,1001,-1"]
+PER_GPU_LOCKSTEP = ["PRP=1,2,521,-1", "PRP=1,2,523,-1", "PRP=1,2,521,-1", "PRP=1,2,523,-1"]
 
 
 def _worker(rank, world, port, q, scenario):
@@ -65,6 +66,11 @@ def _worker(rank, world, port, q, scenario):
             assert any(r.get("interrupted") for r in res1)
             res, status = launch.run_sharded(WORKTODO, lambda p: orc.OracleEngine(p, prp.REGISTERS), checklevel=1, ckpt_dir=d)
             status["first_run_iterations"] = st1["iterations"]
+        elif scenario == "per_gpu_plain":   # two entries of a rank at a time, from two threads (one oracle engine each)
+            res, status = launch.run_sharded(WORKTODO, lambda p: orc.OracleEngine(p, prp.REGISTERS), checklevel=1, per_gpu=2, on_status=seen.append)
+        elif scenario == "per_gpu_lockstep":   # the same under boundary reductions: rank 0 runs 521 twice, rank 1 runs 523 twice, each pair at once
+            res, status = launch.run_sharded(PER_GPU_LOCKSTEP, lambda p: orc.OracleEngine(p, prp.REGISTERS), checklevel=1, per_gpu=2, sync_checks=True,
+                                             on_status=seen.append)
         q.put((rank, [(r["exponent"], r["mode"], r["is_prime"], r["rank"], r.get("error")) for r in res], status, len(seen)))
     finally:
         dist.destroy_process_group()
@@ -141,6 +147,25 @@ def test_interrupt_checkpoints_every_rank_and_a_second_launch_resumes():
         total = 605 + 521 + 1001 + 127
         assert 127 < status["first_run_iterations"] < 127 + 605 + 521
         assert status["iterations"] == total     # every entry reports the iteration it ended on
+
+
+def test_two_entries_of_a_rank_at_a_time():
+    """per_gpu = 2: the results and the status word of the one-at-a-time run, whichever thread finishes first"""
+    expected = sorted([(127, "prp", True, 0, None), (607, "ll", True, 0, None), (521, "prp", True, 1, None), (1001, "prp", False, 1, None)])
+    for rank, res, status, nseen in _run("per_gpu_plain"):
+        assert sorted(res) == expected
+        assert status["all_ok"] == 1 and status["gerbicz_errors"] == 0
+        assert status["iterations"] == 127 + 521 + 605 + 1001
+        assert status["check_boundary_reductions"] is False and nseen == 1   # never automatic with per_gpu > 1: the reduction at exit
+
+
+def test_two_entries_at_a_time_keep_the_boundary_reductions_matched():
+    """sync_checks=True with per_gpu = 2: both threads of a rank reduce at their own boundaries, and every rank issues the same number"""
+    for rank, res, status, nseen in _run("per_gpu_lockstep"):
+        assert status["all_ok"] == 1 and status["gerbicz_errors"] == 0 and status["check_boundary_reductions"] is True
+        assert status["iterations"] == 2 * (521 + 523)
+        assert nseen == 2 * 24 + 1                           # 24 checks for each of a rank's two entries + the reduction at exit
+        assert sorted(res) == [(521, "prp", True, 0, None), (521, "prp", True, 0, None), (523, "prp", False, 1, None), (523, "prp", False, 1, None)]
 
 
 def test_launcher_command_line_dry_run(tmp_path):
