@@ -1,6 +1,7 @@
 // C ABI of libmi355_engine.so (include/mi355_engine.h).  Every entry point catches everything and
 // reports through last_error, as the reference's plugin does (third_party/aevum/src/EngineApi.cpp:447-517).
 #include "../../include/mi355_engine.h"
+#include "../../include/mi355_lanes.h"
 
 #include <cctype>
 #include <cstring>
@@ -44,6 +45,8 @@ mi355::CrtEngine* crt(mi355_engine_handle h) { return dynamic_cast<mi355::CrtEng
 struct CrtSpec { uint32_t odd = 0; size_t words = 0; std::string rest; };   // odd 0: automatic
 bool parse_crt_spec(const char* spec, CrtSpec& out) {
   if (!spec || std::strncmp(spec, "crt", 3) != 0 || (spec[3] != 0 && spec[3] != ':')) return false;
+  if (const char* l = std::strstr(spec, "lanes="))   // lanes are the Goldilocks family's (plan.hpp)
+    if (std::strcmp(l, "lanes=1") != 0) throw std::runtime_error("lanes: not implemented for the crt field family");
   std::string s = spec[3] ? spec + 4 : "";
   size_t pos = 0;
   bool first = true;
@@ -217,6 +220,17 @@ __attribute__((visibility("default"))) int mi355_probe(mi355_engine_handle h, in
   });
 }
 #endif
+// ---- include/mi355_lanes.h ----
+size_t mi355_lanes_count(mi355_engine_handle h) { size_t r = 0; guarded([&] { r = m(h)->lanes(); }); return r; }
+int mi355_lanes_set_words(mi355_engine_handle h, size_t lane, size_t dst, const uint32_t* w, size_t count) {
+  return guarded([&] { if (!w) throw std::runtime_error("set_words: null buffer"); m(h)->set_words_lane(lane, dst, w, count); });
+}
+int mi355_lanes_get_words(mi355_engine_handle h, size_t lane, size_t src, uint32_t* w, size_t count) {
+  return guarded([&] { if (!w) throw std::runtime_error("get_words: null buffer"); m(h)->get_words_lane(lane, src, w, count); });
+}
+int mi355_lanes_res64(mi355_engine_handle h, size_t lane, size_t src, uint64_t* out) {
+  return guarded([&] { if (!out) throw std::runtime_error("res64: null output"); *out = m(h)->res64_lane(lane, src); });
+}
 size_t mi355_engine_algorithmic_bytes(mi355_engine_handle h) { size_t r = 0; guarded([&] { r = m(h)->algorithmic_bytes(); }); return r; }
 
 }  // extern "C"

@@ -63,15 +63,18 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
   HIPCHK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
 
   reg_bytes_ = pl_.n * 8;  // digits use the first 4n bytes, a multiplicand image all 8n
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&regs_), (nregs_ + 1) * reg_bytes_));
-  HIPCHK(hipMemsetAsync(regs_, 0, (nregs_ + 1) * reg_bytes_, stream_));
+  lanes_ = pl_.lanes;
+  lg_ = LaneGeom{uint32_t(lanes_), reg_bytes_, pl_.runs()};
+  const size_t slot_bytes = lanes_ * reg_bytes_, cb_words = lanes_ * pl_.runs();   // a slot is `lanes` registers, one behind the other
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&regs_), (nregs_ + 1) * slot_bytes));
+  HIPCHK(hipMemsetAsync(regs_, 0, (nregs_ + 1) * slot_bytes, stream_));
   slot_.resize(nregs_ + 1);
-  for (size_t r = 0; r <= nregs_; ++r) slot_[r] = regs_ + r * reg_bytes_;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&cbuf_), (nregs_ + 4) * pl_.runs() * 8));
-  HIPCHK(hipMemsetAsync(cbuf_, 0, (nregs_ + 4) * pl_.runs() * 8, stream_));
+  for (size_t r = 0; r <= nregs_; ++r) slot_[r] = regs_ + r * slot_bytes;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&cbuf_), (nregs_ + 4) * cb_words * 8));
+  HIPCHK(hipMemsetAsync(cbuf_, 0, (nregs_ + 4) * cb_words * 8, stream_));
   cb_.resize(nregs_);
-  for (size_t r = 0; r < nregs_; ++r) cb_[r] = cbuf_ + r * pl_.runs();
-  for (size_t r = nregs_; r < nregs_ + 4; ++r) cb_spare_.push_back(cbuf_ + r * pl_.runs());
+  for (size_t r = 0; r < nregs_; ++r) cb_[r] = cbuf_ + r * cb_words;
+  for (size_t r = nregs_; r < nregs_ + 4; ++r) cb_spare_.push_back(cbuf_ + r * cb_words);
   kind_.assign(nregs_, kDigits);
   pending_carry_.assign(nregs_, 0);
 
@@ -129,11 +132,13 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
     dp_.boost_tiles = from(pl_.tiles());
   }
   HIPCHK(configure_kernels(pl_.lds_front, pl_.lds_mid));
+  if (lanes_ > 1) HIPCHK(configure_lane_kernels(pl_.lds_front, pl_.lds_mid));
   if (pl_.split5) {
     HIPCHK(configure_split(dp_));
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&split_), reg_bytes_));
   }
-  // kernel variants: those that serve the shape (plan.hpp), narrowed by MI355_KERNELS=generic|v2rows|v2cols (A/B tests, debugging)
+  // kernel variants: those that serve the shape (plan.hpp), narrowed by MI355_KERNELS=generic|v2rows|v2cols (A/B tests, debugging);
+  // with lanes always the generic set, launched through the lane entry points (run_front ... below)
   kc_ = choose_kernels(pl_, std::getenv("MI355_KERNELS"));
   cols_ = col_sweeps(kc_.cols);
   rows_ = row_sweep(kc_.rows);
@@ -187,7 +192,7 @@ void Engine::sync() {
 void Engine::normalize(size_t r) {
   if (kind_[r] != kDigits) return;
   if (pending_carry_[r]) {
-    HIPCHK(launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
+    HIPCHK(lanes_ > 1 ? launch_carry_fix_lanes(dp_, lg_, digits(r), cbuf(r), stream_) : launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
     pending_carry_[r] = 0;
   }
 }
@@ -197,13 +202,14 @@ void Engine::normalize(size_t r) {
 // run's second digit, log2(n) - 2 (+ log2 a) bits above its width -- too much for the next squaring once that exceeds w.
 // Local carry passes (canon.hip k_relax) take w bits off per pass; as many as it takes to get below the width follow.
 void Engine::carry_fix_now(size_t r, int excess) {
-  HIPCHK(launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
+  HIPCHK(lanes_ > 1 ? launch_carry_fix_lanes(dp_, lg_, digits(r), cbuf(r), stream_) : launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
   pending_carry_[r] = 0;
   if (pl_.C >= 2) return;
   if (excess < 0) excess = ilog2(pl_.n) + 1 + 4 - 2;   // log2(n) rounded up, factor a up to 15 (plan.hpp a_fast)
   const int w = int(pl_.q);                 // the narrower digit width
   while (excess > w - 2) {
-    HIPCHK(canon_relax(dp_, pl_.p, digits(r), reinterpret_cast<uint32_t*>(work()), stream_));
+    for (size_t l = 0; l < lanes_; ++l)   // (lane by lane: runs of two digits are not the ladder's plans)
+      HIPCHK(canon_relax(dp_, pl_.p, digits(r, l), digits(nregs_, l), stream_));
     swap_with_work(r);
     excess -= w;
   }
@@ -212,18 +218,21 @@ void Engine::carry_fix_now(size_t r, int excess) {
 // digits(r) (+ its pending run carries) -> work(); digits(r) stay as they are.  (Runs of two digits never leave carries pending:
 // every operation that writes run carries on a plan with C < 2 takes them in at once, carry_fix_now.)
 void Engine::run_front(size_t r) {
-  if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_front_split(dp_, digits(r), split_, work(), stream_));
+  if (lanes_ > 1) HIPCHK(launch_front_lanes(dp_, lg_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, work(), stream_));
+  else if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_front_split(dp_, digits(r), split_, work(), stream_));
   else HIPCHK(cols_.front(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, work(), stream_));
 }
 
 void Engine::run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, const uint64_t* y2, uint64_t* img) {
-  HIPCHK(rows_(dp_, in, y, y2, img, out, mode, stream_));
+  if (lanes_ > 1) HIPCHK(launch_middle_lanes(dp_, lg_, in, y, y2, img, out, mode, stream_));
+  else HIPCHK(rows_(dp_, in, y, y2, img, out, mode, stream_));
 }
 
 // work() -> digits(r) + run carries in cbuf(r): runs of 2C >= 4 digits leave them to the next sweep, which folds them in, runs of two
 // digits take them at once.  ev (nullable): two events recorded around that carry fix (time_square_mul)
 void Engine::run_back(size_t r, uint32_t a, hipEvent_t* ev) {
-  if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_back_split(dp_, work(), split_, digits(r), cbuf(r), a, stream_));
+  if (lanes_ > 1) HIPCHK(launch_back_lanes(dp_, lg_, work(), digits(r), cbuf(r), a, nullptr, stream_));
+  else if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_back_split(dp_, work(), split_, digits(r), cbuf(r), a, stream_));
   else HIPCHK(cols_.back(dp_, work(), digits(r), cbuf(r), a, stream_));
   if (ev) HIPCHK(hipEventRecord(ev[0], stream_));
   if (pl_.C >= 2) pending_carry_[r] = 1;
@@ -239,14 +248,14 @@ void Engine::write_values(size_t dst, const std::vector<uint32_t>& natural) {
   HIPCHK(hipStreamSynchronize(stream_));
   uint32_t* nat = reinterpret_cast<uint32_t*>(work());
   HIPCHK(hipMemcpy(nat, natural.data(), pl_.n * 4, hipMemcpyHostToDevice));
-  HIPCHK(canon_scatter(dp_, pl_.p, nat, digits(dst), stream_));
+  for (size_t l = 0; l < lanes_; ++l) HIPCHK(canon_scatter(dp_, pl_.p, nat, digits(dst, l), stream_));   // every lane
   HIPCHK(hipStreamSynchronize(stream_));
   kind_[dst] = kDigits;
   pending_carry_[dst] = 0;
 }
 
 // canonical digits of register r (strong carry with wrap-around, 2^p - 1 -> 0) in natural order, on the device
-uint32_t* Engine::canon_digits(size_t r, int slot) {
+uint32_t* Engine::canon_digits(size_t r, int slot, size_t lane) {
   need_residue(r, "get");
   HIPCHK(hipSetDevice(device_));
   const size_t sw = canon_scratch_bytes<uint32_t>(cg_) / 4;
@@ -256,7 +265,7 @@ uint32_t* Engine::canon_digits(size_t r, int slot) {
   }
   normalize(r);
   uint32_t* out = canon_ + sw + size_t(slot) * pl_.n;
-  HIPCHK(canon_launch(cg_, digits(r), out, canon_, stream_));
+  HIPCHK(canon_launch(cg_, digits(r, lane), out, canon_, stream_));
   return out;
 }
 
@@ -284,13 +293,13 @@ void Engine::read_values(size_t src, std::vector<uint64_t>& v) {
   }
 }
 
-void Engine::read_values_host(size_t src, std::vector<uint64_t>& v) {
+void Engine::read_values_host(size_t src, std::vector<uint64_t>& v, size_t lane) {
   need_residue(src, "get");
   stage_.resize(pl_.n);
   HIPCHK(hipSetDevice(device_));
   normalize(src);
   HIPCHK(hipStreamSynchronize(stream_));
-  HIPCHK(hipMemcpy(stage_.data(), digits(src), pl_.n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(stage_.data(), digits(src, lane), pl_.n * 4, hipMemcpyDeviceToHost));
   v.resize(pl_.n);
   const size_t M2 = pl_.M2, C = pl_.C, M1 = pl_.M1;
   for (size_t i = 0; i < pl_.m; ++i) {
@@ -305,10 +314,12 @@ void Engine::read_values_host(size_t src, std::vector<uint64_t>& v) {
 void Engine::set_u32(size_t dst, uint32_t value) {
   need_register(dst, "set");
   HIPCHK(hipSetDevice(device_));
-  HIPCHK(hipMemsetAsync(digits(dst), 0, pl_.n * 4, stream_));
   // spread the constant over the first digits (the reference stores it whole in digit 0,
-  // engine_gpu.h:1444-1449; same value, but never an over-wide digit)
-  if (value) HIPCHK(canon_set_small(dp_, pl_.p, digits(dst), value, stream_));
+  // engine_gpu.h:1444-1449; same value, but never an over-wide digit); every lane gets it
+  for (size_t l = 0; l < lanes_; ++l) {
+    HIPCHK(hipMemsetAsync(digits(dst, l), 0, pl_.n * 4, stream_));
+    if (value) HIPCHK(canon_set_small(dp_, pl_.p, digits(dst, l), value, stream_));
+  }
   kind_[dst] = kDigits;
   pending_carry_[dst] = 0;
 }
@@ -322,24 +333,28 @@ void Engine::set_digits(size_t dst, const uint64_t* d, size_t count) {
 }
 
 void Engine::get_digits(size_t src, uint64_t* d, size_t count) {
+  no_lanes("get_digits");
   if (count != pl_.n) throw std::runtime_error("get_digits: count must equal the transform size");
   std::vector<uint64_t> v;
   read_values(src, v);
   for (size_t k = 0; k < pl_.n; ++k) d[k] = uint32_t(v[k]) | (uint64_t(width_[k]) << 32);  // engine_gpu.h:1560
 }
 
-uint64_t Engine::res64(size_t src) {
+uint64_t Engine::res64(size_t src) { no_lanes("res64"); return res64_of(src, 0); }
+uint64_t Engine::res64_lane(size_t lane, size_t src) { need_lane(lane, "res64"); return res64_of(src, lane); }
+
+uint64_t Engine::res64_of(size_t src, size_t lane) {
   std::vector<uint64_t> v;
   size_t have = pl_.n;
   if (host_carry_) {
-    read_values_host(src, v);
+    read_values_host(src, v, lane);
   } else {
     // the low 64 bits live in the first few digits: canonicalise on the device, read back only those
-    uint32_t* d = canon_digits(src, 0);
+    uint32_t* d = canon_digits(src, 0, lane);
     have = std::min<size_t>(pl_.n, 16);
     uint32_t head[16], flags[4];
     HIPCHK(hipMemcpyAsync(head, d, have * 4, hipMemcpyDeviceToHost, stream_));
-    if (!canon_flags_ok(flags)) { read_values_host(src, v); have = pl_.n; }
+    if (!canon_flags_ok(flags)) { read_values_host(src, v, lane); have = pl_.n; }
     else { v.resize(have); for (size_t k = 0; k < have; ++k) v[k] = flags[0] ? host_digits::ones(width_[k]) : head[k]; }
   }
   return host_digits::res64_of_head(v.data(), width_, have);
@@ -347,10 +362,13 @@ uint64_t Engine::res64(size_t src) {
 
 // The words are packed on the device from the canonical digits (canon.hip k_pack_words; 2^p - 1 comes out as 0 there): word_count() words
 // cross PCIe instead of the n digits.  MI355_HOST_CARRY=1, or a canonical form that falls back, take the host loop (host_digits.hpp).
-void Engine::get_words(size_t src, uint32_t* w, size_t count) {
+void Engine::get_words(size_t src, uint32_t* w, size_t count) { no_lanes("get_words"); words_of(src, 0, w, count); }
+void Engine::get_words_lane(size_t lane, size_t src, uint32_t* w, size_t count) { need_lane(lane, "get_words"); words_of(src, lane, w, count); }
+
+void Engine::words_of(size_t src, size_t lane, uint32_t* w, size_t count) {
   if (count != word_count()) throw std::runtime_error("get_words: count must equal word_count()");
   if (!host_carry_) {
-    uint32_t* d = canon_digits(src, 0);
+    uint32_t* d = canon_digits(src, 0, lane);
     uint32_t* dw = canon_;   // the pipeline's first work array (n words >= word_count(): widths are below 32) is free once the digits are out
     HIPCHK(canon_pack_words(cg_, d, dw, stream_));
     HIPCHK(hipMemcpyAsync(w, dw, count * 4, hipMemcpyDeviceToHost, stream_));
@@ -358,13 +376,35 @@ void Engine::get_words(size_t src, uint32_t* w, size_t count) {
     if (canon_flags_ok(flags)) return;
   }
   std::vector<uint64_t> v;
-  read_values_host(src, v);
+  read_values_host(src, v, lane);
   host_digits::pack_words(v.data(), width_, w, count);
 }
 
 void Engine::set_words(size_t dst, const uint32_t* w, size_t count) {
   need_register(dst, "set_words");
   if (count != word_count()) throw std::runtime_error("set_words: count must equal word_count()");
+  put_words(dst, w, count, 0, lanes_);   // every lane
+  kind_[dst] = kDigits;
+  pending_carry_[dst] = 0;
+}
+
+// One lane of a register of digits; the other lanes stay as they are, pending run carries included: the kind and the pending flag are
+// the register's, so an image is refused (set the register to a value first) and this lane's pending carry words are cleared instead.
+void Engine::set_words_lane(size_t lane, size_t dst, const uint32_t* w, size_t count) {
+  need_lane(lane, "set_words");
+  need_register(dst, "set_words");
+  if (count != word_count()) throw std::runtime_error("set_words: count must equal word_count()");
+  if (lanes_ == 1) { set_words(dst, w, count); return; }
+  if (kind_[dst] != kDigits)
+    throw std::runtime_error("set_words: the register holds a multiplicand image, and the kind is the register's, not the lane's (write a value to every lane first)");
+  if (pending_carry_[dst]) {
+    HIPCHK(hipSetDevice(device_));
+    HIPCHK(hipMemsetAsync(cbuf(dst) + lane * pl_.runs(), 0, pl_.runs() * 8, stream_));
+  }
+  put_words(dst, w, count, lane, lane + 1);
+}
+
+void Engine::put_words(size_t dst, const uint32_t* w, size_t count, size_t lane0, size_t lane1) {
   // bits at and above p are folded back (2^p = 1), so any count-word value is accepted; the fold runs on the host, before the upload,
   // and only for a value that has such bits
   std::vector<uint32_t> src;
@@ -373,23 +413,27 @@ void Engine::set_words(size_t dst, const uint32_t* w, size_t count) {
     host_digits::fold_words_mod_mp(src.data(), count, pl_.p);
     w = src.data();
   }
+  HIPCHK(hipSetDevice(device_));
   if (!host_carry_) {
     // the words go up as they are and are cut into digits on the device (canon.hip k_unpack_words), straight into tile-major order
-    HIPCHK(hipSetDevice(device_));
     uint32_t* dw = reinterpret_cast<uint32_t*>(work());
     HIPCHK(hipMemcpyAsync(dw, w, count * 4, hipMemcpyHostToDevice, stream_));
-    HIPCHK(canon_unpack_words(cg_, dw, digits(dst), stream_));
+    for (size_t l = lane0; l < lane1; ++l) HIPCHK(canon_unpack_words(cg_, dw, digits(dst, l), stream_));
     HIPCHK(hipStreamSynchronize(stream_));
-    kind_[dst] = kDigits;
-    pending_carry_[dst] = 0;
     return;
   }
   std::vector<uint64_t> v(pl_.n);
   host_digits::unpack_words(w, count, width_, v.data());
-  write_values(dst, std::vector<uint32_t>(v.begin(), v.end()));
+  const std::vector<uint32_t> natural(v.begin(), v.end());
+  HIPCHK(hipStreamSynchronize(stream_));
+  uint32_t* nat = reinterpret_cast<uint32_t*>(work());
+  HIPCHK(hipMemcpy(nat, natural.data(), pl_.n * 4, hipMemcpyHostToDevice));
+  for (size_t l = lane0; l < lane1; ++l) HIPCHK(canon_scatter(dp_, pl_.p, nat, digits(dst, l), stream_));
+  HIPCHK(hipStreamSynchronize(stream_));
 }
 
 bool Engine::equal(size_t lhs, size_t rhs) {
+  no_lanes("equal");
   if (!host_carry_) {
     // both registers canonicalised and compared on the device: 16 bytes cross PCIe (the reference reads both
     // registers back and carries them on the host: engine.h:148-157 via engine_gpu.h:1534-1561)
@@ -409,11 +453,11 @@ void Engine::copy(size_t dst, size_t src) {
   if (dst == src) return;
   HIPCHK(hipSetDevice(device_));
   // the register is copied as it stands: digits with their pending run carries (no carry sweep),
-  // a multiplicand image whole
-  const size_t bytes = (kind_[src] == kDigits) ? pl_.n * 4 : reg_bytes_;
+  // a multiplicand image whole; with lanes the whole slot (a lane's digits are the first half of its 8n bytes)
+  const size_t bytes = lanes_ > 1 ? lanes_ * reg_bytes_ : (kind_[src] == kDigits) ? pl_.n * 4 : reg_bytes_;
   HIPCHK(hipMemcpyAsync(slot_[dst], slot_[src], bytes, hipMemcpyDeviceToDevice, stream_));
   if (kind_[src] == kDigits && pending_carry_[src])
-    HIPCHK(hipMemcpyAsync(cbuf(dst), cbuf(src), pl_.runs() * 8, hipMemcpyDeviceToDevice, stream_));
+    HIPCHK(hipMemcpyAsync(cbuf(dst), cbuf(src), lanes_ * pl_.runs() * 8, hipMemcpyDeviceToDevice, stream_));
   pending_carry_[dst] = (kind_[src] == kDigits) ? pending_carry_[src] : 0;
   kind_[dst] = kind_[src];
 }
@@ -463,7 +507,9 @@ void Engine::mul(size_t dst, size_t src, uint32_t a) {
 void Engine::scale(size_t r, uint32_t a) {
   need_residue(r, "scale");
   uint64_t* fresh = take_spare_cbuf();
-  HIPCHK(launch_scale(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, digits(r), fresh, a, stream_));
+  const uint64_t* cin = pending_carry_[r] ? cbuf(r) : nullptr;
+  if (lanes_ > 1) HIPCHK(launch_scale_lanes(dp_, lg_, digits(r), cin, digits(r), fresh, a, stream_));
+  else HIPCHK(launch_scale(dp_, digits(r), cin, digits(r), fresh, a, stream_));
   adopt_cbuf(r, fresh);
   pending_carry_[r] = 1;
   // runs of two digits: the carry words (below 2^34: digit < 2^(q+2) after the passes, times a < 2^32) go in at once
@@ -499,7 +545,7 @@ void Engine::addsub(long s1, long s2, long d1, long d2, size_t a, size_t b) {
   if (d1 >= 0) { la.d1 = digits(size_t(d1)); la.cd1 = fresh[2]; }
   if (d2 >= 0) { la.d2 = digits(size_t(d2)); la.cd2 = fresh[3]; }
   if ((s2 >= 0 && s1 < 0) || (d2 >= 0 && d1 < 0)) throw std::runtime_error("internal: copy output without a primary output");
-  HIPCHK(launch_linear(dp_, la, stream_));
+  HIPCHK(lanes_ > 1 ? launch_linear_lanes(dp_, lg_, la, stream_) : launch_linear(dp_, la, stream_));
   for (int i = 0; i < 4; ++i)
     if (outs[i] >= 0) {
       const size_t r = size_t(outs[i]);
@@ -518,7 +564,8 @@ void Engine::back_ext(size_t dst, uint32_t a, long copy_to, long add_src) {
   if (copy_to >= 0 && size_t(copy_to) != dst) { x.digits2 = digits(size_t(copy_to)); x.cbuf2 = cbuf(size_t(copy_to)); }
   if (add_src >= 0) { x.add_digits = digits(size_t(add_src)); x.add_cbuf = pending_carry_[size_t(add_src)] ? cbuf(size_t(add_src)) : nullptr; }
   uint64_t* fresh = take_spare_cbuf();   // the addend may be dst itself: its pending carries are read while the new ones are written
-  HIPCHK(cols_.back_ext(dp_, work(), digits(dst), fresh, a, x, stream_));
+  if (lanes_ > 1) HIPCHK(launch_back_lanes(dp_, lg_, work(), digits(dst), fresh, a, &x, stream_));
+  else HIPCHK(cols_.back_ext(dp_, work(), digits(dst), fresh, a, x, stream_));
   adopt_cbuf(dst, fresh);
   const size_t outs[2] = {dst, x.digits2 ? size_t(copy_to) : dst};
   for (int i = 0; i < (x.digits2 ? 2 : 1); ++i) {
@@ -598,12 +645,13 @@ void Engine::sub_u32(size_t r, uint32_t v) {
   // then go negative, which the unsigned back sweep reads as values near the field prime; the borrow below is exact for every register)
   // the small subtraction only touches the digit vector (cyclic borrow), so run carries that are still pending
   // for the next front sweep can stay pending: value = digits + carries - v either way
-  HIPCHK(launch_sub_small(dp_, digits(r), v, stream_));
+  HIPCHK(lanes_ > 1 ? launch_sub_small_lanes(dp_, lg_, digits(r), v, stream_) : launch_sub_small(dp_, digits(r), v, stream_));
 }
 
 // ---- raw images -----------------------------------------------------------------------------
 
 void Engine::get_data(size_t src, void* data, size_t size) {
+  no_lanes("get_data");
   need_register(src, "get_data");
   if (size != register_data_size()) throw std::runtime_error("get_data: size mismatch");
   HIPCHK(hipSetDevice(device_));
@@ -617,6 +665,7 @@ void Engine::get_data(size_t src, void* data, size_t size) {
 // the tag must be this engine's own for digits or for an image (plan.hpp register_tag): the size alone is the same for every plan of an
 // exponent, and the bytes of another plan would load as a permutation of the digits
 void Engine::check_data(const void* data, size_t size) const {
+  no_lanes("set_data");
   if (size != register_data_size()) throw std::runtime_error("set_data: size mismatch");
   uint64_t tag = 0;
   std::memcpy(&tag, static_cast<const unsigned char*>(data) + reg_bytes_, 8);
@@ -663,6 +712,7 @@ const char* Engine::stage_name(size_t k) {
 // (kernel_ms[5], measured as the spacing of back-to-back records on the same stream: without the subtraction every
 // interval carries one record, ~4-5 us, and a path that launches no kernel between two records shows it as a kernel).
 void Engine::time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, double* total_ms, double* kernel_ms, size_t kcount) {
+  no_lanes("time_square_mul");
   need_residue(r, "time_square_mul");
   if (a == 0 || iters == 0) throw std::runtime_error("time_square_mul: factor and iters must be >= 1");
   HIPCHK(hipSetDevice(device_));

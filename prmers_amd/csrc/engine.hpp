@@ -36,6 +36,12 @@ class Engine final : public RegisterMachine {
   void set_words(size_t dst, const uint32_t* w, size_t count) override;
   void get_words(size_t src, uint32_t* w, size_t count) override;
   uint64_t res64(size_t src) override;
+  // Lanes (plan token lanes=B): B residues per register, every operation on all of them in one launch.  The writes above
+  // then write every lane; the reads, equal, raw images and time_square_mul are refused, and these read or write one lane.
+  size_t lanes() const override { return lanes_; }
+  void set_words_lane(size_t lane, size_t dst, const uint32_t* w, size_t count) override;
+  void get_words_lane(size_t lane, size_t src, uint32_t* w, size_t count) override;
+  uint64_t res64_lane(size_t lane, size_t src) override;
   void copy(size_t dst, size_t src) override;
   void set_multiplicand(size_t dst, size_t src) override;
   void square_mul(size_t r, uint32_t a) override;
@@ -85,13 +91,21 @@ class Engine final : public RegisterMachine {
   // kDigits: unweighted u32 digits (+ deferred run carries); kImage: multiplicand
   enum Kind : uint8_t { kDigits = 0, kImage = 1 };
   bool holds_image(size_t r) const override { return kind_[r] == kImage; }
-  uint32_t* digits(size_t r) { return reinterpret_cast<uint32_t*>(slot_[r]); }
+  // lane l of a slot lies l * reg_bytes_ behind lane 0, lane l of a carry buffer l * runs() words (kernels.hpp LaneGeom)
+  uint32_t* digits(size_t r, size_t lane = 0) { return reinterpret_cast<uint32_t*>(slot_[r] + lane * reg_bytes_); }
+  void no_lanes(const char* op) const {   // operations a lane engine does not have
+    if (lanes_ > 1) throw std::runtime_error(std::string(op) + ": not with lanes (per-lane I/O: mi355_lanes_* in include/mi355_lanes.h)");
+  }
   uint64_t* image(size_t r) { return reinterpret_cast<uint64_t*>(slot_[r]); }
   uint64_t* work() { return reinterpret_cast<uint64_t*>(slot_[nregs_]); }
   void swap_with_work(size_t r) { std::swap(slot_[r], slot_[nregs_]); }
   void read_values(size_t src, std::vector<uint64_t>& v);   // natural order, strongly carried digits
-  void read_values_host(size_t src, std::vector<uint64_t>& v);   // the same through D2H + host carry (reference's way: host_digits.hpp)
-  uint32_t* canon_digits(size_t r, int slot);   // device: canonical digits of r in natural order (canon.hip), slot 0 / 1
+  void read_values_host(size_t src, std::vector<uint64_t>& v, size_t lane = 0);   // the same through D2H + host carry (reference's way: host_digits.hpp)
+  uint32_t* canon_digits(size_t r, int slot, size_t lane = 0);   // device: canonical digits of r in natural order (canon.hip), slot 0 / 1
+  void words_of(size_t src, size_t lane, uint32_t* w, size_t count);   // get_words of one lane
+  uint64_t res64_of(size_t src, size_t lane);
+  // fold w mod 2^p - 1 where it has bits at or above p, upload it to the work buffer and cut it into the digits of lanes [lane0, lane1) of dst
+  void put_words(size_t dst, const uint32_t* w, size_t count, size_t lane0, size_t lane1);
   bool canon_flags_ok(uint32_t (&flags)[4]);    // reads the flag words; false: fall back to the host carry
   void write_values(size_t dst, const std::vector<uint32_t>& natural);
   void square_chain(size_t r, uint32_t a, hipEvent_t* ev);
@@ -114,9 +128,11 @@ class Engine final : public RegisterMachine {
   bool verbose_ = false;
   hipStream_t stream_ = nullptr;
   size_t nregs_ = 0, reg_bytes_ = 0;
-  unsigned char* regs_ = nullptr;            // (reg_count + 1) slots of 8n bytes; the extra one is the work buffer
+  size_t lanes_ = 1;         // residues per register (pl_.lanes)
+  LaneGeom lg_{};            // what the lane launches need; used when lanes_ > 1
+  unsigned char* regs_ = nullptr;            // (reg_count + 1) slots of lanes x 8n bytes; the extra one is the work buffer
   std::vector<unsigned char*> slot_;          // slot_[r]: storage of register r; slot_[reg_count]: work buffer (swappable)
-  uint64_t* cbuf_ = nullptr;                  // reg_count + 4 buffers of runs() carry words
+  uint64_t* cbuf_ = nullptr;                  // reg_count + 4 buffers of lanes x runs() carry words
   std::vector<uint64_t*> cb_, cb_spare_;      // cb_[r]: the buffer register r uses now
   void* tables_ = nullptr;
   uint64_t* split_ = nullptr;   // second work buffer of the split column sweeps (plan.split5: n = 5 2^26)

@@ -597,8 +597,7 @@ __global__ void __launch_bounds__(256) k_back_split_a(DevPlan pl, const uint64_t
 // One thread per run: a, b (+ their pending carry words) -> sum and / or difference, each written to up to two
 // registers, with the run's carry-out word left pending (kernels.hpp LinArgs).  The difference is a - b + 2 Mp
 // digit by digit (neg2_mp4, marin.cl:246-256), so nothing goes negative: digits are below 2^width + a small excess.
-__global__ void __launch_bounds__(256) k_linear(DevPlan pl, LinArgs la) {
-  const uint32_t run = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void linear_body(const DevPlan& pl, const LinArgs& la, uint32_t run) {
   const uint32_t M1 = pl.M1, C = pl.C, NT = pl.M2 / C;
   if (run >= M1 * NT) return;
   const uint32_t T = run / M1, i1 = run - T * M1;
@@ -635,15 +634,14 @@ __global__ void __launch_bounds__(256) k_linear(DevPlan pl, LinArgs la) {
   if (want_s) { la.cs1[ci] = cs; if (la.s2) la.cs2[ci] = cs; }
   if (want_d) { la.cd1[ci] = cd; if (la.d2) la.cd2[ci] = cd; }
 }
+__global__ void __launch_bounds__(256) k_linear(DevPlan pl, LinArgs la) { linear_body(pl, la, blockIdx.x * blockDim.x + threadIdx.x); }
 
 
 // x a for the factors above the plan's fused bound (plan.hpp fused_factor_limit; Engine::scale): one thread per run, the run's digits with
 // their pending carry-in taken as k_linear takes them (three masked digits, the rest on the fourth; all of it on the second when C = 1),
 // times a with a carry through the run, whose carry-out word is left pending.  Digit outputs may alias the input, cout must not alias cin.
 // Bounds: a digit after the carry-in is below 2^31 (fused_factor_ok), so digit a + carry < 2^63 + 2^(64 - q).
-__global__ void __launch_bounds__(256) k_scale(DevPlan pl, const uint32_t* __restrict__ in, const uint64_t* __restrict__ cin,
-                                               uint32_t* __restrict__ out, uint64_t* __restrict__ cout, uint32_t a) {
-  const uint32_t run = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void scale_body(const DevPlan& pl, const uint32_t* in, const uint64_t* cin, uint32_t* out, uint64_t* cout, uint32_t a, uint32_t run) {
   const uint32_t M1 = pl.M1, C = pl.C, NT = pl.M2 / C;
   if (run >= M1 * NT) return;
   const uint32_t T = run / M1, i1 = run - T * M1;
@@ -663,12 +661,15 @@ __global__ void __launch_bounds__(256) k_scale(DevPlan pl, const uint32_t* __res
   }
   cout[size_t(T) * M1 + i1] = c;
 }
+__global__ void __launch_bounds__(256) k_scale(DevPlan pl, const uint32_t* __restrict__ in, const uint64_t* __restrict__ cin,
+                                               uint32_t* __restrict__ out, uint64_t* __restrict__ cout, uint32_t a) {
+  scale_body(pl, in, cin, out, cout, a, blockIdx.x * blockDim.x + threadIdx.x);
+}
 
 
 // carry fix: one thread per run; weak carry (the remainder, if any, stays on the run's last digit:
 // same contract as adc4, marin.cl:203-212)
-__global__ void __launch_bounds__(256) k_carry_fix(DevPlan pl, uint32_t* __restrict__ digits, const uint64_t* __restrict__ cbuf) {
-  const uint32_t run = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void carry_fix_body(const DevPlan& pl, uint32_t* digits, const uint64_t* cbuf, uint32_t run) {
   const uint32_t M1 = pl.M1, C = pl.C, NT = pl.M2 / C;
   if (run >= M1 * NT) return;
   const uint32_t T = run / M1, i1 = run - T * M1;
@@ -686,6 +687,9 @@ __global__ void __launch_bounds__(256) k_carry_fix(DevPlan pl, uint32_t* __restr
     if (cin == 0) break;
   }
 }
+__global__ void __launch_bounds__(256) k_carry_fix(DevPlan pl, uint32_t* __restrict__ digits, const uint64_t* __restrict__ cbuf) {
+  carry_fix_body(pl, digits, cbuf, blockIdx.x * blockDim.x + threadIdx.x);
+}
 
 // digit j -> memory slot (Plan::pos)
 __device__ __forceinline__ size_t slot_of(const DevPlan& pl, uint32_t j) {
@@ -696,7 +700,7 @@ __device__ __forceinline__ size_t slot_of(const DevPlan& pl, uint32_t j) {
 }
 
 // x <- x - a with borrow, one thread (marin.cl:2376-2393)
-__global__ void k_sub_small(DevPlan pl, uint32_t* __restrict__ digits, uint32_t a) {
+__device__ __forceinline__ void sub_small_body(const DevPlan& pl, uint32_t* digits, uint32_t a) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   uint64_t borrow = a;
   for (int lap = 0; lap < 3 && borrow; ++lap) {
@@ -717,6 +721,59 @@ __global__ void k_sub_small(DevPlan pl, uint32_t* __restrict__ digits, uint32_t 
     }
   }
 }
+__global__ void k_sub_small(DevPlan pl, uint32_t* __restrict__ digits, uint32_t a) { sub_small_body(pl, digits, a); }
+
+// ---------------------------------------------------------------------------------------------
+// Lane engines (kernels.hpp LaneGeom): every register slot holds `lanes` independent residues, and one launch applies the sweep to all of
+// them.  blockIdx.y is the lane, blockIdx.x what it is in the single-lane kernel; the bodies are the ones above, on pointers moved to
+// the lane.  Entry points of their own: the single-lane kernels and their launches stay as they are.  (No priority boost here: with a
+// lane dimension the last half round of a launch is not the top of blockIdx.x.)
+// ---------------------------------------------------------------------------------------------
+template <class T> __device__ __forceinline__ T* lane_reg(const LaneGeom& lg, T* p) {   // a register, the work buffer or an image
+  return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + size_t(blockIdx.y) * lg.reg_bytes) : nullptr;
+}
+template <class T> __device__ __forceinline__ T* lane_cbuf(const LaneGeom& lg, T* p) { return p ? p + size_t(blockIdx.y) * lg.runs : nullptr; }
+
+__global__ void __launch_bounds__(1024) k_front_lanes(DevPlan pl, LaneGeom lg, const uint32_t* __restrict__ digits, const uint64_t* __restrict__ cbuf_in,
+                                                      uint64_t* __restrict__ Wout) {
+  front_body(pl, lane_reg(lg, digits), lane_cbuf(lg, cbuf_in), lane_reg(lg, Wout), blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
+}
+__global__ void __launch_bounds__(1024) k_middle_lanes(DevPlan pl, LaneGeom lg, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Yimg,
+                                                       const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout, int mode) {
+  middle_body(pl, lane_reg(lg, Win), lane_reg(lg, Yimg), lane_reg(lg, Yimg2), lane_reg(lg, Wout), mode, blockIdx.x, reinterpret_cast<P2*>(smem_raw),
+              threadIdx.x, blockDim.x);
+}
+__global__ void __launch_bounds__(1024) k_middle_keep_lanes(DevPlan pl, LaneGeom lg, const uint64_t* __restrict__ Win, uint64_t* __restrict__ Wimg,
+                                                            uint64_t* __restrict__ Wout) {
+  middle_body<true>(pl, lane_reg(lg, Win), nullptr, nullptr, lane_reg(lg, Wout), 0, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x,
+                    lane_reg(lg, Wimg));
+}
+template <bool EXT>
+__global__ void __launch_bounds__(1024) k_back_lanes(DevPlan pl, LaneGeom lg, const uint64_t* __restrict__ Win, uint32_t* __restrict__ digits,
+                                                     uint64_t* __restrict__ cbuf, uint32_t a, BackExt ext) {
+  BackExt x;
+  if (EXT) {
+    x.digits2 = lane_reg(lg, ext.digits2); x.cbuf2 = lane_cbuf(lg, ext.cbuf2);
+    x.add_digits = lane_reg(lg, ext.add_digits); x.add_cbuf = lane_cbuf(lg, ext.add_cbuf);
+  }
+  back_body<EXT>(pl, lane_reg(lg, Win), lane_reg(lg, digits), lane_cbuf(lg, cbuf), a, x, xcd_tile(pl, blockIdx.x, gridDim.x),
+                 reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
+}
+__global__ void __launch_bounds__(256) k_linear_lanes(DevPlan pl, LaneGeom lg, LinArgs la) {
+  LinArgs l;
+  l.a = lane_reg(lg, la.a); l.ca = lane_cbuf(lg, la.ca); l.b = lane_reg(lg, la.b); l.cb = lane_cbuf(lg, la.cb);
+  l.s1 = lane_reg(lg, la.s1); l.cs1 = lane_cbuf(lg, la.cs1); l.s2 = lane_reg(lg, la.s2); l.cs2 = lane_cbuf(lg, la.cs2);
+  l.d1 = lane_reg(lg, la.d1); l.cd1 = lane_cbuf(lg, la.cd1); l.d2 = lane_reg(lg, la.d2); l.cd2 = lane_cbuf(lg, la.cd2);
+  linear_body(pl, l, blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void __launch_bounds__(256) k_scale_lanes(DevPlan pl, LaneGeom lg, const uint32_t* __restrict__ in, const uint64_t* __restrict__ cin,
+                                                     uint32_t* __restrict__ out, uint64_t* __restrict__ cout, uint32_t a) {
+  scale_body(pl, lane_reg(lg, in), lane_cbuf(lg, cin), lane_reg(lg, out), lane_cbuf(lg, cout), a, blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void __launch_bounds__(256) k_carry_fix_lanes(DevPlan pl, LaneGeom lg, uint32_t* __restrict__ digits, const uint64_t* __restrict__ cbuf) {
+  carry_fix_body(pl, lane_reg(lg, digits), lane_cbuf(lg, cbuf), blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void k_sub_small_lanes(DevPlan pl, LaneGeom lg, uint32_t* __restrict__ digits, uint32_t a) { sub_small_body(pl, lane_reg(lg, digits), a); }
 
 // ------------------------------- launch wrappers ---------------------------------------------
 
@@ -728,8 +785,8 @@ static inline uint32_t block_for(size_t work) {
 
 // work-group size for a tile of `pairs` pairs: a quarter of it (one radix-4 butterfly per thread and pass), or half of it when the whole
 // launch has no more work-groups than the chip has CUs (latency-bound: one plane per thread, lds_pow2_dft_planes)
-static inline uint32_t block_for_small(const DevPlan& pl, size_t pairs) {
-  const size_t groups = size_t(pl.M1) * pl.M2 / (pairs ? pairs : 1);
+static inline uint32_t block_for_small(const DevPlan& pl, size_t pairs, size_t lanes = 1) {
+  const size_t groups = lanes * (size_t(pl.M1) * pl.M2 / (pairs ? pairs : 1));   // of the whole launch: a lane engine's launch has `lanes` times the tiles
   // at most one work-group per CU (with two per CU the classic form wins: n = 2^21, 0.066 vs 0.073 ms; profiles/r02_ab_small_tiles.txt)
   if (groups > 256) return block_for(pairs / 4 ? pairs / 4 : 1);
   // one pair per thread in the element-wise loops where the tile allows (C2: 0.0331 -> 0.0318 ms), else one plane per thread
@@ -802,6 +859,55 @@ hipError_t launch_carry_fix(const DevPlan& pl, uint32_t* digits, const uint64_t*
 hipError_t launch_sub_small(const DevPlan& pl, uint32_t* digits, uint32_t a, hipStream_t s) {
   hipLaunchKernelGGL(k_sub_small, dim3(1), dim3(64), 0, s, pl, digits, a);
   return hipGetLastError();
+}
+// the lane launches: the single-lane grid in x, the lanes in y
+hipError_t launch_front_lanes(const DevPlan& pl, const LaneGeom& lg, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s) {
+  const size_t tile = size_t(pl.M1) * pl.C;
+  hipLaunchKernelGGL(k_front_lanes, dim3(pl.M2 / pl.C, lg.lanes), dim3(block_for_small(pl, tile, lg.lanes)), tile * 16, s, pl, lg, digits, cbuf_in, W);
+  return hipGetLastError();
+}
+hipError_t launch_middle_lanes(const DevPlan& pl, const LaneGeom& lg, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout,
+                               int mode, hipStream_t s) {
+  if (mode < 0 || mode > 4) return hipErrorInvalidValue;
+  const dim3 grid(pl.M1, lg.lanes), block(block_for_small(pl, pl.M2, lg.lanes));
+  if (mode == 4) hipLaunchKernelGGL(k_middle_keep_lanes, grid, block, size_t(pl.M2) * 16, s, pl, lg, Win, Wimg, Wout);
+  else hipLaunchKernelGGL(k_middle_lanes, grid, block, size_t(pl.M2) * 16, s, pl, lg, Win, Y, Y2, Wout, mode);
+  return hipGetLastError();
+}
+hipError_t launch_back_lanes(const DevPlan& pl, const LaneGeom& lg, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt* x, hipStream_t s) {
+  const size_t tile = size_t(pl.M1) * pl.C;
+  const dim3 grid(pl.M2 / pl.C, lg.lanes), block(block_for_small(pl, tile, lg.lanes));
+  if (x) hipLaunchKernelGGL(k_back_lanes<true>, grid, block, tile * 16, s, pl, lg, W, digits, cbuf, a, *x);
+  else hipLaunchKernelGGL(k_back_lanes<false>, grid, block, tile * 16, s, pl, lg, W, digits, cbuf, a, BackExt());
+  return hipGetLastError();
+}
+hipError_t launch_linear_lanes(const DevPlan& pl, const LaneGeom& lg, const LinArgs& la, hipStream_t s) {
+  const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
+  hipLaunchKernelGGL(k_linear_lanes, dim3((runs + 255) / 256, lg.lanes), dim3(256), 0, s, pl, lg, la);
+  return hipGetLastError();
+}
+hipError_t launch_scale_lanes(const DevPlan& pl, const LaneGeom& lg, const uint32_t* in, const uint64_t* cin, uint32_t* out, uint64_t* cout, uint32_t a, hipStream_t s) {
+  const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
+  hipLaunchKernelGGL(k_scale_lanes, dim3((runs + 255) / 256, lg.lanes), dim3(256), 0, s, pl, lg, in, cin, out, cout, a);
+  return hipGetLastError();
+}
+hipError_t launch_carry_fix_lanes(const DevPlan& pl, const LaneGeom& lg, uint32_t* digits, const uint64_t* cbuf, hipStream_t s) {
+  const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
+  hipLaunchKernelGGL(k_carry_fix_lanes, dim3((runs + 255) / 256, lg.lanes), dim3(256), 0, s, pl, lg, digits, cbuf);
+  return hipGetLastError();
+}
+hipError_t launch_sub_small_lanes(const DevPlan& pl, const LaneGeom& lg, uint32_t* digits, uint32_t a, hipStream_t s) {
+  hipLaunchKernelGGL(k_sub_small_lanes, dim3(1, lg.lanes), dim3(64), 0, s, pl, lg, digits, a);
+  return hipGetLastError();
+}
+hipError_t configure_lane_kernels(size_t lds_front, size_t lds_mid) {
+  const void* cols[3] = {reinterpret_cast<const void*>(k_front_lanes), reinterpret_cast<const void*>(k_back_lanes<false>), reinterpret_cast<const void*>(k_back_lanes<true>)};
+  const void* rows[2] = {reinterpret_cast<const void*>(k_middle_lanes), reinterpret_cast<const void*>(k_middle_keep_lanes)};
+  for (const void* f : cols)
+    if (lds_front > 48 * 1024) { hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_front)); if (e != hipSuccess) return e; }
+  for (const void* f : rows)
+    if (lds_mid > 48 * 1024) { hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_mid)); if (e != hipSuccess) return e; }
+  return hipSuccess;
 }
 hipError_t configure_kernels(size_t lds_front, size_t lds_mid) {
   hipError_t e = hipSuccess;

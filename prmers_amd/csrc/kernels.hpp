@@ -92,6 +92,20 @@ hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_
 hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
 hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s);
 hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
+// Lane engines (plan token lanes=B, B > 1): a register slot -- and the work buffer, and a multiplicand image -- is `lanes` single-lane
+// registers reg_bytes apart, a carry buffer `lanes` x runs words.  Every launch below is the single-lane one with the lanes as grid.y
+// (kernels.hip k_*_lanes: the same bodies on pointers moved to lane blockIdx.y); pointers are those of lane 0, null stays null.
+// launch_back_lanes: x null for the plain back sweep.
+struct LaneGeom { uint32_t lanes; size_t reg_bytes; size_t runs; };
+hipError_t configure_lane_kernels(size_t lds_front, size_t lds_mid);
+hipError_t launch_front_lanes(const DevPlan& pl, const LaneGeom& lg, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s);
+hipError_t launch_middle_lanes(const DevPlan& pl, const LaneGeom& lg, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout,
+                               int mode, hipStream_t s);
+hipError_t launch_back_lanes(const DevPlan& pl, const LaneGeom& lg, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt* x, hipStream_t s);
+hipError_t launch_linear_lanes(const DevPlan& pl, const LaneGeom& lg, const LinArgs& la, hipStream_t s);
+hipError_t launch_scale_lanes(const DevPlan& pl, const LaneGeom& lg, const uint32_t* in, const uint64_t* cin, uint32_t* out, uint64_t* cout, uint32_t a, hipStream_t s);
+hipError_t launch_carry_fix_lanes(const DevPlan& pl, const LaneGeom& lg, uint32_t* digits, const uint64_t* cbuf, hipStream_t s);
+hipError_t launch_sub_small_lanes(const DevPlan& pl, const LaneGeom& lg, uint32_t* digits, uint32_t a, hipStream_t s);
 // columns of 5 L1 pairs that do not fit LDS (n = 5 * 2^26): the radix-5 stage through a second work buffer U (8 n bytes), C = 1
 hipError_t configure_split(const DevPlan& pl);
 hipError_t launch_front_split(const DevPlan& pl, const uint32_t* digits, uint64_t* U, uint64_t* W, hipStream_t s);

@@ -55,6 +55,7 @@ struct Plan {
   uint32_t L1 = 1, logL1 = 0, logM2 = 0;
   uint32_t C = 1;           // adjacent columns per front/back tile (runs of 2C digits)
   bool split5 = false;      // columns of 5 L1 pairs beyond LDS: the radix-5 stage runs through memory (kernels.hip k_front_split_*), C = 1
+  uint32_t lanes = 1;       // independent residues per register (plan token lanes=B): every operation acts on all of them in one launch
   uint32_t q = 0, t = 0;    // p = q*n + t
   uint32_t twh = 0;         // omega_m^e = TWlo[e & (2^twh-1)] * TWhi[e >> twh]
   uint32_t a_fast = 1;      // largest factor the back sweeps multiply in themselves (fused_factor_ok); above it: factor 1 + k_scale
@@ -96,7 +97,7 @@ struct Plan {
   std::string describe() const {
     char buf[160];
     std::snprintf(buf, sizeof buf, "marin-hip:n=%zu:m1=%u:m2=%u:c=%u%s", n, M1, M2, C, split5 ? ":split5" : "");
-    return buf;
+    return lanes > 1 ? std::string(buf) + ":lanes=" + std::to_string(lanes) : std::string(buf);
   }
 };
 
@@ -218,7 +219,9 @@ inline uint32_t fused_factor_limit(uint32_t q, size_t n, uint32_t C) {
   return uint32_t(C >= 2 ? lo : std::min<uint64_t>(lo, 15));
 }
 
-// spec: "" (auto) or comma/colon separated "m2=<pow2>", "c=<pow2>"
+constexpr uint32_t kMaxLanes = 65535;   // the lane is blockIdx.y
+
+// spec: "" (auto) or comma/colon separated "m2=<pow2>", "c=<pow2>", "lanes=<1..65535>"
 inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables = true) {
   if (p < 3) throw std::runtime_error("exponent must be >= 3");
   Plan pl;
@@ -240,6 +243,12 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
       if (tok.rfind("m2=", 0) == 0) want_m2 = std::atol(tok.c_str() + 3);
       else if (tok.rfind("c=", 0) == 0) want_c = std::atol(tok.c_str() + 2);
       else if (tok == "split5") want_split = true;   // tests: the split column sweeps at a small 5 2^k size
+      else if (tok.rfind("lanes=", 0) == 0) {
+        const std::string v = tok.substr(6);
+        if (v.empty() || v.size() > 5 || v.find_first_not_of("0123456789") != std::string::npos || std::atol(v.c_str()) < 1 || std::atol(v.c_str()) > long(kMaxLanes))
+          throw std::runtime_error("bad lanes in plan spec: '" + tok + "' (lanes=1 .. lanes=" + std::to_string(kMaxLanes) + ")");
+        pl.lanes = uint32_t(std::atol(v.c_str()));
+      }
       else if (!tok.empty() && tok != "marin-hip" && tok.rfind("n=", 0) != 0 && tok.rfind("m1=", 0) != 0)
         throw std::runtime_error("unknown plan token '" + tok + "'");
       i = e + 1;
@@ -273,6 +282,7 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
   if (want_split && pl.r5 != 5) throw std::runtime_error("split5 needs a 5 * 2^k transform");
   pl.split5 = want_split || size_t(pl.M1) * 16 > 160 * 1024;
   if (pl.split5 && (pl.r5 != 5 || size_t(pl.L1) * 16 > 128 * 1024)) throw std::runtime_error("transform size not supported (columns beyond the split sweeps)");
+  if (pl.split5 && pl.lanes > 1) throw std::runtime_error("lanes: not with the split column sweeps (split5)");
 
   // tile: up to 4096 pairs (64 KiB), runs of at most 16 pairs (256 B of the work buffer);
   // grow to 8192 pairs (128 KiB) when that is what C >= 4 needs
@@ -335,7 +345,7 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
   const uint64_t om1 = gf::pow(om, pl.M2), om2 = gf::pow(om, pl.M1);
   pl.UT1.resize(pl.M1); pl.UT1[0] = 1; for (uint32_t i = 1; i < pl.M1; ++i) pl.UT1[i] = gf::mul(pl.UT1[i - 1], om1);
   pl.UT2.resize(pl.M2); pl.UT2[0] = 1; for (uint32_t i = 1; i < pl.M2; ++i) pl.UT2[i] = gf::mul(pl.UT2[i - 1], om2);
-  const KernelChoice kc = served_kernels(pl.r5, pl.M1, pl.M2, pl.C, pl.split5);
+  const KernelChoice kc = pl.lanes > 1 ? KernelChoice{} : served_kernels(pl.r5, pl.M1, pl.M2, pl.C, pl.split5);   // (choose_kernels)
   if (kc.rows == RowKernels::kRadix8 || kc.rows == RowKernels::kRadix8Wide) {   // rows of 8192 = one radix-2 level over two 4096-point transforms
     const uint32_t st = pl.M2 / 4096;       // omega_4096 = omega_M2^st
     pl.S2r.resize(4096); pl.S2ri.resize(4096);
@@ -398,6 +408,7 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
 // The kernels a plan runs: those that serve its shape, narrowed by MI355_KERNELS (A/B tests, debugging): unset or "v2" keeps them,
 // "v2rows" / "v2cols" keep only the register-resident rows / columns, anything else takes the generic ones (the split sweeps stay).
 inline KernelChoice choose_kernels(const Plan& pl, const char* mi355_kernels) {
+  if (pl.lanes > 1) return KernelChoice{};   // lane engines run the generic set, whatever serves the shape (kernels.hip k_*_lanes)
   KernelChoice k = served_kernels(pl.r5, pl.M1, pl.M2, pl.C, pl.split5);
   const std::string sel = mi355_kernels ? mi355_kernels : "v2";
   if (sel != "v2" && sel != "v2rows") k.rows = RowKernels::kGeneric;

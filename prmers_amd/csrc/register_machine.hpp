@@ -49,6 +49,13 @@ class RegisterMachine {
   virtual void get_words(size_t src, uint32_t* w, size_t count) = 0;          // canonical: 2^p - 1 reads as 0
   virtual uint64_t res64(size_t src) = 0;
 
+  // Lanes (include/mi355_lanes.h): an engine made with the plan token lanes=B holds B independent residues per register and applies every
+  // operation to all of them; these read and write one.  A machine without lanes has the one lane 0, which is the register itself.
+  virtual size_t lanes() const { return 1; }
+  virtual void set_words_lane(size_t lane, size_t dst, const uint32_t* w, size_t count) { need_lane(lane, "set_words"); set_words(dst, w, count); }
+  virtual void get_words_lane(size_t lane, size_t src, uint32_t* w, size_t count) { need_lane(lane, "get_words"); get_words(src, w, count); }
+  virtual uint64_t res64_lane(size_t lane, size_t src) { need_lane(lane, "res64"); return res64(src); }
+
   virtual size_t register_data_size() const = 0;                              // raw register images (engine.h:134-146)
   virtual void get_data(size_t src, void* data, size_t size) = 0;
   virtual void set_data(size_t dst, const void* data, size_t size) = 0;
@@ -138,6 +145,9 @@ class RegisterMachine {
   // argument checks, run before an operation's first launch
   void need_register(size_t reg, const char* op) const {
     if (reg >= reg_count()) throw std::runtime_error(std::string(op) + ": register index out of range");
+  }
+  void need_lane(size_t lane, const char* op) const {
+    if (lane >= lanes()) throw std::runtime_error(std::string(op) + ": lane index out of range (the engine has " + std::to_string(lanes()) + ")");
   }
   void need_residue(size_t reg, const char* op) const {
     need_register(reg, op);

@@ -1,6 +1,6 @@
 """ECM factoring of a Mersenne number 2^p - 1 on the engine: Montgomery curves, stages 1 and 2 (the reference: src/modes/RunEcm.cpp).
 
-    python -m prmers_amd.ecm P B1 [B2] [--sigma S] [--curves N] [--D 30|210|2310] [--plan SPEC] [--device N]
+    python -m prmers_amd.ecm P B1 [B2] [--sigma S] [--curves N] [--lanes B] [--D 30|210|2310] [--plan SPEC] [--device N]
 
 Curve:    Suyama's parametrisation from sigma: u = sigma^2 - 5, v = 4 sigma, the point (u^3 : v^3) on B y^2 = x^3 + A x^2 + x with
           a24 = (A + 2) / 4 = (v - u)^3 (3 u + v) / (16 u^3 v).  The start is taken affine, x0 = u^3 / v^3 and Z = 1: one modular inversion
@@ -22,7 +22,11 @@ Stage 2:  the standard continuation on x-coordinates over the wheel D: every pri
           it).  0 Q = (1 : 0) is a valid giant point: the k = 0 terms are Z_j.
 
 The driver works on anything with the interface of prmers_amd.Engine; addsub and square_mul_prepare are used when the object has them
-and replaced by the compositions they stand for when it has not.  Not here: twisted Edwards curves, PRAC chains,
+and replaced by the compositions they stand for when it has not.
+Lanes:    all curves of a batch make the same engine calls (the ladder bits come from B1, the stage-2 pairs from B1, B2 and D); only x0 and
+          a24 differ.  run_lanes() puts curve l into lane l of an engine with lanes (Engine(..., lanes=B), include/mi355_lanes.h) and
+          issues the calls of one run(): B curves per launch sequence.  --lanes B / ecm(lanes=B) batches the curves that way.
+Not here: twisted Edwards curves, PRAC chains,
 checkpoints, ECM= worktodo lines, the PrimeNet JSON, a C++ twin.
 """
 import argparse
@@ -222,14 +226,13 @@ class _Curve:
                 self.add(r1, r0, r1, pt); self.dbl(r0, r0)
 
 
-def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None):
-    """One curve of ECM on 2^p - 1 with bounds B1 and B2 (B2 <= B1: stage 1 only) on `eng`, an engine for exponent p with at least
-    FIXED_REGISTERS registers (stage 1) or registers_needed(D) (stage 2).  use_fused=False forces set_multiplicand + square_mul in
-    place of square_mul_prepare.  Afterwards registers R_XQ, R_ZQ hold the stage-1 point.
-    -> {p, b1, b2, D, sigma, factors, g1, g2, squarings, products, prepares, fused}"""
+def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane):
+    """The curves of `sigmas` through one sequence of engine calls: the ladder bits come from B1 and the stage-2 pairs from (B1, B2, D),
+    so only the data differ.  by_lane=False: one curve on an engine used as it is (run).  by_lane=True: curve l in lane l of an engine
+    with len(sigmas) lanes (run_lanes); every engine call then acts on all of them.  -> one result per curve"""
     if b1 < 2:
         raise ValueError("B1 must be at least 2")
-    if sigma < SIGMA_MIN:
+    if min(sigmas) < SIGMA_MIN:
         raise ValueError("sigma must be at least %d" % SIGMA_MIN)
     mp = (1 << p) - 1
     have = getattr(eng, "reg_count", None)
@@ -245,15 +248,35 @@ def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None)
         raise ValueError("the engine has %d registers, ECM with D = %s needs %d" % (have, D if stage2 else None, need))
     ops = _Ops(eng, use_fused)
     cv = _Curve(ops)
+    lanes = range(len(sigmas))
 
-    def result(g1, g2):
-        return {"p": p, "b1": b1, "b2": b2 if stage2 else 0, "D": D if stage2 else None, "sigma": sigma,
-                "factors": [f for f in (g1, g2) if 1 < f < mp], "g1": g1, "g2": g2,
-                "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused}
+    def put(reg, values):
+        if not by_lane:
+            eng.set_int(reg, values[0])
+            return
+        eng.set(reg, 0)          # a lane is written into a register of residues; the register may hold an image of the last batch
+        for l in lanes:
+            eng.set_int(reg, values[l], lane=l)
 
-    x0, a24, g = suyama(sigma, mp, use_gmp)
-    if g != 1:
-        return result(g, 1)      # the inversion failed: its argument shares g with Mp
+    def get(reg):
+        return [eng.get_int(reg, lane=l) for l in lanes] if by_lane else [eng.get_int(reg)]
+
+    def results(g1, g2):
+        return [{"p": p, "b1": b1, "b2": b2 if stage2 else 0, "D": D if stage2 else None, "sigma": sigmas[l],
+                 "factors": [f for f in (g1[l], g2[l]) if 1 < f < mp], "g1": g1[l], "g2": g2[l],
+                 "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused} for l in lanes]
+
+    setup = [suyama(s, mp, use_gmp) for s in sigmas]
+    failed = [g != 1 for _, _, g in setup]   # the inversion failed: its argument shares g with Mp, which is the curve's result
+    g1 = [g if bad else 1 for (_, _, g), bad in zip(setup, failed)]
+    g2 = [1] * len(sigmas)
+    if all(failed):
+        return results(g1, g2)
+    if any(failed):              # such a lane rides along on a valid curve whose outcome is dropped
+        s = SIGMA_MIN
+        while suyama(s, mp, use_gmp)[2] != 1:
+            s += 1
+        setup = [suyama(s, mp, use_gmp) if bad else c for c, bad in zip(setup, failed)]
 
     # ---- stage 1 ----
     e = stage1_exponent(b1)
@@ -261,10 +284,10 @@ def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None)
         for q in (2, 3, 5, 7, 11):
             if D % q == 0 and b1 < q <= b2:
                 e *= q
-    eng.set_int(R_A24, a24); ops.prep(R_A24, R_A24)
-    eng.set_int(R_X0, x0); ops.prep(R_X0, R_X0)
+    put(R_A24, [c[1] for c in setup]); ops.prep(R_A24, R_A24)
+    put(R_X0, [c[0] for c in setup]); ops.prep(R_X0, R_X0)
     a, b = (R_XA, R_ZA), (R_XB, R_ZB)
-    eng.set_int(R_XA, x0); eng.set(R_ZA, 1)
+    put(R_XA, [c[0] for c in setup]); eng.set(R_ZA, 1)
     cv.dbl(b, a)                                 # (a, b) = (P, 2 P)
     for i in range(e.bit_length() - 2, -1, -1):
         if (e >> i) & 1:
@@ -273,12 +296,12 @@ def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None)
             cv.ladder_step(a, b)
     Q = (R_XQ, R_ZQ)
     eng.copy(R_XQ, a[0]); eng.copy(R_ZQ, a[1])
-    z = eng.get_int(R_ZQ)
-    g1 = mp if z == 0 else big_gcd(z, mp, use_gmp)
-    g2 = 1
+    for l, z in enumerate(get(R_ZQ)):
+        if not failed[l]:
+            g1[l] = mp if z == 0 else big_gcd(z, mp, use_gmp)
 
     # ---- stage 2 ----
-    if stage2 and g1 != mp:
+    if stage2 and any(g1[l] != mp for l in lanes if not failed[l]):
         J = residues(D)
         slot = {j: (FIXED_REGISTERS + 2 * i, FIXED_REGISTERS + 2 * i + 1) for i, j in enumerate(J)}
         pairs = stage2_pairs(b1, b2, D)
@@ -321,30 +344,71 @@ def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None)
                     cur, nxt, spare = nxt, spare, cur
                 else:
                     cur, nxt = nxt, cur
-            acc = eng.get_int(R_A)
-            g = mp if acc == 0 else big_gcd(acc, mp, use_gmp)
-            g2 = g // big_gcd(g, g1, use_gmp)
-    return result(g1, g2)
+            for l, acc in enumerate(get(R_A)):
+                if not failed[l] and g1[l] != mp:   # (a curve whose stage 1 gave Mp itself has no stage 2)
+                    g = mp if acc == 0 else big_gcd(acc, mp, use_gmp)
+                    g2[l] = g // big_gcd(g, g1[l], use_gmp)
+    return results(g1, g2)
 
 
-def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0):
+def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None):
+    """One curve of ECM on 2^p - 1 with bounds B1 and B2 (B2 <= B1: stage 1 only) on `eng`, an engine for exponent p with at least
+    FIXED_REGISTERS registers (stage 1) or registers_needed(D) (stage 2).  use_fused=False forces set_multiplicand + square_mul in
+    place of square_mul_prepare.  Afterwards registers R_XQ, R_ZQ hold the stage-1 point.
+    -> {p, b1, b2, D, sigma, factors, g1, g2, squarings, products, prepares, fused}"""
+    return _run_curves(eng, p, b1, b2, [sigma], D, use_fused, use_gmp, False)[0]
+
+
+def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None):
+    """len(sigmas) == eng.lanes curves at once on an engine with lanes (Engine(..., lanes=B)), curve l in lane l: the engine calls of ONE
+    run(), each of which acts on every lane.  x0 and a24 are written lane by lane, the stage-1 Z and the stage-2 accumulator read back
+    and gcd'd lane by lane.  A curve whose inversion fails reports that factor as run() does; its lane carries a valid curve whose
+    outcome is dropped.  -> one result per curve in the shape of run(); squarings, products and prepares are those of the batch, which
+    are those of one curve."""
+    sigmas = list(sigmas)
+    if len(sigmas) != getattr(eng, "lanes", 1) or not sigmas:
+        raise ValueError("run_lanes needs one sigma per lane: %d given, the engine has %d lanes" % (len(sigmas), getattr(eng, "lanes", 1)))
+    return _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, True)
+
+
+def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0, lanes=1):
     """`curves` curves of run() on a fresh prmers_amd.Engine sized for the chosen D, until one finds a factor.  sigma: the first curve's
-    (None: drawn like the others, from random.Random(seed)).  -> the result of the last curve run, with "sigmas": every sigma used."""
+    (None: drawn like the others, from random.Random(seed)).  -> the result of the last curve run, with "sigmas": every sigma used.
+    lanes = B > 1: the curves run B at a time through run_lanes() on one engine with B lanes (whole batches: `curves` rounded up to a
+    multiple of B), sigmas drawn from the same generator in the same order, until a batch in which some lane finds a factor.  -> the
+    result of that batch's first curve with a factor (of the last curve run when there is none), "factors": those of all its lanes,
+    "sigmas": every sigma of every batch run, "batch": the last batch's results, one per lane."""
     from .engine import Engine, resolve_plan
+    if lanes < 1:
+        raise ValueError("lanes must be at least 1")
     if b2 > b1 and D is None:
         n = int(resolve_plan(p, plan).split("n=")[1].split(":")[0])
-        D = choose_D(n, b1, b2, budget)
+        D = choose_D(n, b1, b2, budget // lanes)
     regs = registers_needed(D) if b2 > b1 else FIXED_REGISTERS
     rng = random.Random(seed)
     sigmas = []
     res = None
-    with Engine(p, regs, device=device, plan=plan) as eng:
-        for c in range(max(1, curves)):
-            s = sigma if (c == 0 and sigma is not None) else rng.randrange(SIGMA_MIN, 1 << 32)
-            sigmas.append(s)
-            res = run(eng, p, b1, b2, s, D)
-            if res["factors"]:
-                break
+
+    def draw():
+        s = sigma if (not sigmas and sigma is not None) else rng.randrange(SIGMA_MIN, 1 << 32)
+        sigmas.append(s)
+        return s
+    if lanes == 1:
+        with Engine(p, regs, device=device, plan=plan) as eng:
+            for c in range(max(1, curves)):
+                res = run(eng, p, b1, b2, draw(), D)
+                if res["factors"]:
+                    break
+    else:
+        with Engine(p, regs, device=device, plan=plan, lanes=lanes) as eng:
+            for c in range(0, max(1, curves), lanes):
+                batch = run_lanes(eng, p, b1, b2, [draw() for _ in range(lanes)], D)
+                found = [r for r in batch if r["factors"]]
+                res = dict(found[0] if found else batch[-1])
+                res["factors"] = sorted({f for r in batch for f in r["factors"]})
+                res["batch"] = batch
+                if found:
+                    break
     res["sigmas"] = sigmas
     return res
 
@@ -361,8 +425,9 @@ def main(argv=None):
     ap.add_argument("--budget-gib", type=float, default=DEFAULT_BUDGET / 2**30)
     ap.add_argument("--plan", default=None)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--lanes", type=int, default=1, help="curves per batch: an engine with this many lanes runs them in one launch sequence")
     a = ap.parse_args(argv)
-    res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed)
+    res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed, a.lanes)
     print(json.dumps(res))
     return 0 if res["factors"] else 1
 

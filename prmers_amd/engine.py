@@ -88,8 +88,15 @@ def load_library():
         "mi355_engine_describe": (C.c_int, [vp, C.c_char_p, sz]),
         "mi355_crt_get_raw_digits": (C.c_int, [vp, sz, vp, sz, C.c_int]),
         "mi355_crt_set_raw_digits": (C.c_int, [vp, sz, vp, sz]),
+        # include/mi355_lanes.h
+        "mi355_lanes_count": (sz, [vp]),
+        "mi355_lanes_set_words": (C.c_int, [vp, sz, sz, vp, sz]),
+        "mi355_lanes_get_words": (C.c_int, [vp, sz, sz, vp, sz]),
+        "mi355_lanes_res64": (C.c_int, [vp, sz, sz, u64p]),
     }
     for name, (res, args) in sig.items():
+        if name in LANE_EXPORTS and os.environ.get("MI355_ENGINE_LIB") and not hasattr(L, name):
+            continue           # an A/B library from before the lanes (tools/time_lanes.py): plain engines only, Engine.lanes reads 1
         f = getattr(L, name)   # AttributeError here = the library does not export what the header declares
         f.restype, f.argtypes = res, args
     _lib = L
@@ -112,6 +119,10 @@ EXPORTS = [
     "mi355_engine_mul_sum", "mi355_engine_mul_sum_is_fused", "mi355_engine_square_mul_bits",
     "mi355_engine_square_mul_prepare", "mi355_engine_square_mul_prepare_is_fused",
 ]
+
+
+# include/mi355_lanes.h: per-lane I/O of engines created with the plan token lanes=B
+LANE_EXPORTS = ["mi355_lanes_count", "mi355_lanes_set_words", "mi355_lanes_get_words", "mi355_lanes_res64"]
 
 
 def resolve_plan(p, spec=None):
@@ -153,12 +164,17 @@ def u32_arg(name, v):
 class Engine:
     """engine::create_gpu(p, reg_count, device, verbose) on an MI355X (include/marin/engine.h:301)."""
 
-    def __init__(self, p, reg_count=8, device=0, verbose=False, plan=None):
+    def __init__(self, p, reg_count=8, device=0, verbose=False, plan=None, lanes=1):
+        """lanes = B > 1: B independent residues per register, every operation on all of them in one launch (include/mi355_lanes.h);
+        reads then take lane=l, writes lane=l or None for every lane."""
         self.L = load_library()
+        if lanes != 1:
+            plan = (plan + "," if plan else "") + "lanes=%d" % operator.index(lanes)
         self.h = self.L.mi355_engine_create(p, reg_count, device, int(verbose), plan.encode() if plan else None, None)
         if not self.h:
             raise EngineError(self.L.mi355_engine_last_error().decode())
         self.p, self.reg_count = p, reg_count
+        self.lanes = self.L.mi355_lanes_count(self.h) if hasattr(self.L, "mi355_lanes_count") else 1
         self.n = self.L.mi355_engine_transform_size(self.h)
         self.word_count = self.L.mi355_engine_word_count(self.h)
 
@@ -265,30 +281,41 @@ class Engine:
         d = np.ascontiguousarray(d, dtype=np.uint64)
         self._ok(self.L.mi355_engine_set_digits(self.h, dst, _ptr(d), d.size))
 
-    def res64(self, src):
+    # lane=None: the register as a whole -- today's call on an engine without lanes; with lanes a write goes to every lane and a read
+    # is refused (name the lane).  lane=l: that lane (l = 0 is the register itself on an engine without lanes).
+    def res64(self, src, lane=None):
         out = C.c_uint64(0)
-        self._ok(self.L.mi355_engine_res64(self.h, src, C.byref(out)))
+        if lane is None:
+            self._ok(self.L.mi355_engine_res64(self.h, src, C.byref(out)))
+        else:
+            self._ok(self.L.mi355_lanes_res64(self.h, lane, src, C.byref(out)))
         return out.value
 
-    def words(self, src):
+    def words(self, src, lane=None):
         w = np.zeros(self.word_count, dtype=np.uint32)
-        self._ok(self.L.mi355_engine_get_words(self.h, src, _ptr(w), w.size))
+        if lane is None:
+            self._ok(self.L.mi355_engine_get_words(self.h, src, _ptr(w), w.size))
+        else:
+            self._ok(self.L.mi355_lanes_get_words(self.h, lane, src, _ptr(w), w.size))
         return w
 
     get_words = words
 
-    def set_words(self, dst, w):
+    def set_words(self, dst, w, lane=None):
         w = np.ascontiguousarray(w, dtype=np.uint32)
-        self._ok(self.L.mi355_engine_set_words(self.h, dst, _ptr(w), w.size))
+        if lane is None:
+            self._ok(self.L.mi355_engine_set_words(self.h, dst, _ptr(w), w.size))
+        else:
+            self._ok(self.L.mi355_lanes_set_words(self.h, lane, dst, _ptr(w), w.size))
 
-    def get_int(self, src):
+    def get_int(self, src, lane=None):
         """get_mpz (engine.h:173-203) as a Python int in [0, 2^p-1)."""
-        return int.from_bytes(self.words(src).astype("<u4").tobytes(), "little")
+        return int.from_bytes(self.words(src, lane).astype("<u4").tobytes(), "little")
 
-    def set_int(self, dst, v):
+    def set_int(self, dst, v, lane=None):
         """set_mpz (engine.h:206-232); v is reduced mod 2^p-1 first."""
         v = int(v) % ((1 << self.p) - 1)
-        self.set_words(dst, np.frombuffer(v.to_bytes(self.word_count * 4, "little"), dtype="<u4"))
+        self.set_words(dst, np.frombuffer(v.to_bytes(self.word_count * 4, "little"), dtype="<u4"), lane)
 
     # --- raw images / checkpoints ---
     def get_register_data_size(self): return self.L.mi355_engine_register_data_size(self.h)
