@@ -6,6 +6,9 @@ two and three engines from threads that construct them at the same moment.  Ever
 (When these tests were written every case passed on an MI355X as the library stood: a kernel whose attribute a later engine had set to
 64 KiB still launched with 128 KiB of dynamic LDS, as the HIP header's remark that AMD devices ignore the attribute suggests.  The
 tests pin that; should a runtime start to enforce the attribute, configure_kernels / configure_split have to keep a running maximum.)
+Lane engines (plan token lanes=B) set the same attribute on kernels of their own (configure_lane_kernels); they appear in both parts, beside a
+plain engine of the same plan and beside a lane engine of another tile size and lane count, and run the program of lane_program.py, every
+lane compared with its integer model.
 One engine used from two threads is not a supported pattern and is not tested.
 Needs a real MI355X:  python -m pytest tests -m gpu"""
 import threading
@@ -15,6 +18,7 @@ import numpy as np
 import pytest
 
 import orc
+from lane_program import OUT_REGS, REGS, expected_of, inputs, mulmod, run_program
 
 pytestmark = pytest.mark.gpu
 
@@ -40,6 +44,19 @@ def CRT(p, odd, text):
         assert e.describe() == text, (p, odd, e.describe())
         return e
     make.p = p
+    return make
+
+
+def L(p, plan, lanes):
+    """an engine of REGS registers and `lanes` lanes (1: a plain engine) that runs the program of lane_program.py"""
+    def make():
+        from prmers_amd import Engine
+        from prmers_amd.engine import resolve_plan
+        e = Engine(p, REGS, plan=plan, lanes=lanes)
+        assert e.lanes == lanes and e.describe() == resolve_plan(p, plan) + (":lanes=%d" % lanes if lanes > 1 else ""), (p, plan, lanes, e.describe())
+        return e
+    make.p, make.lanes = p, lanes
+    make.inputs = inputs(p, lanes=lanes)
     return make
 
 
@@ -73,7 +90,47 @@ PAIRS = {
     "same kernels, different exponent": (None, G(300007, "m2=4096", "marin-hip:n=16384:m1=2:m2=4096:c=16"),
                                          G(301447, "m2=4096", "marin-hip:n=16384:m1=2:m2=4096:c=16")),
     "both families": (None, G(9941, None, "marin-hip:n=512:m1=8:m2=32:c=4"), CRT(9941, 9, CRT_9941)),
+    # lane engines: an 80 KiB column tile beside the plain engine of the same plan (radix-5 resident columns), and beside a lane engine of
+    # another tile size (20 KiB) and lane count
+    "lanes beside a plain engine of the same plan": (None, L(1600589, "m2=32,c=4", 2), L(1600589, "m2=32,c=4", 1)),
+    "lanes beside lanes, LDS 80 KiB vs 20 KiB": (None, L(1600589, "m2=32,c=4", 2), L(3021377, None, 5)),
 }
+
+
+def check_program(e, want, what):
+    for l in range(e.lanes):
+        for r in OUT_REGS:
+            assert e.get_int(r, lane=l) == want[l][r], (what, e.p, "lane", l, "register", r)
+
+
+def program_in_turn(make_first, make_second):
+    """in_turn for engines that run the program of lane_program.py (with lanes, or lane 0 of a plain engine)"""
+    pf = make_first.p
+    want_first, want_second = expected_of(pf, make_first.inputs), expected_of(make_second.p, make_second.inputs)
+    first = make_first()
+    try:
+        run_program(first, make_first.inputs)
+        second = make_second()          # the process-wide attributes are now the second engine's
+        try:
+            run_program(second, make_second.inputs)
+            check_program(second, want_second, "second engine")
+            # back on the first one, with the second alive: what it holds, then both row modes and a back sweep with a copy
+            check_program(first, want_first, "first engine, second alive")
+            first.square_mul_copy(0, 1, 3)
+            first.mul(4, 3)
+            y = [v[1] for v in make_first.inputs]
+            for l in range(first.lanes):
+                sq = mulmod(pf, want_first[l][0], want_first[l][0], 3)
+                assert first.get_int(0, lane=l) == first.get_int(1, lane=l) == sq, ("first engine, squared", "lane", l)
+                assert first.get_int(4, lane=l) == mulmod(pf, want_first[l][4], y[l]), ("first engine, multiplied", "lane", l)
+            check_program(second, want_second, "second engine, after the first ran")
+        finally:
+            second.close()
+        first.square_mul(5)
+        for l in range(first.lanes):
+            assert first.get_int(5, lane=l) == mulmod(pf, want_first[l][5], want_first[l][5]), ("first engine, second closed", "lane", l)
+    finally:
+        first.close()
 
 
 def in_turn(make_first, make_second):
@@ -122,7 +179,8 @@ def test_two_engines_created_and_used_in_turn(shared, order, monkeypatch):
     kernels, a, b = PAIRS[shared]
     set_switches(monkeypatch, **({"MI355_KERNELS": kernels} if kernels else {}))
     t0 = time.time()
-    in_turn(a, b) if order == "first-then-second" else in_turn(b, a)
+    turn = program_in_turn if hasattr(a, "lanes") else in_turn
+    turn(a, b) if order == "first-then-second" else turn(b, a)
     print("in turn, %s, %s: %.2f s" % (shared, order, time.time() - t0))
 
 
@@ -184,6 +242,19 @@ def chain_on(make, x0, marks, own_error=None):
     return fn
 
 
+PROGRAM_ROUNDS = 8
+
+
+def program_on(make, want):
+    """chain_on for an engine that runs the program of lane_program.py: PROGRAM_ROUNDS times, every lane checked after each"""
+    def fn(i):
+        with make() as e:
+            for r in range(PROGRAM_ROUNDS):
+                run_program(e, make.inputs)
+                check_program(e, want, "thread %d, round %d" % (i, r))
+    return fn
+
+
 P4096 = G(300007, "m2=4096", "marin-hip:n=16384:m1=2:m2=4096:c=16")
 THREADED = {
     "the same exponent and plan twice": [P4096, P4096],
@@ -192,6 +263,7 @@ THREADED = {
     "both families": [G(9941, None, "marin-hip:n=512:m1=8:m2=32:c=4"), CRT(9941, 9, CRT_9941)],
     "three threads": [G(9941, None, "marin-hip:n=512:m1=8:m2=32:c=4"), G(9949, None, "marin-hip:n=512:m1=8:m2=32:c=4"),
                       G(11213, None, "marin-hip:n=512:m1=8:m2=32:c=4")],
+    "a lane engine with a plain engine of its plan": [L(301447, None, 9), L(301447, None, 1)],
 }
 
 
@@ -199,9 +271,14 @@ THREADED = {
 def test_engines_constructed_and_driven_from_threads_at_once(case, monkeypatch):
     set_switches(monkeypatch)
     makers = THREADED[case]
-    models = [chain_model(m.p, 10 + i) for i, m in enumerate(makers)]     # before the threads start
+    # the models before the threads start
+    if hasattr(makers[0], "lanes"):
+        targets = [program_on(m, expected_of(m.p, m.inputs)) for m in makers]
+    else:
+        models = [chain_model(m.p, 10 + i) for i, m in enumerate(makers)]
+        targets = [chain_on(m, x0, marks) for m, (x0, marks) in zip(makers, models)]
     t0 = time.time()
-    run_threads([chain_on(m, x0, marks) for m, (x0, marks) in zip(makers, models)])
+    run_threads(targets)
     print("threads, %s: %.2f s" % (case, time.time() - t0))
 
 

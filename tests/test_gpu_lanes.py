@@ -2,14 +2,14 @@
 A register-machine program per lane against Python integers mod 2^p - 1, isolation between lanes, the per-lane I/O and what a lane
 engine refuses, and ECM with one curve per lane against ecm.run on a plain engine.
 Needs a real MI355X:  python -m pytest tests -m gpu"""
-import ctypes
 import random
 
 import numpy as np
 import pytest
 
 import orc
-from prmers_amd import ecm, pm1
+from lane_program import MAX_LANES, OUT_REGS, REGS, _bigmul, expected, inputs, model, run_program  # noqa: F401 -- the program and its model
+from prmers_amd import ecm
 
 pytestmark = pytest.mark.gpu
 
@@ -26,108 +26,7 @@ SHAPES = [
     (9815459, None),           # 256 x 1024: the default is the radix-4 sets; several groups per lane
 ]
 LANES = [2, 3, 5]              # an odd count; more lanes than tiles at the small sizes
-MAX_LANES = max(LANES)
-REGS = 10
-
-
-# ---- integers mod 2^p - 1 (products through libgmp where it loads: Python's own take seconds each at 10^7 bits) ----
-
-def _bigmul(a, b):
-    G = pm1.load_gmp()
-    if G is None or max(a.bit_length(), b.bit_length()) < 100000:
-        return a * b
-    P = ctypes.POINTER(G.Mpz)
-    G.__gmpz_mul.argtypes = [P, P, P]
-    za, zb = G.Mpz(), G.Mpz()
-    for z in (za, zb):
-        G.__gmpz_init(ctypes.byref(z))
-    try:
-        for z, v in ((za, a), (zb, b)):
-            raw = v.to_bytes((v.bit_length() + 7) // 8 or 1, "little")
-            G.__gmpz_import(ctypes.byref(z), len(raw), -1, 1, -1, 0, raw)
-        G.__gmpz_mul(ctypes.byref(za), ctypes.byref(za), ctypes.byref(zb))
-        size = (G.__gmpz_sizeinbase(ctypes.byref(za), 2) + 7) // 8
-        buf = ctypes.create_string_buffer(size or 1)
-        count = ctypes.c_size_t(0)
-        G.__gmpz_export(buf, ctypes.byref(count), -1, 1, -1, 0, ctypes.byref(za))
-        return int.from_bytes(buf.raw[:count.value], "little")
-    finally:
-        for z in (za, zb):
-            G.__gmpz_clear(ctypes.byref(z))
-
-
-def inputs(p, seed=0):
-    """(x, y, z) for MAX_LANES lanes: seeded full-size operands; lane 0 has x = 2^p - 2, lane 1 has x = 0"""
-    rng = random.Random(1000 * p + seed)
-    mp = (1 << p) - 1
-    lanes = [[rng.getrandbits(p) % mp for _ in range(3)] for _ in range(MAX_LANES)]
-    lanes[0][0] = mp - 1
-    lanes[1][0] = 0
-    return lanes
-
-
-def model(p, x, y, z):
-    """the program of run_program on integers -> the values of registers 0, 4, 5, 6, 7"""
-    mp = (1 << p) - 1
-
-    def mul(a, b, f=1):
-        return orc.mers_reduce(_bigmul(a, b) * f, p)
-    r0 = mul(x, x)
-    r0 = mul(r0, r0, 3)                    # 1  square_mul, factors 1 and 3
-    r0 = (r0 - 5) % mp                     # 2  sub
-    r0 = mul(r0, y)                        # 3, 4  set_multiplicand, mul
-    r0 = (r0 + z) % mp                     # 5  add
-    r0 = (r0 - y) % mp                     # 6  sub_reg
-    r4, r5 = (r0 + z) % mp, (r0 - z) % mp  # 7  addsub
-    r4 = (mul(r4, y) + r5) % mp            # 8  mul_add
-    r4 = mul(r4, r4, 2); r6 = r4           # 9  square_mul_copy
-    r6 = mul(r6, y); r7 = r6               # 10 mul_copy
-    r7 = mul(r7, (y + z) % mp)             # 11 mul_sum
-    old5 = r5
-    r5 = mul(r5, r5); r7 = mul(r7, old5)   # 12 square_mul_prepare, then a mul by its image
-    for _ in range(5):
-        r7 = (mul(r7, r7) - 2) % mp        # 13 square_mul_n(..., 5, sub=2)
-    return {0: r0, 4: r4, 5: r5, 6: r6, 7: r7}
-
-
-OUT_REGS = (0, 4, 5, 6, 7)
-
-
-def run_program(e, lane_inputs):
-    """every operation runs while the last result's run carries are still pending: nothing is read in between"""
-    for r in (0, 1, 2):
-        e.set(r, 0)
-        for l, v in enumerate(lane_inputs):
-            e.set_int(r, v[r], lane=l)
-    e.square_mul(0, 1); e.square_mul(0, 3)
-    e.sub(0, 5)
-    e.set_multiplicand(3, 1)
-    e.mul(0, 3)
-    e.add(0, 2)
-    e.sub_reg(0, 1)
-    e.addsub(4, 5, 0, 2)
-    e.mul_add(4, 3, 5)
-    e.square_mul_copy(4, 6, 2)
-    e.mul_copy(6, 3, 7)
-    e.set_multiplicand(8, 2)
-    e.mul_sum(7, 3, 8, 9)
-    e.square_mul_prepare(5, 9)
-    e.mul(7, 9)
-    e.square_mul_n(7, 5, 1, 2)
-
-
-_expected = {}
-
-
-def expected(p, lanes=MAX_LANES, lane_inputs=None):
-    """the model's registers for the first `lanes` lanes of inputs(p): each lane computed once and shared by the tests that need it"""
-    if lane_inputs is not None:
-        return [model(p, *v) for v in lane_inputs]
-    ins = inputs(p)
-    for l in range(lanes):
-        if (p, l) not in _expected:
-            _expected[(p, l)] = model(p, *ins[l])
-    return [_expected[(p, l)] for l in range(lanes)]
+assert MAX_LANES == max(LANES)
 
 
 # ---- (a) the program per lane ----
@@ -285,3 +184,36 @@ def test_ecm_entry_point_with_lanes():
     rc = ecm.main([str(p), "50", "--sigma", "6", "--curves", "2", "--lanes", "2", "--seed", "5"])
     found = ecm.ecm(p, 50, 0, sigma=6, curves=2, lanes=2, seed=5)["factors"]
     assert rc == (0 if found else 1)
+
+
+# ---- (f) ECM at 64 lanes ----
+
+WIDE_P, WIDE_F, WIDE_NAMED = 3001, 3217073, [6, 8, 3217073, 36]      # tests/test_lanes_host.py: the third inversion fails on the factor
+
+
+def test_ecm_at_64_lanes_matches_64_single_curves():
+    from prmers_amd import Engine
+    p, b1, b2, D = WIDE_P, 30, 300, 30
+    rng = random.Random(7)
+    sigmas = WIDE_NAMED + [rng.randrange(ecm.SIGMA_MIN, 1 << 32) for _ in range(60)]
+    assert len(sigmas) == len(set(sigmas)) == 64 and pow(2, p, WIDE_F) == 1
+    regs = ecm.registers_needed(D)
+    with Engine(p, regs) as e:
+        single = [ecm.run(e, p, b1, b2, s, D) for s in sigmas]
+    oracle = []
+    for s in WIDE_NAMED:
+        with orc.OracleEngine(p, regs) as o:
+            oracle.append(ecm.run(o, p, b1, b2, s, D))
+    with Engine(p, regs, lanes=64) as e:
+        out = ecm.run_lanes(e, p, b1, b2, sigmas, D)
+    assert len(out) == 64
+    for l, s in enumerate(sigmas):
+        assert out[l]["sigma"] == s, ("lane", l)
+        assert (out[l]["g1"], out[l]["g2"], out[l]["factors"]) == (single[l]["g1"], single[l]["g2"], single[l]["factors"]), ("lane", l, "sigma", s)
+        for f in out[l]["factors"]:
+            assert pow(2, p, f) == 1, ("lane", l, "sigma", s, f)
+    for l, ref in enumerate(oracle):
+        assert (out[l]["g1"], out[l]["g2"], out[l]["factors"]) == (ref["g1"], ref["g2"], ref["factors"]), ("lane", l, "against the CPU oracle")
+    bad = WIDE_NAMED.index(WIDE_F)
+    assert out[bad]["g1"] % WIDE_F == 0 and out[bad]["g2"] == 1 and single[bad]["squarings"] == 0   # the failed inversion reports the factor
+    assert [l for l in range(64) if l != bad and any(f % WIDE_F == 0 for f in out[l]["factors"])]     # and a curve finds it
