@@ -64,7 +64,6 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
 
   reg_bytes_ = pl_.n * 8;  // digits use the first 4n bytes, a multiplicand image all 8n
   lanes_ = pl_.lanes;
-  lg_ = LaneGeom{uint32_t(lanes_), reg_bytes_, pl_.runs()};
   const size_t slot_bytes = lanes_ * reg_bytes_, cb_words = lanes_ * pl_.runs();   // a slot is `lanes` registers, one behind the other
   HIPCHK(hipMalloc(reinterpret_cast<void**>(&regs_), (nregs_ + 1) * slot_bytes));
   HIPCHK(hipMemsetAsync(regs_, 0, (nregs_ + 1) * slot_bytes, stream_));
@@ -111,6 +110,7 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
   dp_.n = uint32_t(pl_.n); dp_.m = uint32_t(pl_.m);
   dp_.M1 = pl_.M1; dp_.M2 = pl_.M2; dp_.L1 = pl_.L1; dp_.logL1 = pl_.logL1; dp_.logM2 = pl_.logM2;
   dp_.r5 = pl_.r5; dp_.C = pl_.C; dp_.logC = 0; while ((1u << dp_.logC) < pl_.C) ++dp_.logC; dp_.q = pl_.q; dp_.t = pl_.t; dp_.twh = pl_.twh;
+  dp_.lanes = pl_.lanes;
   dp_.I4 = pl_.I4; dp_.I4inv = pl_.I4inv;
   dp_.DI = nullptr;
   dp_.F0f = dp_.F0i = dp_.FBf = dp_.FBi = nullptr;
@@ -129,16 +129,15 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
     const uint32_t slots = 2u * uint32_t(prop.multiProcessorCount);
     auto from = [&](size_t grid) { return grid > slots ? uint32_t(grid - size_t(slots) * 50 / 100) : ~0u; };
     dp_.boost_rows = from(pl_.M2 == 2048 ? pl_.M1 / 2 : pl_.M1);   // (rows of 2048 go two to a tile on the register-resident row kernel)
-    dp_.boost_tiles = from(pl_.tiles());
+    dp_.boost_tiles = lanes_ > 1 ? ~0u : from(pl_.tiles());   // with a lane dimension the last half round of a launch is not the top of blockIdx.x
   }
-  HIPCHK(configure_kernels(pl_.lds_front, pl_.lds_mid));
-  if (lanes_ > 1) HIPCHK(configure_lane_kernels(pl_.lds_front, pl_.lds_mid));
+  HIPCHK(configure_kernels(pl_.lds_front, pl_.lds_mid, pl_.lanes));
   if (pl_.split5) {
     HIPCHK(configure_split(dp_));
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&split_), reg_bytes_));
   }
   // kernel variants: those that serve the shape (plan.hpp), narrowed by MI355_KERNELS=generic|v2rows|v2cols (A/B tests, debugging);
-  // with lanes always the generic set, launched through the lane entry points (run_front ... below)
+  // with lanes always the generic set, whose launches take the lanes as grid.y (kernels.hpp DevPlan.lanes)
   kc_ = choose_kernels(pl_, std::getenv("MI355_KERNELS"));
   cols_ = col_sweeps(kc_.cols);
   rows_ = row_sweep(kc_.rows);
@@ -192,7 +191,7 @@ void Engine::sync() {
 void Engine::normalize(size_t r) {
   if (kind_[r] != kDigits) return;
   if (pending_carry_[r]) {
-    HIPCHK(lanes_ > 1 ? launch_carry_fix_lanes(dp_, lg_, digits(r), cbuf(r), stream_) : launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
+    HIPCHK(launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
     pending_carry_[r] = 0;
   }
 }
@@ -202,7 +201,7 @@ void Engine::normalize(size_t r) {
 // run's second digit, log2(n) - 2 (+ log2 a) bits above its width -- too much for the next squaring once that exceeds w.
 // Local carry passes (canon.hip k_relax) take w bits off per pass; as many as it takes to get below the width follow.
 void Engine::carry_fix_now(size_t r, int excess) {
-  HIPCHK(lanes_ > 1 ? launch_carry_fix_lanes(dp_, lg_, digits(r), cbuf(r), stream_) : launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
+  HIPCHK(launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
   pending_carry_[r] = 0;
   if (pl_.C >= 2) return;
   if (excess < 0) excess = ilog2(pl_.n) + 1 + 4 - 2;   // log2(n) rounded up, factor a up to 15 (plan.hpp a_fast)
@@ -218,21 +217,18 @@ void Engine::carry_fix_now(size_t r, int excess) {
 // digits(r) (+ its pending run carries) -> work(); digits(r) stay as they are.  (Runs of two digits never leave carries pending:
 // every operation that writes run carries on a plan with C < 2 takes them in at once, carry_fix_now.)
 void Engine::run_front(size_t r) {
-  if (lanes_ > 1) HIPCHK(launch_front_lanes(dp_, lg_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, work(), stream_));
-  else if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_front_split(dp_, digits(r), split_, work(), stream_));
+  if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_front_split(dp_, digits(r), split_, work(), stream_));
   else HIPCHK(cols_.front(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, work(), stream_));
 }
 
 void Engine::run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, const uint64_t* y2, uint64_t* img) {
-  if (lanes_ > 1) HIPCHK(launch_middle_lanes(dp_, lg_, in, y, y2, img, out, mode, stream_));
-  else HIPCHK(rows_(dp_, in, y, y2, img, out, mode, stream_));
+  HIPCHK(rows_(dp_, in, y, y2, img, out, mode, stream_));
 }
 
 // work() -> digits(r) + run carries in cbuf(r): runs of 2C >= 4 digits leave them to the next sweep, which folds them in, runs of two
 // digits take them at once.  ev (nullable): two events recorded around that carry fix (time_square_mul)
 void Engine::run_back(size_t r, uint32_t a, hipEvent_t* ev) {
-  if (lanes_ > 1) HIPCHK(launch_back_lanes(dp_, lg_, work(), digits(r), cbuf(r), a, nullptr, stream_));
-  else if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_back_split(dp_, work(), split_, digits(r), cbuf(r), a, stream_));
+  if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_back_split(dp_, work(), split_, digits(r), cbuf(r), a, stream_));
   else HIPCHK(cols_.back(dp_, work(), digits(r), cbuf(r), a, stream_));
   if (ev) HIPCHK(hipEventRecord(ev[0], stream_));
   if (pl_.C >= 2) pending_carry_[r] = 1;
@@ -508,8 +504,7 @@ void Engine::scale(size_t r, uint32_t a) {
   need_residue(r, "scale");
   uint64_t* fresh = take_spare_cbuf();
   const uint64_t* cin = pending_carry_[r] ? cbuf(r) : nullptr;
-  if (lanes_ > 1) HIPCHK(launch_scale_lanes(dp_, lg_, digits(r), cin, digits(r), fresh, a, stream_));
-  else HIPCHK(launch_scale(dp_, digits(r), cin, digits(r), fresh, a, stream_));
+  HIPCHK(launch_scale(dp_, digits(r), cin, digits(r), fresh, a, stream_));
   adopt_cbuf(r, fresh);
   pending_carry_[r] = 1;
   // runs of two digits: the carry words (below 2^34: digit < 2^(q+2) after the passes, times a < 2^32) go in at once
@@ -545,7 +540,7 @@ void Engine::addsub(long s1, long s2, long d1, long d2, size_t a, size_t b) {
   if (d1 >= 0) { la.d1 = digits(size_t(d1)); la.cd1 = fresh[2]; }
   if (d2 >= 0) { la.d2 = digits(size_t(d2)); la.cd2 = fresh[3]; }
   if ((s2 >= 0 && s1 < 0) || (d2 >= 0 && d1 < 0)) throw std::runtime_error("internal: copy output without a primary output");
-  HIPCHK(lanes_ > 1 ? launch_linear_lanes(dp_, lg_, la, stream_) : launch_linear(dp_, la, stream_));
+  HIPCHK(launch_linear(dp_, la, stream_));
   for (int i = 0; i < 4; ++i)
     if (outs[i] >= 0) {
       const size_t r = size_t(outs[i]);
@@ -564,8 +559,7 @@ void Engine::back_ext(size_t dst, uint32_t a, long copy_to, long add_src) {
   if (copy_to >= 0 && size_t(copy_to) != dst) { x.digits2 = digits(size_t(copy_to)); x.cbuf2 = cbuf(size_t(copy_to)); }
   if (add_src >= 0) { x.add_digits = digits(size_t(add_src)); x.add_cbuf = pending_carry_[size_t(add_src)] ? cbuf(size_t(add_src)) : nullptr; }
   uint64_t* fresh = take_spare_cbuf();   // the addend may be dst itself: its pending carries are read while the new ones are written
-  if (lanes_ > 1) HIPCHK(launch_back_lanes(dp_, lg_, work(), digits(dst), fresh, a, &x, stream_));
-  else HIPCHK(cols_.back_ext(dp_, work(), digits(dst), fresh, a, x, stream_));
+  HIPCHK(cols_.back_ext(dp_, work(), digits(dst), fresh, a, x, stream_));
   adopt_cbuf(dst, fresh);
   const size_t outs[2] = {dst, x.digits2 ? size_t(copy_to) : dst};
   for (int i = 0; i < (x.digits2 ? 2 : 1); ++i) {
@@ -645,7 +639,7 @@ void Engine::sub_u32(size_t r, uint32_t v) {
   // then go negative, which the unsigned back sweep reads as values near the field prime; the borrow below is exact for every register)
   // the small subtraction only touches the digit vector (cyclic borrow), so run carries that are still pending
   // for the next front sweep can stay pending: value = digits + carries - v either way
-  HIPCHK(lanes_ > 1 ? launch_sub_small_lanes(dp_, lg_, digits(r), v, stream_) : launch_sub_small(dp_, digits(r), v, stream_));
+  HIPCHK(launch_sub_small(dp_, digits(r), v, stream_));
 }
 
 // ---- raw images -----------------------------------------------------------------------------

@@ -91,7 +91,7 @@ class Engine final : public RegisterMachine {
   // kDigits: unweighted u32 digits (+ deferred run carries); kImage: multiplicand
   enum Kind : uint8_t { kDigits = 0, kImage = 1 };
   bool holds_image(size_t r) const override { return kind_[r] == kImage; }
-  // lane l of a slot lies l * reg_bytes_ behind lane 0, lane l of a carry buffer l * runs() words (kernels.hpp LaneGeom)
+  // lane l of a slot lies l * reg_bytes_ behind lane 0, lane l of a carry buffer l * runs() words (kernels.hpp DevPlan.lanes)
   uint32_t* digits(size_t r, size_t lane = 0) { return reinterpret_cast<uint32_t*>(slot_[r] + lane * reg_bytes_); }
   void no_lanes(const char* op) const {   // operations a lane engine does not have
     if (lanes_ > 1) throw std::runtime_error(std::string(op) + ": not with lanes (per-lane I/O: mi355_lanes_* in include/mi355_lanes.h)");
@@ -129,7 +129,6 @@ class Engine final : public RegisterMachine {
   hipStream_t stream_ = nullptr;
   size_t nregs_ = 0, reg_bytes_ = 0;
   size_t lanes_ = 1;         // residues per register (pl_.lanes)
-  LaneGeom lg_{};            // what the lane launches need; used when lanes_ > 1
   unsigned char* regs_ = nullptr;            // (reg_count + 1) slots of lanes x 8n bytes; the extra one is the work buffer
   std::vector<unsigned char*> slot_;          // slot_[r]: storage of register r; slot_[reg_count]: work buffer (swappable)
   uint64_t* cbuf_ = nullptr;                  // reg_count + 4 buffers of lanes x runs() carry words

@@ -28,6 +28,11 @@ __device__ __forceinline__ P2 p2_add(P2 x, P2 y) { return {gf::add(x.a, y.a), gf
 __device__ __forceinline__ P2 p2_sub(P2 x, P2 y) { return {gf::sub(x.a, y.a), gf::sub(x.b, y.b)}; }
 __device__ __forceinline__ P2 p2_mul(P2 x, uint64_t w) { return {gf::mul(x.a, w), gf::mul(x.b, w)}; }
 __device__ __forceinline__ P2 p2_shift48(P2 x) { return {gf::mul_pow2(x.a, 48), gf::mul_pow2(x.b, 48)}; }
+// the same on one word of a pair (lds_pow2_passes, one plane per thread)
+__device__ __forceinline__ uint64_t p2_add(uint64_t x, uint64_t y) { return gf::add(x, y); }
+__device__ __forceinline__ uint64_t p2_sub(uint64_t x, uint64_t y) { return gf::sub(x, y); }
+__device__ __forceinline__ uint64_t p2_mul(uint64_t x, uint64_t w) { return gf::mul(x, w); }
+__device__ __forceinline__ uint64_t p2_shift48(uint64_t x) { return gf::mul_pow2(x, 48); }
 
 // omega_m^e from the two-level table (e < m)
 __device__ __forceinline__ uint64_t tw_lookup(const DevPlan& pl, uint64_t e) {
@@ -55,75 +60,16 @@ __device__ __forceinline__ void digit_info(const DevPlan& pl, uint32_t sa, uint3
 // Elements of one transform sit at X[(base + i) * stride + col]; `groups` independent transforms of
 // length L (blocks x columns) are processed by the whole work-group.  root[e * rstep] = omega_L^e.
 // ---------------------------------------------------------------------------------------------
-// The same passes with one PLANE of a butterfly per thread (the two words of a pair go through identical, independent arithmetic):
-// twice the threads, half the instruction stream per wave.  Small tiles are latency-bound -- one or two waves per SIMD, so a launch
-// lasts as long as the dependent instruction stream of one wave (C2: 0.041 ms for three launches whose VALU work is 3 us) -- and the
-// way to shorten that stream is more threads with less work each, not wider butterflies (a radix-8 form made C2 35 % slower).
-template <bool INVERSE>
-__device__ __forceinline__ void lds_pow2_dft_planes(P2* X, uint32_t L, uint32_t logL, uint32_t nblocks, uint32_t ncols, uint32_t logcols,
-                                                    const uint64_t* __restrict__ root, uint32_t rootN, uint32_t rstep, uint32_t tid, uint32_t nthr) {
-  uint64_t* Xw = reinterpret_cast<uint64_t*>(X);   // element e, plane b at Xw[2 e + b]
-  const uint32_t n4 = logL / 2, has2 = logL & 1;
-  const uint32_t npass = n4 + has2;
-  for (uint32_t ps = 0; ps < npass; ++ps) {
-    const uint32_t pf = INVERSE ? (npass - 1 - ps) : ps;
-    if (pf < n4) {
-      const uint32_t loglen = logL - 2 * pf, len = 1u << loglen, q = len >> 2;
-      const uint32_t per = L >> 2;
-      const uint32_t total = per * nblocks * ncols * 2;
-      const uint32_t tstep = (L >> loglen) * rstep;
-      for (uint32_t idx2 = tid; idx2 < total; idx2 += nthr) {
-        const uint32_t plane = idx2 & 1, idx = idx2 >> 1;
-        const uint32_t col = idx & (ncols - 1), bi = idx >> logcols;
-        const uint32_t blk = bi >> (logL - 2), bj = bi & (per - 1);
-        const uint32_t sub = bj >> (loglen - 2), t = bj & (q - 1);
-        const uint32_t e0 = 2 * ((blk * L + sub * len + t) * ncols + col) + plane, es = 2 * q * ncols;
-        const uint32_t r1 = t * tstep;
-        const uint64_t x0 = Xw[e0], x1 = Xw[e0 + es], x2 = Xw[e0 + 2 * es], x3 = Xw[e0 + 3 * es];
-        if (!INVERSE) {
-          const uint64_t w1 = root[r1], w2 = root[2 * r1], w3 = root[3 * r1];
-          const uint64_t a = gf::add(x0, x2), b = gf::add(x1, x3), c = gf::sub(x0, x2), d = gf::mul_pow2(gf::sub(x1, x3), 48);
-          Xw[e0] = gf::add(a, b);
-          Xw[e0 + es] = gf::mul(gf::sub(a, b), w2);
-          Xw[e0 + 2 * es] = gf::mul(gf::add(c, d), w1);
-          Xw[e0 + 3 * es] = gf::mul(gf::sub(c, d), w3);
-        } else {
-          const uint64_t w1 = root[r1 ? rootN - r1 : 0], w2 = root[r1 ? rootN - 2 * r1 : 0], w3 = root[r1 ? rootN - 3 * r1 : 0];
-          const uint64_t y1 = gf::mul(x1, w2);
-          const uint64_t A = gf::add(x0, y1), B = gf::sub(x0, y1);
-          const uint64_t y2 = gf::mul(x2, w1), y3 = gf::mul(x3, w3);
-          const uint64_t Cc = gf::add(y2, y3), D = gf::mul_pow2(gf::sub(y3, y2), 48);
-          Xw[e0] = gf::add(A, Cc);
-          Xw[e0 + 2 * es] = gf::sub(A, Cc);
-          Xw[e0 + es] = gf::add(B, D);
-          Xw[e0 + 3 * es] = gf::sub(B, D);
-        }
-      }
-    } else {
-      const uint32_t per = L >> 1, total = per * nblocks * ncols * 2;
-      for (uint32_t idx2 = tid; idx2 < total; idx2 += nthr) {
-        const uint32_t plane = idx2 & 1, idx = idx2 >> 1;
-        const uint32_t col = idx & (ncols - 1), bi = idx >> logcols;
-        const uint32_t blk = bi >> (logL - 1), bj = bi & (per - 1);
-        const uint32_t e0 = 2 * ((blk * L + 2 * bj) * ncols + col) + plane;
-        const uint64_t u = Xw[e0], v = Xw[e0 + 2 * ncols];
-        Xw[e0] = gf::add(u, v);
-        Xw[e0 + 2 * ncols] = gf::sub(u, v);
-      }
-    }
-    __syncthreads();
-  }
-}
-
-template <bool INVERSE>
-__device__ __forceinline__ void lds_pow2_dft(P2* X, uint32_t L, uint32_t logL, uint32_t nblocks, uint32_t ncols, uint32_t logcols,
-                                             const uint64_t* __restrict__ root, uint32_t rootN, uint32_t rstep,
-                                             uint64_t I4, uint32_t tid, uint32_t nthr) {
-  // small tiles: one plane per thread (see above); the work-group was sized for that by the launcher
-  if (nthr * 2 >= (L >> 2) * nblocks * ncols * 2 && nthr > (L >> 2) * nblocks * ncols) {
-    lds_pow2_dft_planes<INVERSE>(X, L, logL, nblocks, ncols, logcols, root, rootN, rstep, tid, nthr);
-    return;
-  }
+// E = P2: a butterfly of pairs per thread.  E = uint64_t: one PLANE of it (the two words of a pair go through identical, independent
+// arithmetic; element e, plane b at word 2 e + b): twice the threads, half the instruction stream per wave.  Small tiles are
+// latency-bound -- one or two waves per SIMD, so a launch lasts as long as the dependent instruction stream of one wave (C2: 0.041 ms for
+// three launches whose VALU work is 3 us) -- and the way to shorten that stream is more threads with less work each, not wider
+// butterflies (a radix-8 form made C2 35 % slower).
+template <bool INVERSE, class E>
+__device__ __forceinline__ void lds_pow2_passes(P2* Xp, uint32_t L, uint32_t logL, uint32_t nblocks, uint32_t ncols, uint32_t logcols,
+                                                const uint64_t* __restrict__ root, uint32_t rootN, uint32_t rstep, uint32_t tid, uint32_t nthr) {
+  constexpr uint32_t W = sizeof(P2) / sizeof(E);   // E's per pair
+  E* X = reinterpret_cast<E*>(Xp);
   // forward: len = L, L/4, ... (radix-4) then a final radix-2 when log2 L is odd; inverse mirrors
   const uint32_t n4 = logL / 2, has2 = logL & 1;
   const uint32_t npass = n4 + has2;
@@ -132,19 +78,20 @@ __device__ __forceinline__ void lds_pow2_dft(P2* X, uint32_t L, uint32_t logL, u
     if (pf < n4) {
       const uint32_t loglen = logL - 2 * pf, len = 1u << loglen, q = len >> 2;
       const uint32_t per = L >> 2;  // butterflies per transform
-      const uint32_t total = per * nblocks * ncols;
+      const uint32_t total = per * nblocks * ncols * W;
       const uint32_t tstep = (L >> loglen) * rstep;  // omega_len^t = root[t * tstep]
-      for (uint32_t idx = tid; idx < total; idx += nthr) {
-        // ncols, per and q are powers of two: shifts and masks, no integer division in the loop
+      for (uint32_t idxw = tid; idxw < total; idxw += nthr) {
+        // W, ncols, per and q are powers of two: shifts and masks, no integer division in the loop
+        const uint32_t plane = idxw & (W - 1), idx = idxw / W;
         const uint32_t col = idx & (ncols - 1), bi = idx >> logcols;
         const uint32_t blk = bi >> (logL - 2), bj = bi & (per - 1);
         const uint32_t sub = bj >> (loglen - 2), t = bj & (q - 1);
-        const uint32_t e0 = (blk * L + sub * len + t) * ncols + col, es = q * ncols;
+        const uint32_t e0 = W * ((blk * L + sub * len + t) * ncols + col) + plane, es = W * q * ncols;
         const uint32_t r1 = t * tstep;
-        P2 x0 = X[e0], x1 = X[e0 + es], x2 = X[e0 + 2 * es], x3 = X[e0 + 3 * es];
+        const E x0 = X[e0], x1 = X[e0 + es], x2 = X[e0 + 2 * es], x3 = X[e0 + 3 * es];
         if (!INVERSE) {
           const uint64_t w1 = root[r1], w2 = root[2 * r1], w3 = root[3 * r1];
-          const P2 a = p2_add(x0, x2), b = p2_add(x1, x3), c = p2_sub(x0, x2), d = p2_shift48(p2_sub(x1, x3));   // omega_4 = 2^48 (checked in make_plan)
+          const E a = p2_add(x0, x2), b = p2_add(x1, x3), c = p2_sub(x0, x2), d = p2_shift48(p2_sub(x1, x3));   // omega_4 = 2^48 (checked in make_plan)
           X[e0] = p2_add(a, b);
           X[e0 + es] = p2_mul(p2_sub(a, b), w2);
           X[e0 + 2 * es] = p2_mul(p2_add(c, d), w1);
@@ -152,10 +99,10 @@ __device__ __forceinline__ void lds_pow2_dft(P2* X, uint32_t L, uint32_t logL, u
         } else {
           // inverse roots: omega^-e = root[(N - e) % N]
           const uint64_t w1 = root[r1 ? rootN - r1 : 0], w2 = root[r1 ? rootN - 2 * r1 : 0], w3 = root[r1 ? rootN - 3 * r1 : 0];
-          const P2 y1 = p2_mul(x1, w2);
-          const P2 A = p2_add(x0, y1), B = p2_sub(x0, y1);
-          const P2 y2 = p2_mul(x2, w1), y3 = p2_mul(x3, w3);
-          const P2 Cc = p2_add(y2, y3), D = p2_shift48(p2_sub(y3, y2));   // omega_4^-1 = -2^48
+          const E y1 = p2_mul(x1, w2);
+          const E A = p2_add(x0, y1), B = p2_sub(x0, y1);
+          const E y2 = p2_mul(x2, w1), y3 = p2_mul(x3, w3);
+          const E Cc = p2_add(y2, y3), D = p2_shift48(p2_sub(y3, y2));   // omega_4^-1 = -2^48
           X[e0] = p2_add(A, Cc);
           X[e0 + 2 * es] = p2_sub(A, Cc);
           X[e0 + es] = p2_add(B, D);
@@ -164,17 +111,29 @@ __device__ __forceinline__ void lds_pow2_dft(P2* X, uint32_t L, uint32_t logL, u
       }
     } else {
       // radix-2, len = 2: no twiddle
-      const uint32_t per = L >> 1, total = per * nblocks * ncols;
-      for (uint32_t idx = tid; idx < total; idx += nthr) {
+      const uint32_t per = L >> 1, total = per * nblocks * ncols * W;
+      for (uint32_t idxw = tid; idxw < total; idxw += nthr) {
+        const uint32_t plane = idxw & (W - 1), idx = idxw / W;
         const uint32_t col = idx & (ncols - 1), bi = idx >> logcols;
         const uint32_t blk = bi >> (logL - 1), bj = bi & (per - 1);
-        const uint32_t e0 = (blk * L + 2 * bj) * ncols + col;
-        const P2 u = X[e0], v = X[e0 + ncols];
+        const uint32_t e0 = W * ((blk * L + 2 * bj) * ncols + col) + plane;
+        const E u = X[e0], v = X[e0 + W * ncols];
         X[e0] = p2_add(u, v);
-        X[e0 + ncols] = p2_sub(u, v);
+        X[e0 + W * ncols] = p2_sub(u, v);
       }
     }
     __syncthreads();
+  }
+}
+
+template <bool INVERSE>
+__device__ __forceinline__ void lds_pow2_dft(P2* X, uint32_t L, uint32_t logL, uint32_t nblocks, uint32_t ncols, uint32_t logcols,
+                                             const uint64_t* __restrict__ root, uint32_t rootN, uint32_t rstep, uint32_t tid, uint32_t nthr) {
+  // small tiles: one plane per thread (see above); the work-group was sized for that by the launcher
+  if (nthr * 2 >= (L >> 2) * nblocks * ncols * 2 && nthr > (L >> 2) * nblocks * ncols) {
+    lds_pow2_passes<INVERSE, uint64_t>(X, L, logL, nblocks, ncols, logcols, root, rootN, rstep, tid, nthr);
+  } else {
+    lds_pow2_passes<INVERSE, P2>(X, L, logL, nblocks, ncols, logcols, root, rootN, rstep, tid, nthr);
   }
 }
 
@@ -239,12 +198,63 @@ __device__ __forceinline__ void lds_radix5(const DevPlan& pl, P2* X, uint32_t nc
 
 extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
 
+// Lanes (kernels.hpp DevPlan.lanes): blockIdx.y is the lane, blockIdx.x what it is without lanes.  Every kernel moves its pointers, which
+// are those of lane 0, to its lane first; null stays null.  64-bit offsets: a lane may lie beyond 4 GiB.
+// Every entry point is compiled twice from its one source, k<LANES>: k<false>, which a plain engine launches (pl.lanes == 1), leaves the
+// pointers alone.  As a run-time offset of lane 0 the same arithmetic cost the latency-bound launches of a plain engine 0.8-3.4 %
+// (profiles/generic_one_entry_ab.txt).
+template <bool LANES, class T> __device__ __forceinline__ T* lane_reg(const DevPlan& pl, T* p) {   // a register, the work buffer or an image: 8 n bytes a lane
+  if (!LANES) return p;
+  return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + uint64_t(blockIdx.y) * pl.n * 8) : nullptr;
+}
+template <bool LANES, class T> __device__ __forceinline__ T* lane_cbuf(const DevPlan& pl, T* p) {   // a carry buffer: one word per run
+  if (!LANES) return p;
+  return p ? p + uint64_t(blockIdx.y) * pl.M1 * (pl.M2 >> pl.logC) : nullptr;
+}
+
 // previous run (in digit order) of run (T, i1): same row, previous tile; first tile wraps to the
 // last tile of the previous row (cyclic: 2^p = 1)
 __device__ __forceinline__ uint64_t carry_in_of(const DevPlan& pl, const uint64_t* cbuf, uint32_t T, uint32_t i1) {
   const uint32_t NT = pl.M2 / pl.C;
   if (T > 0) return *(cbuf + size_t(T - 1) * pl.M1 + i1);
   return *(cbuf + size_t(NT - 1) * pl.M1 + (i1 ? i1 - 1 : pl.M1 - 1));
+}
+
+// Digit k (value v, `width` bits) of a run of ndig digits takes the run's incoming carry word c (weak carry: adc4, marin.cl:203-212): three
+// masked digits, the remainder stays on the fourth; runs of two digits (C = 1) take all of it on the second.
+__device__ __forceinline__ uint64_t take_carry_in(uint64_t v, uint64_t& c, uint32_t k, uint32_t ndig, uint32_t width) {
+  if (k < 3 && k + 1 < ndig) { v += c; c = v >> width; v &= (uint64_t(1) << width) - 1; }
+  else if (k == 3 || k + 1 == ndig) { v += c; c = 0; }
+  return v;
+}
+// the same for a tile kernel that holds the run's first four digits dd (C >= 2)
+__device__ __forceinline__ void run_carry_in(const DevPlan& pl, uint32_t sa, uint32_t T, uint64_t cin, uint32_t (&dd)[4]) {
+#pragma unroll
+  for (uint32_t k = 0; k < 4; ++k) {
+    uint32_t width; bool wr;
+    digit_info(pl, sa, pl.SB[2 * (T * pl.C) + k], width, wr);
+    dd[k] = uint32_t(take_carry_in(dd[k], cin, k, 4, width));
+  }
+}
+
+// Weighted pair of the digits d of pair (i1, i2), sb = SB[2 i2]: weight = TA * TB / (wrap ? 2 : 1), TB left to the four-step twiddle.  The
+// odd digit takes its exponent split from the second half of SA / TA (plan.hpp) so that both digits of the pair share the column factor
+// TB[2 i2]; the halving sits on TA and the digits that do not wrap are doubled instead (digits are < 2^21: still a mul_u32).
+__device__ __forceinline__ P2 weigh_pair(const DevPlan& pl, uint32_t i1, uint32_t sb, uint2 d) {
+  uint32_t w0, w1; bool wr0, wr1;
+  digit_info(pl, pl.SA[i1], sb, w0, wr0);
+  digit_info(pl, pl.SA[pl.M1 + i1], sb, w1, wr1);
+  return {gf::mul_u32(pl.TAh[i1], d.x << (wr0 ? 0 : 1)), gf::mul_u32(pl.TAh[pl.M1 + i1], d.y << (wr1 ? 0 : 1))};
+}
+
+// Four-step twiddle of work-buffer element (pos, i2) times the column factor of its pair: omega_m^(i2 k1) TB[2 i2], INVERSE the inverse of both.
+// have: pre holds the three table words of the forward one, requested earlier (front_body).
+struct TwPre { uint64_t lo = 0, hi = 0, tb = 0; };
+template <bool INVERSE>
+__device__ __forceinline__ uint64_t fourstep_word(const DevPlan& pl, uint32_t pos, uint32_t i2, bool have = false, TwPre pre = TwPre()) {
+  const uint32_t ex = i2 * freq1(pl, pos);   // i2 < M2, k1 < M1: below m, no reduction needed
+  const uint64_t tw = have ? gf::mul(pre.lo, pre.hi) : tw_lookup(pl, INVERSE ? (ex ? pl.m - ex : 0) : ex);
+  return gf::mul(tw, have ? pre.tb : INVERSE ? pl.TBi[2 * i2] : pl.TB[2 * i2]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -260,69 +270,47 @@ __device__ __forceinline__ void front_body(const DevPlan& pl, const uint32_t* di
   for (uint32_t e = tid; e < tile; e += nthr) {
     const uint32_t i1 = e >> pl.logC, c = e & (C - 1), i2 = T * C + c;
     uint2 d = dg[e];
-    const uint32_t sa = pl.SA[i1];
+    const uint32_t sa = pl.SA[i1];   // before the branch: inside it the load is issued a second time for the weighting (12 instructions more)
     if (cbuf_in && c < 2) {
-      // deferred run carries (C >= 2): the carry word left by the previous run goes into the first digits
-      // of this one (three masked digits, the remainder onto the fourth: adc4, marin.cl:203-212).  The two
+      // deferred run carries (C >= 2): the carry word left by the previous run goes into the first digits of this one.  The two
       // threads that own the run's first two pairs each redo the four-digit chain and keep their pair.
-      uint64_t cin = carry_in_of(pl, cbuf_in, T, i1);
+      const uint64_t cin = carry_in_of(pl, cbuf_in, T, i1);
       if (cin) {
         const uint2* run = dg + i1 * C;
         const uint2 p0 = run[0], p1 = run[1];
         uint32_t dd[4] = {p0.x, p0.y, p1.x, p1.y};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          uint32_t width; bool wr;
-          digit_info(pl, sa, pl.SB[2 * (T * C) + k], width, wr);
-          const uint64_t v = uint64_t(dd[k]) + cin;
-          dd[k] = uint32_t(v & ((uint64_t(1) << width) - 1));
-          cin = v >> width;
-        }
-        dd[3] += uint32_t(cin);
+        run_carry_in(pl, sa, T, cin, dd);
         d = c ? make_uint2(dd[2], dd[3]) : make_uint2(dd[0], dd[1]);
       }
     }
-    // weight = TA * TB / (wrap ? 2 : 1).  The odd digit takes its exponent split from the second half of
-    // SA / TA (plan.hpp) so that both digits of the pair share the column factor TB[2 i2]; the halving sits
-    // on TA and the digits that do not wrap are doubled instead (digits are < 2^21: still a mul_u32).
-    uint32_t w0, w1; bool wr0, wr1;
-    const uint32_t sb = pl.SB[2 * i2];
-    digit_info(pl, sa, sb, w0, wr0);
-    digit_info(pl, pl.SA[M1 + i1], sb, w1, wr1);
-    const uint64_t a0 = gf::mul_u32(pl.TAh[i1], d.x << (wr0 ? 0 : 1));
-    const uint64_t a1 = gf::mul_u32(pl.TAh[M1 + i1], d.y << (wr1 ? 0 : 1));
-    X[e] = {a0, a1};
+    X[e] = weigh_pair(pl, i1, pl.SB[2 * i2], d);
   }
   __syncthreads();
 
   // small tiles (one output element per thread): the three table words of its four-step twiddle are requested before the transform,
-  // whose passes hide their latency (latency-bound launches: see lds_pow2_dft_planes)
+  // whose passes hide their latency (latency-bound launches: see lds_pow2_passes)
   const bool one = tile <= nthr;
-  uint64_t pre_lo = 0, pre_hi = 0, pre_tb = 0;
+  TwPre pre;
   if (one && tid < tile) {
     const uint32_t pos = tid >> pl.logC, i2 = T * C + (tid & (C - 1));
     const uint64_t ex = uint64_t(i2) * freq1(pl, pos);
-    pre_lo = pl.TWlo[ex & ((1u << pl.twh) - 1)]; pre_hi = pl.TWhi[ex >> pl.twh]; pre_tb = pl.TB[2 * i2];
+    pre.lo = pl.TWlo[ex & ((1u << pl.twh) - 1)]; pre.hi = pl.TWhi[ex >> pl.twh]; pre.tb = pl.TB[2 * i2];
   }
   if (pl.r5 == 5) lds_radix5<false>(pl, X, C, tid, nthr);
-  if (pl.logL1) lds_pow2_dft<false>(X, pl.L1, pl.logL1, pl.r5, C, pl.logC, pl.UT1, M1, pl.r5, pl.I4, tid, nthr);
+  if (pl.logL1) lds_pow2_dft<false>(X, pl.L1, pl.logL1, pl.r5, C, pl.logC, pl.UT1, M1, pl.r5, tid, nthr);
 
   P2* W = reinterpret_cast<P2*>(Wout);
   for (uint32_t e = tid; e < tile; e += nthr) {
-    const uint32_t pos = e >> pl.logC, c = e & (C - 1), i2 = T * C + c;
-    const uint32_t k1 = freq1(pl, pos);
-    const uint32_t ex = i2 * k1;   // i2 < M2, k1 < M1: below m, no reduction needed
-    const uint64_t tw = one ? gf::mul(pre_lo, pre_hi) : tw_lookup(pl, ex);
-    const P2 x = X[e];
-    const uint64_t twb = gf::mul(tw, one ? pre_tb : pl.TB[2 * i2]);
+    const uint32_t pos = e >> pl.logC, i2 = T * C + (e & (C - 1));
     P2* out = W + size_t(pos) * pl.M2 + i2;
-    *out = {gf::mul(x.a, twb), gf::mul(x.b, twb)};
+    *out = p2_mul(X[e], fourstep_word<false>(pl, pos, i2, one, pre));
   }
 }
+template <bool LANES>
 __global__ void __launch_bounds__(1024) k_front(DevPlan pl, const uint32_t* __restrict__ digits, const uint64_t* __restrict__ cbuf_in,
                                                 uint64_t* __restrict__ Wout) {
-  if (blockIdx.x >= pl.boost_tiles) __builtin_amdgcn_s_setprio(3);   // last half round: see kernels_v2.hip, boost_if_late (C4: -2.7 %)
-  front_body(pl, digits, cbuf_in, Wout, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
+  if (blockIdx.x >= pl.boost_tiles) __builtin_amdgcn_s_setprio(3);   // last half round: see kernels_v2.hip, boost_if_late (C4: -2.7 %); never with lanes
+  front_body(pl, lane_reg<LANES>(pl, digits), lane_cbuf<LANES>(pl, cbuf_in), lane_reg<LANES>(pl, Wout), blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -345,7 +333,7 @@ __device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* W
     const uint64_t ex = rho_exponent(pl, k1, __brev(tid) >> (32 - pl.logM2));
     pre_lo = pl.TWlo[ex & ((1u << pl.twh) - 1)]; pre_hi = pl.TWhi[ex >> pl.twh];
   }
-  lds_pow2_dft<false>(X, M2, pl.logM2, 1, 1, 0, pl.UT2, M2, 1, pl.I4, tid, nthr);
+  lds_pow2_dft<false>(X, M2, pl.logM2, 1, 1, 0, pl.UT2, M2, 1, tid, nthr);
   if (mode == 2) {
     for (uint32_t e = tid; e < M2; e += nthr) out[e] = X[e];
     return;
@@ -375,31 +363,48 @@ __device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* W
     X[e] = r;
   }
   __syncthreads();
-  lds_pow2_dft<true>(X, M2, pl.logM2, 1, 1, 0, pl.UT2, M2, 1, pl.I4inv, tid, nthr);
+  lds_pow2_dft<true>(X, M2, pl.logM2, 1, 1, 0, pl.UT2, M2, 1, tid, nthr);
   for (uint32_t e = tid; e < M2; e += nthr) out[e] = X[e];
 }
+template <bool LANES>
 __global__ void __launch_bounds__(1024) k_middle(DevPlan pl, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Yimg,
                                                 const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout, int mode) {
-  middle_body(pl, Win, Yimg, Yimg2, Wout, mode, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
+  middle_body(pl, lane_reg<LANES>(pl, Win), lane_reg<LANES>(pl, Yimg), lane_reg<LANES>(pl, Yimg2), lane_reg<LANES>(pl, Wout), mode, blockIdx.x, reinterpret_cast<P2*>(smem_raw),
+              threadIdx.x, blockDim.x);
 }
+template <bool LANES>
 __global__ void __launch_bounds__(1024) k_middle_keep(DevPlan pl, const uint64_t* __restrict__ Win, uint64_t* __restrict__ Wimg, uint64_t* __restrict__ Wout) {
-  middle_body<true>(pl, Win, nullptr, nullptr, Wout, 0, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x, Wimg);
+  middle_body<true>(pl, lane_reg<LANES>(pl, Win), nullptr, nullptr, lane_reg<LANES>(pl, Wout), 0, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x,
+                    lane_reg<LANES>(pl, Wimg));
 }
 
 // ---------------------------------------------------------------------------------------------
 // back: inverse of front + unweight + carry over the tile's M1 runs of 2C digits
 // ---------------------------------------------------------------------------------------------
-// weak carry of a run's incoming carry word into its first digits (adc4, marin.cl:203-212); dd: the run's first four digits
-__device__ __forceinline__ void run_carry_in(const DevPlan& pl, uint32_t sa, uint32_t T, uint64_t cin, uint32_t (&dd)[4]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    uint32_t width; bool wr;
-    digit_info(pl, sa, pl.SB[2 * (T * pl.C) + k], width, wr);
-    const uint64_t v = uint64_t(dd[k]) + cin;
-    dd[k] = uint32_t(v & ((uint64_t(1) << width) - 1));
-    cin = v >> width;
+// Row i1's unweighting factors, even / odd digit (second half of the tables: see weigh_pair); tai2 serves the wrapped exponents, whose
+// weight was halved.  unweigh: word x of a pair of that row, digit b, column exponent sb = SB[2 i2] -> the unweighted value and its width.
+struct RowUnweight { uint32_t sa[2]; uint64_t tai[2], tai2[2]; };
+__device__ __forceinline__ RowUnweight row_unweight(const DevPlan& pl, uint32_t i1) {
+  return {{pl.SA[i1], pl.SA[pl.M1 + i1]}, {pl.TAi[i1], pl.TAi[pl.M1 + i1]}, {pl.TAi2[i1], pl.TAi2[pl.M1 + i1]}};
+}
+__device__ __forceinline__ uint64_t unweigh(const DevPlan& pl, const RowUnweight& r, int b, uint32_t sb, uint64_t x, uint32_t& width) {
+  bool wrap;
+  digit_info(pl, r.sa[b], sb, width, wrap);
+  return gf::mul(x, wrap ? r.tai2[b] : r.tai[b]);
+}
+// One step of the carry chain: u a + addend + carry -> a digit of `width` bits and the next carry
+__device__ __forceinline__ uint32_t adc_mul(uint64_t u, uint32_t a, uint32_t addend, uint32_t width, uint64_t& carry) {
+  const uint64_t mask = (uint64_t(1) << width) - 1;
+  uint64_t r;
+  if (a == 1) {               // the common case (uniform): no 64-bit multiplies
+    r = u + carry + addend;   // u < 2^63 by the size rule (ibdwt.h:28-30), carry < 2^48, addend < 2^32
+    carry = r >> width;
+  } else {                    // adc_mul (marin.cl:194-201): digit first, so that everything stays in 64 bits
+    const uint64_t dlo = u & mask, chi = u >> width;
+    r = dlo * a + carry + addend;
+    carry = (r >> width) + chi * a;
   }
-  dd[3] += uint32_t(cin);
+  return uint32_t(r & mask);
 }
 
 // blocks that share an XCD (b, b + 8, ...) take neighbouring tiles: the 64-byte pieces of a work-buffer line meet in one L2
@@ -414,24 +419,18 @@ __device__ __forceinline__ void back_body(const DevPlan& pl, const uint64_t* Win
   const P2* W = reinterpret_cast<const P2*>(Win);
 
   for (uint32_t e = tid; e < tile; e += nthr) {
-    const uint32_t pos = e >> pl.logC, c = e & (C - 1), i2 = T * C + c;
-    const uint32_t k1 = freq1(pl, pos);
-    const uint32_t ex = i2 * k1;   // i2 < M2, k1 < M1: below m, no reduction needed
-    const uint64_t tw = tw_lookup(pl, ex ? pl.m - ex : 0);
+    const uint32_t pos = e >> pl.logC, i2 = T * C + (e & (C - 1));
     const P2 x = *(W + size_t(pos) * pl.M2 + i2);
-    const uint64_t twb = gf::mul(tw, pl.TBi[2 * i2]);   // one column factor per pair (see k_front)
-    X[e] = {gf::mul(x.a, twb), gf::mul(x.b, twb)};
+    X[e] = p2_mul(x, fourstep_word<true>(pl, pos, i2));   // one column factor per pair (see weigh_pair)
   }
   __syncthreads();
 
-  if (pl.logL1) lds_pow2_dft<true>(X, pl.L1, pl.logL1, pl.r5, C, pl.logC, pl.UT1, M1, pl.r5, pl.I4inv, tid, nthr);
+  if (pl.logL1) lds_pow2_dft<true>(X, pl.L1, pl.logL1, pl.r5, C, pl.logC, pl.UT1, M1, pl.r5, tid, nthr);
   if (pl.r5 == 5) lds_radix5<true>(pl, X, C, tid, nthr);
 
   uint2* dg = reinterpret_cast<uint2*>(digits) + size_t(T) * tile;
   for (uint32_t i1 = tid; i1 < M1; i1 += nthr) {
-    const uint32_t sa[2] = {pl.SA[i1], pl.SA[M1 + i1]};          // even / odd digit (second half: see k_front)
-    const uint64_t tai[2] = {pl.TAi[i1], pl.TAi[M1 + i1]};
-    const uint64_t tai2[2] = {pl.TAi2[i1], pl.TAi2[M1 + i1]};  // wrapped exponents: the weight was halved
+    const RowUnweight uw = row_unweight(pl, i1);
     uint64_t carry = 0;
     uint32_t addh[4] = {0, 0, 0, 0};   // first digits of the addend's run with its pending carry folded in (C >= 2)
     const uint2* ad = nullptr;
@@ -440,7 +439,7 @@ __device__ __forceinline__ void back_body(const DevPlan& pl, const uint64_t* Win
       if (ext.add_cbuf) {
         const uint2 p0 = ad[0], p1 = ad[1];
         addh[0] = p0.x; addh[1] = p0.y; addh[2] = p1.x; addh[3] = p1.y;
-        run_carry_in(pl, pl.SA[i1], T, carry_in_of(pl, ext.add_cbuf, T, i1), addh);
+        run_carry_in(pl, uw.sa[0], T, carry_in_of(pl, ext.add_cbuf, T, i1), addh);
       }
     }
     for (uint32_t c = 0; c < C; ++c) {
@@ -455,20 +454,9 @@ __device__ __forceinline__ void back_body(const DevPlan& pl, const uint64_t* Win
       }
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
-        uint32_t width; bool wrap;
-        digit_info(pl, sa[b], sb, width, wrap);
-        const uint64_t u = gf::mul(b ? x.b : x.a, wrap ? tai2[b] : tai[b]);
-        const uint64_t mask = (uint64_t(1) << width) - 1;
-        if (a == 1) {               // the common case (uniform): no 64-bit multiplies
-          const uint64_t r = u + carry + (EXT ? av[b] : 0u);   // u < 2^63 by the size rule (ibdwt.h:28-30), carry < 2^48, addend < 2^32
-          out[b] = uint32_t(r & mask);
-          carry = r >> width;
-        } else {                    // adc_mul (marin.cl:194-201): digit first, so that everything stays in 64 bits
-          const uint64_t dlo = u & mask, chi = u >> width;
-          const uint64_t r = dlo * a + carry + (EXT ? av[b] : 0u);
-          out[b] = uint32_t(r & mask);
-          carry = (r >> width) + chi * a;
-        }
+        uint32_t width;
+        const uint64_t u = unweigh(pl, uw, b, sb, b ? x.b : x.a, width);
+        out[b] = adc_mul(u, a, EXT ? av[b] : 0u, width, carry);
       }
       *(dg + i1 * C + c) = make_uint2(out[0], out[1]);
       if (EXT && ext.digits2) reinterpret_cast<uint2*>(ext.digits2)[size_t(T) * tile + size_t(i1) * C + c] = make_uint2(out[0], out[1]);
@@ -477,11 +465,17 @@ __device__ __forceinline__ void back_body(const DevPlan& pl, const uint64_t* Win
     if (EXT && ext.digits2) ext.cbuf2[size_t(T) * M1 + i1] = carry;
   }
 }
-template <bool EXT>
+template <bool EXT, bool LANES>
 __global__ void __launch_bounds__(1024) k_back(DevPlan pl, const uint64_t* __restrict__ Win, uint32_t* __restrict__ digits,
                                               uint64_t* __restrict__ cbuf, uint32_t a, BackExt ext) {
-  if (blockIdx.x >= pl.boost_tiles) __builtin_amdgcn_s_setprio(3);   // last half round: see kernels_v2.hip, boost_if_late (C4: -2.7 %)
-  back_body<EXT>(pl, Win, digits, cbuf, a, ext, xcd_tile(pl, blockIdx.x, gridDim.x), reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
+  if (blockIdx.x >= pl.boost_tiles) __builtin_amdgcn_s_setprio(3);   // last half round: see kernels_v2.hip, boost_if_late (C4: -2.7 %); never with lanes
+  BackExt x;
+  if (EXT) {
+    x.digits2 = lane_reg<LANES>(pl, ext.digits2); x.cbuf2 = lane_cbuf<LANES>(pl, ext.cbuf2);
+    x.add_digits = lane_reg<LANES>(pl, ext.add_digits); x.add_cbuf = lane_cbuf<LANES>(pl, ext.add_cbuf);
+  }
+  back_body<EXT>(pl, lane_reg<LANES>(pl, Win), lane_reg<LANES>(pl, digits), lane_cbuf<LANES>(pl, cbuf), a, x, xcd_tile(pl, blockIdx.x, gridDim.x),
+                 reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -489,7 +483,7 @@ __global__ void __launch_bounds__(1024) k_back(DevPlan pl, const uint64_t* __res
 // schedule (include/marin/engine_gpu.h:1624; forward80_0 ... there).  The radix-5 stage of the column transform runs on its own through a
 // second work buffer U ([k0][i2][t]: 5 blocks x M2 columns x L1 pairs), one thread per (column, t) and C = 1; the power-of-two part of
 // every block stays LDS-resident (L1 pairs x Cb columns).  Four sweeps instead of two around the row kernel: correct first, this size
-// exists for exponents above 3.0e9.
+// exists for exponents above 3.0e9.  (Never with lanes: plan.hpp refuses them at this size.)
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_front_split_a(DevPlan pl, const uint32_t* __restrict__ digits, uint64_t* __restrict__ Uout) {
   const size_t e = size_t(blockIdx.x) * 256 + threadIdx.x;
@@ -499,14 +493,7 @@ __global__ void __launch_bounds__(256) k_front_split_a(DevPlan pl, const uint32_
   const uint32_t sb = pl.SB[2 * i2];
   P2 x[5];
 #pragma unroll
-  for (int r = 0; r < 5; ++r) {
-    const uint32_t i1 = pl.L1 * r + t;
-    const uint2 d = dg[i1];
-    uint32_t w0, w1; bool wr0, wr1;
-    digit_info(pl, pl.SA[i1], sb, w0, wr0);
-    digit_info(pl, pl.SA[M1 + i1], sb, w1, wr1);
-    x[r] = {gf::mul_u32(pl.TAh[i1], d.x << (wr0 ? 0 : 1)), gf::mul_u32(pl.TAh[M1 + i1], d.y << (wr1 ? 0 : 1))};   // see k_front
-  }
+  for (int r = 0; r < 5; ++r) { const uint32_t i1 = pl.L1 * r + t; x[r] = weigh_pair(pl, i1, sb, dg[i1]); }
   dft5<false>(x, pl.W5c);
 #pragma unroll
   for (int k = 1; k < 5; ++k) x[k] = p2_mul(x[k], pl.UT1[t * k]);
@@ -525,14 +512,11 @@ __global__ void __launch_bounds__(1024) k_front_split_b(DevPlan pl, const uint64
     X[(pp << logCb) + c] = U[(size_t(k0) * pl.M2 + (T << logCb) + c) * pl.L1 + pp];
   }
   __syncthreads();
-  if (pl.logL1) lds_pow2_dft<false>(X, pl.L1, pl.logL1, 1, Cb, logCb, pl.UT1, pl.M1, pl.r5, pl.I4, tid, nthr);
+  if (pl.logL1) lds_pow2_dft<false>(X, pl.L1, pl.logL1, 1, Cb, logCb, pl.UT1, pl.M1, pl.r5, tid, nthr);
   P2* W = reinterpret_cast<P2*>(Wout);
   for (uint32_t e = tid; e < tile; e += nthr) {
     const uint32_t pp = e >> logCb, c = e & (Cb - 1), i2 = (T << logCb) + c, pos = k0 * pl.L1 + pp;
-    const uint64_t ex = uint64_t(i2) * freq1(pl, pos);
-    const uint64_t twb = gf::mul(tw_lookup(pl, ex), pl.TB[2 * i2]);
-    const P2 x = X[e];
-    W[size_t(pos) * pl.M2 + i2] = {gf::mul(x.a, twb), gf::mul(x.b, twb)};
+    W[size_t(pos) * pl.M2 + i2] = p2_mul(X[e], fourstep_word<false>(pl, pos, i2));
   }
 }
 __global__ void __launch_bounds__(1024) k_back_split_b(DevPlan pl, const uint64_t* __restrict__ Win, uint64_t* __restrict__ Uout, uint32_t logCb) {
@@ -542,13 +526,10 @@ __global__ void __launch_bounds__(1024) k_back_split_b(DevPlan pl, const uint64_
   const P2* W = reinterpret_cast<const P2*>(Win);
   for (uint32_t e = tid; e < tile; e += nthr) {
     const uint32_t pp = e >> logCb, c = e & (Cb - 1), i2 = (T << logCb) + c, pos = k0 * pl.L1 + pp;
-    const uint64_t ex = uint64_t(i2) * freq1(pl, pos);
-    const uint64_t twb = gf::mul(tw_lookup(pl, ex ? pl.m - ex : 0), pl.TBi[2 * i2]);
-    const P2 x = W[size_t(pos) * pl.M2 + i2];
-    X[e] = {gf::mul(x.a, twb), gf::mul(x.b, twb)};
+    X[e] = p2_mul(W[size_t(pos) * pl.M2 + i2], fourstep_word<true>(pl, pos, i2));
   }
   __syncthreads();
-  if (pl.logL1) lds_pow2_dft<true>(X, pl.L1, pl.logL1, 1, Cb, logCb, pl.UT1, pl.M1, pl.r5, pl.I4inv, tid, nthr);
+  if (pl.logL1) lds_pow2_dft<true>(X, pl.L1, pl.logL1, 1, Cb, logCb, pl.UT1, pl.M1, pl.r5, tid, nthr);
   P2* U = reinterpret_cast<P2*>(Uout);
   for (uint32_t e = tid; e < tile; e += nthr) {
     const uint32_t c = e >> pl.logL1, pp = e & (pl.L1 - 1);
@@ -574,47 +555,49 @@ __global__ void __launch_bounds__(256) k_back_split_a(DevPlan pl, const uint64_t
 #pragma unroll
   for (int r = 0; r < 5; ++r) {
     const uint32_t i1 = pl.L1 * r + t;
-    const uint32_t sa[2] = {pl.SA[i1], pl.SA[M1 + i1]};
-    const uint64_t tai[2] = {pl.TAi[i1], pl.TAi[M1 + i1]};
+    const RowUnweight uw = row_unweight(pl, i1);
     uint64_t carry = 0;
     uint32_t out[2];
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      uint32_t width; bool wrap;
-      digit_info(pl, sa[b], sb, width, wrap);
-      const uint64_t u = gf::mul(b ? x[r].b : x[r].a, wrap ? pl.TAi2[b ? M1 + i1 : i1] : tai[b]);
-      const uint64_t mask = (uint64_t(1) << width) - 1;
-      const uint64_t dlo = u & mask, chi = u >> width;      // adc_mul (marin.cl:194-201)
-      const uint64_t rr = dlo * a + carry;
-      out[b] = uint32_t(rr & mask);
-      carry = (rr >> width) + chi * a;
+      uint32_t width;
+      const uint64_t u = unweigh(pl, uw, b, sb, b ? x[r].b : x[r].a, width);
+      out[b] = adc_mul(u, a, 0u, width, carry);
     }
     dg[i1] = make_uint2(out[0], out[1]);
     cbuf[size_t(i2) * M1 + i1] = carry;
   }
 }
 
-// One thread per run: a, b (+ their pending carry words) -> sum and / or difference, each written to up to two
+// ---------------------------------------------------------------------------------------------
+// run-wise kernels: one thread per run (T, i1) of 2C digits
+// ---------------------------------------------------------------------------------------------
+struct RunHead { uint32_t T, i1; size_t ci, off; };   // ci: index of the run's carry word; off: of its first digit
+// the thread's run; false beyond the last one
+__device__ __forceinline__ bool run_head(const DevPlan& pl, RunHead& r) {
+  const uint32_t run = blockIdx.x * blockDim.x + threadIdx.x, M1 = pl.M1;
+  if (run >= M1 * (pl.M2 / pl.C)) return false;
+  r.T = run / M1; r.i1 = run - r.T * M1;
+  r.ci = size_t(r.T) * M1 + r.i1; r.off = r.ci * pl.C * 2;
+  return true;
+}
+
+// a, b (+ their pending carry words) -> sum and / or difference, each written to up to two
 // registers, with the run's carry-out word left pending (kernels.hpp LinArgs).  The difference is a - b + 2 Mp
 // digit by digit (neg2_mp4, marin.cl:246-256), so nothing goes negative: digits are below 2^width + a small excess.
-__device__ __forceinline__ void linear_body(const DevPlan& pl, const LinArgs& la, uint32_t run) {
-  const uint32_t M1 = pl.M1, C = pl.C, NT = pl.M2 / C;
-  if (run >= M1 * NT) return;
-  const uint32_t T = run / M1, i1 = run - T * M1;
-  const size_t off = (size_t(T) * M1 + i1) * C * 2;
-  const uint32_t sa = pl.SA[i1];
-  uint64_t ca = la.ca ? carry_in_of(pl, la.ca, T, i1) : 0, cb = la.cb ? carry_in_of(pl, la.cb, T, i1) : 0;
+__device__ __forceinline__ void linear_body(const DevPlan& pl, const LinArgs& la) {
+  RunHead r;
+  if (!run_head(pl, r)) return;
+  const uint32_t C = pl.C, sa = pl.SA[r.i1];
+  const size_t off = r.off;
+  uint64_t ca = la.ca ? carry_in_of(pl, la.ca, r.T, r.i1) : 0, cb = la.cb ? carry_in_of(pl, la.cb, r.T, r.i1) : 0;
   uint64_t cs = 0, cd = 0;
   const bool want_s = la.s1 != nullptr, want_d = la.d1 != nullptr;
   for (uint32_t k = 0; k < 2 * C; ++k) {
     uint32_t width; bool wrap;
-    digit_info(pl, sa, pl.SB[2 * (T * C) + k], width, wrap);
+    digit_info(pl, sa, pl.SB[2 * (r.T * C) + k], width, wrap);
     const uint64_t mask = (uint64_t(1) << width) - 1;
-    // inputs with their own (weak) carry-in: three masked digits, the rest stays on the fourth (adc4); runs of
-    // two digits (C = 1) take all of it on the second
-    uint64_t av = la.a[off + k], bv = la.b[off + k];
-    if (k < 3 && k + 1 < 2 * C) { av += ca; ca = av >> width; av &= mask; bv += cb; cb = bv >> width; bv &= mask; }
-    else if (k == 3 || k + 1 == 2 * C) { av += ca; ca = 0; bv += cb; cb = 0; }
+    const uint64_t av = take_carry_in(la.a[off + k], ca, k, 2 * C, width), bv = take_carry_in(la.b[off + k], cb, k, 2 * C, width);
     if (want_s) {
       const uint64_t v = av + bv + cs;
       const uint32_t o = uint32_t(v & mask);
@@ -630,66 +613,67 @@ __device__ __forceinline__ void linear_body(const DevPlan& pl, const LinArgs& la
       if (la.d2) la.d2[off + k] = o;
     }
   }
-  const size_t ci = size_t(T) * M1 + i1;
-  if (want_s) { la.cs1[ci] = cs; if (la.s2) la.cs2[ci] = cs; }
-  if (want_d) { la.cd1[ci] = cd; if (la.d2) la.cd2[ci] = cd; }
+  if (want_s) { la.cs1[r.ci] = cs; if (la.s2) la.cs2[r.ci] = cs; }
+  if (want_d) { la.cd1[r.ci] = cd; if (la.d2) la.cd2[r.ci] = cd; }
 }
-__global__ void __launch_bounds__(256) k_linear(DevPlan pl, LinArgs la) { linear_body(pl, la, blockIdx.x * blockDim.x + threadIdx.x); }
+template <bool LANES>
+__global__ void __launch_bounds__(256) k_linear(DevPlan pl, LinArgs la) {
+  LinArgs l;
+  l.a = lane_reg<LANES>(pl, la.a); l.ca = lane_cbuf<LANES>(pl, la.ca); l.b = lane_reg<LANES>(pl, la.b); l.cb = lane_cbuf<LANES>(pl, la.cb);
+  l.s1 = lane_reg<LANES>(pl, la.s1); l.cs1 = lane_cbuf<LANES>(pl, la.cs1); l.s2 = lane_reg<LANES>(pl, la.s2); l.cs2 = lane_cbuf<LANES>(pl, la.cs2);
+  l.d1 = lane_reg<LANES>(pl, la.d1); l.cd1 = lane_cbuf<LANES>(pl, la.cd1); l.d2 = lane_reg<LANES>(pl, la.d2); l.cd2 = lane_cbuf<LANES>(pl, la.cd2);
+  linear_body(pl, l);
+}
 
-
-// x a for the factors above the plan's fused bound (plan.hpp fused_factor_limit; Engine::scale): one thread per run, the run's digits with
-// their pending carry-in taken as k_linear takes them (three masked digits, the rest on the fourth; all of it on the second when C = 1),
-// times a with a carry through the run, whose carry-out word is left pending.  Digit outputs may alias the input, cout must not alias cin.
+// x a for the factors above the plan's fused bound (plan.hpp fused_factor_limit; Engine::scale): the run's digits with their pending
+// carry-in taken as k_linear takes them, times a with a carry through the run, whose carry-out word is left pending.  Digit outputs may
+// alias the input, cout must not alias cin.
 // Bounds: a digit after the carry-in is below 2^31 (fused_factor_ok), so digit a + carry < 2^63 + 2^(64 - q).
-__device__ __forceinline__ void scale_body(const DevPlan& pl, const uint32_t* in, const uint64_t* cin, uint32_t* out, uint64_t* cout, uint32_t a, uint32_t run) {
-  const uint32_t M1 = pl.M1, C = pl.C, NT = pl.M2 / C;
-  if (run >= M1 * NT) return;
-  const uint32_t T = run / M1, i1 = run - T * M1;
-  const size_t off = (size_t(T) * M1 + i1) * C * 2;
-  const uint32_t sa = pl.SA[i1];
-  uint64_t ci = cin ? carry_in_of(pl, cin, T, i1) : 0, c = 0;
+__device__ __forceinline__ void scale_body(const DevPlan& pl, const uint32_t* in, const uint64_t* cin, uint32_t* out, uint64_t* cout, uint32_t a) {
+  RunHead r;
+  if (!run_head(pl, r)) return;
+  const uint32_t C = pl.C, sa = pl.SA[r.i1];
+  uint64_t ci = cin ? carry_in_of(pl, cin, r.T, r.i1) : 0, c = 0;
   for (uint32_t k = 0; k < 2 * C; ++k) {
     uint32_t width; bool wrap;
-    digit_info(pl, sa, pl.SB[2 * (T * C) + k], width, wrap);
-    const uint64_t mask = (uint64_t(1) << width) - 1;
-    uint64_t xv = in[off + k];
-    if (k < 3 && k + 1 < 2 * C) { xv += ci; ci = xv >> width; xv &= mask; }
-    else if (k == 3 || k + 1 == 2 * C) { xv += ci; ci = 0; }
-    const uint64_t v = xv * a + c;
-    out[off + k] = uint32_t(v & mask);
+    digit_info(pl, sa, pl.SB[2 * (r.T * C) + k], width, wrap);
+    const uint64_t v = take_carry_in(in[r.off + k], ci, k, 2 * C, width) * a + c;
+    out[r.off + k] = uint32_t(v & ((uint64_t(1) << width) - 1));
     c = v >> width;
   }
-  cout[size_t(T) * M1 + i1] = c;
+  cout[r.ci] = c;
 }
+template <bool LANES>
 __global__ void __launch_bounds__(256) k_scale(DevPlan pl, const uint32_t* __restrict__ in, const uint64_t* __restrict__ cin,
                                                uint32_t* __restrict__ out, uint64_t* __restrict__ cout, uint32_t a) {
-  scale_body(pl, in, cin, out, cout, a, blockIdx.x * blockDim.x + threadIdx.x);
+  scale_body(pl, lane_reg<LANES>(pl, in), lane_cbuf<LANES>(pl, cin), lane_reg<LANES>(pl, out), lane_cbuf<LANES>(pl, cout), a);
 }
 
-
-// carry fix: one thread per run; weak carry (the remainder, if any, stays on the run's last digit:
-// same contract as adc4, marin.cl:203-212)
-__device__ __forceinline__ void carry_fix_body(const DevPlan& pl, uint32_t* digits, const uint64_t* cbuf, uint32_t run) {
-  const uint32_t M1 = pl.M1, C = pl.C, NT = pl.M2 / C;
-  if (run >= M1 * NT) return;
-  const uint32_t T = run / M1, i1 = run - T * M1;
-  uint64_t cin = carry_in_of(pl, cbuf, T, i1);
+// carry fix: weak carry (the remainder, if any, stays on the run's last digit: same contract as adc4, marin.cl:203-212); a loop of its
+// own, which ends as soon as no carry is left
+__device__ __forceinline__ void carry_fix_body(const DevPlan& pl, uint32_t* digits, const uint64_t* cbuf) {
+  RunHead r;
+  if (!run_head(pl, r)) return;
+  const uint32_t C = pl.C;
+  uint64_t cin = carry_in_of(pl, cbuf, r.T, r.i1);
   if (cin == 0) return;
-  uint32_t* d = digits + (size_t(T) * M1 + i1) * C * 2;
-  const uint32_t sa = pl.SA[i1];
+  uint32_t* d = digits + r.off;
+  const uint32_t sa = pl.SA[r.i1];   // after the early exit
   for (uint32_t k = 0; k < 2 * C; ++k) {
     if (k == 2 * C - 1) { d[k] += uint32_t(cin); break; }
     uint32_t width; bool wrap;
-    digit_info(pl, sa, pl.SB[2 * (T * C) + k], width, wrap);
+    digit_info(pl, sa, pl.SB[2 * (r.T * C) + k], width, wrap);
     const uint64_t v = uint64_t(d[k]) + cin;
     d[k] = uint32_t(v & ((uint64_t(1) << width) - 1));
     cin = v >> width;
     if (cin == 0) break;
   }
 }
+template <bool LANES>
 __global__ void __launch_bounds__(256) k_carry_fix(DevPlan pl, uint32_t* __restrict__ digits, const uint64_t* __restrict__ cbuf) {
-  carry_fix_body(pl, digits, cbuf, blockIdx.x * blockDim.x + threadIdx.x);
+  carry_fix_body(pl, lane_reg<LANES>(pl, digits), lane_cbuf<LANES>(pl, cbuf));
 }
+
 
 // digit j -> memory slot (Plan::pos)
 __device__ __forceinline__ size_t slot_of(const DevPlan& pl, uint32_t j) {
@@ -721,61 +705,11 @@ __device__ __forceinline__ void sub_small_body(const DevPlan& pl, uint32_t* digi
     }
   }
 }
-__global__ void k_sub_small(DevPlan pl, uint32_t* __restrict__ digits, uint32_t a) { sub_small_body(pl, digits, a); }
-
-// ---------------------------------------------------------------------------------------------
-// Lane engines (kernels.hpp LaneGeom): every register slot holds `lanes` independent residues, and one launch applies the sweep to all of
-// them.  blockIdx.y is the lane, blockIdx.x what it is in the single-lane kernel; the bodies are the ones above, on pointers moved to
-// the lane.  Entry points of their own: the single-lane kernels and their launches stay as they are.  (No priority boost here: with a
-// lane dimension the last half round of a launch is not the top of blockIdx.x.)
-// ---------------------------------------------------------------------------------------------
-template <class T> __device__ __forceinline__ T* lane_reg(const LaneGeom& lg, T* p) {   // a register, the work buffer or an image
-  return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + size_t(blockIdx.y) * lg.reg_bytes) : nullptr;
-}
-template <class T> __device__ __forceinline__ T* lane_cbuf(const LaneGeom& lg, T* p) { return p ? p + size_t(blockIdx.y) * lg.runs : nullptr; }
-
-__global__ void __launch_bounds__(1024) k_front_lanes(DevPlan pl, LaneGeom lg, const uint32_t* __restrict__ digits, const uint64_t* __restrict__ cbuf_in,
-                                                      uint64_t* __restrict__ Wout) {
-  front_body(pl, lane_reg(lg, digits), lane_cbuf(lg, cbuf_in), lane_reg(lg, Wout), blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
-}
-__global__ void __launch_bounds__(1024) k_middle_lanes(DevPlan pl, LaneGeom lg, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Yimg,
-                                                       const uint64_t* __restrict__ Yimg2, uint64_t* __restrict__ Wout, int mode) {
-  middle_body(pl, lane_reg(lg, Win), lane_reg(lg, Yimg), lane_reg(lg, Yimg2), lane_reg(lg, Wout), mode, blockIdx.x, reinterpret_cast<P2*>(smem_raw),
-              threadIdx.x, blockDim.x);
-}
-__global__ void __launch_bounds__(1024) k_middle_keep_lanes(DevPlan pl, LaneGeom lg, const uint64_t* __restrict__ Win, uint64_t* __restrict__ Wimg,
-                                                            uint64_t* __restrict__ Wout) {
-  middle_body<true>(pl, lane_reg(lg, Win), nullptr, nullptr, lane_reg(lg, Wout), 0, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x,
-                    lane_reg(lg, Wimg));
-}
-template <bool EXT>
-__global__ void __launch_bounds__(1024) k_back_lanes(DevPlan pl, LaneGeom lg, const uint64_t* __restrict__ Win, uint32_t* __restrict__ digits,
-                                                     uint64_t* __restrict__ cbuf, uint32_t a, BackExt ext) {
-  BackExt x;
-  if (EXT) {
-    x.digits2 = lane_reg(lg, ext.digits2); x.cbuf2 = lane_cbuf(lg, ext.cbuf2);
-    x.add_digits = lane_reg(lg, ext.add_digits); x.add_cbuf = lane_cbuf(lg, ext.add_cbuf);
-  }
-  back_body<EXT>(pl, lane_reg(lg, Win), lane_reg(lg, digits), lane_cbuf(lg, cbuf), a, x, xcd_tile(pl, blockIdx.x, gridDim.x),
-                 reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
-}
-__global__ void __launch_bounds__(256) k_linear_lanes(DevPlan pl, LaneGeom lg, LinArgs la) {
-  LinArgs l;
-  l.a = lane_reg(lg, la.a); l.ca = lane_cbuf(lg, la.ca); l.b = lane_reg(lg, la.b); l.cb = lane_cbuf(lg, la.cb);
-  l.s1 = lane_reg(lg, la.s1); l.cs1 = lane_cbuf(lg, la.cs1); l.s2 = lane_reg(lg, la.s2); l.cs2 = lane_cbuf(lg, la.cs2);
-  l.d1 = lane_reg(lg, la.d1); l.cd1 = lane_cbuf(lg, la.cd1); l.d2 = lane_reg(lg, la.d2); l.cd2 = lane_cbuf(lg, la.cd2);
-  linear_body(pl, l, blockIdx.x * blockDim.x + threadIdx.x);
-}
-__global__ void __launch_bounds__(256) k_scale_lanes(DevPlan pl, LaneGeom lg, const uint32_t* __restrict__ in, const uint64_t* __restrict__ cin,
-                                                     uint32_t* __restrict__ out, uint64_t* __restrict__ cout, uint32_t a) {
-  scale_body(pl, lane_reg(lg, in), lane_cbuf(lg, cin), lane_reg(lg, out), lane_cbuf(lg, cout), a, blockIdx.x * blockDim.x + threadIdx.x);
-}
-__global__ void __launch_bounds__(256) k_carry_fix_lanes(DevPlan pl, LaneGeom lg, uint32_t* __restrict__ digits, const uint64_t* __restrict__ cbuf) {
-  carry_fix_body(pl, lane_reg(lg, digits), lane_cbuf(lg, cbuf), blockIdx.x * blockDim.x + threadIdx.x);
-}
-__global__ void k_sub_small_lanes(DevPlan pl, LaneGeom lg, uint32_t* __restrict__ digits, uint32_t a) { sub_small_body(pl, lane_reg(lg, digits), a); }
+template <bool LANES>
+__global__ void k_sub_small(DevPlan pl, uint32_t* __restrict__ digits, uint32_t a) { sub_small_body(pl, lane_reg<LANES>(pl, digits), a); }
 
 // ------------------------------- launch wrappers ---------------------------------------------
+
 
 static inline uint32_t block_for(size_t work) {
   size_t b = 64;
@@ -784,9 +718,9 @@ static inline uint32_t block_for(size_t work) {
 }
 
 // work-group size for a tile of `pairs` pairs: a quarter of it (one radix-4 butterfly per thread and pass), or half of it when the whole
-// launch has no more work-groups than the chip has CUs (latency-bound: one plane per thread, lds_pow2_dft_planes)
-static inline uint32_t block_for_small(const DevPlan& pl, size_t pairs, size_t lanes = 1) {
-  const size_t groups = lanes * (size_t(pl.M1) * pl.M2 / (pairs ? pairs : 1));   // of the whole launch: a lane engine's launch has `lanes` times the tiles
+// launch has no more work-groups than the chip has CUs (latency-bound: one plane per thread, lds_pow2_passes)
+static inline uint32_t block_for_small(const DevPlan& pl, size_t pairs) {
+  const size_t groups = pl.lanes * (size_t(pl.M1) * pl.M2 / (pairs ? pairs : 1));   // of the whole launch: a lane engine's launch has `lanes` times the tiles
   // at most one work-group per CU (with two per CU the classic form wins: n = 2^21, 0.066 vs 0.073 ms; profiles/r02_ab_small_tiles.txt)
   if (groups > 256) return block_for(pairs / 4 ? pairs / 4 : 1);
   // one pair per thread in the element-wise loops where the tile allows (C2: 0.0331 -> 0.0318 ms), else one plane per thread
@@ -795,26 +729,30 @@ static inline uint32_t block_for_small(const DevPlan& pl, size_t pairs, size_t l
   return uint32_t(b);
 }
 
+// every launch: its grid without lanes in x, the lanes in y
 hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s) {
   const size_t tile = size_t(pl.M1) * pl.C;
-  hipLaunchKernelGGL(k_front, dim3(pl.M2 / pl.C), dim3(block_for_small(pl, tile)), tile * 16, s, pl, digits, cbuf_in, W);
+  hipLaunchKernelGGL(pl.lanes > 1 ? k_front<true> : k_front<false>, dim3(pl.M2 / pl.C, pl.lanes), dim3(block_for_small(pl, tile)), tile * 16, s, pl, digits, cbuf_in, W);
   return hipGetLastError();
 }
 hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s) {
   if (mode < 0 || mode > 4) return hipErrorInvalidValue;
-  if (mode == 4) hipLaunchKernelGGL(k_middle_keep, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Wimg, Wout);
-  else hipLaunchKernelGGL(k_middle, dim3(pl.M1), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Y, Y2, Wout, mode);
+  const dim3 grid(pl.M1, pl.lanes), block(block_for_small(pl, pl.M2));
+  if (mode == 4) hipLaunchKernelGGL(pl.lanes > 1 ? k_middle_keep<true> : k_middle_keep<false>, grid, block, size_t(pl.M2) * 16, s, pl, Win, Wimg, Wout);
+  else hipLaunchKernelGGL(pl.lanes > 1 ? k_middle<true> : k_middle<false>, grid, block, size_t(pl.M2) * 16, s, pl, Win, Y, Y2, Wout, mode);
+  return hipGetLastError();
+}
+template <bool EXT>
+static hipError_t launch_back_of(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s) {
+  const size_t tile = size_t(pl.M1) * pl.C;
+  hipLaunchKernelGGL((pl.lanes > 1 ? k_back<EXT, true> : k_back<EXT, false>), dim3(pl.M2 / pl.C, pl.lanes), dim3(block_for_small(pl, tile)), tile * 16, s, pl, W, digits, cbuf, a, x);
   return hipGetLastError();
 }
 hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s) {
-  const size_t tile = size_t(pl.M1) * pl.C;
-  hipLaunchKernelGGL(k_back<false>, dim3(pl.M2 / pl.C), dim3(block_for_small(pl, tile)), tile * 16, s, pl, W, digits, cbuf, a, BackExt());
-  return hipGetLastError();
+  return launch_back_of<false>(pl, W, digits, cbuf, a, BackExt(), s);
 }
 hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s) {
-  const size_t tile = size_t(pl.M1) * pl.C;
-  hipLaunchKernelGGL(k_back<true>, dim3(pl.M2 / pl.C), dim3(block_for_small(pl, tile)), tile * 16, s, pl, W, digits, cbuf, a, x);
-  return hipGetLastError();
+  return launch_back_of<true>(pl, W, digits, cbuf, a, x, s);
 }
 // the split column sweeps (M1 = 5 L1 beyond LDS): U is a second work buffer of 8 n bytes
 static uint32_t split_log_cb(const DevPlan& pl) { uint32_t l = 0; while ((size_t(pl.L1) << (l + 1)) * 16 <= size_t(128) * 1024 && (2u << l) <= pl.M2 && l < 2) ++l; return l; }
@@ -841,90 +779,42 @@ hipError_t configure_split(const DevPlan& pl) {
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute(reinterpret_cast<const void*>(k_back_split_b), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
 }
+// the run-wise launches: 256 runs a work-group
+static dim3 run_grid(const DevPlan& pl) { return dim3(uint32_t((size_t(pl.M1) * (pl.M2 / pl.C) + 255) / 256), pl.lanes); }
 hipError_t launch_linear(const DevPlan& pl, const LinArgs& la, hipStream_t s) {
-  const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
-  hipLaunchKernelGGL(k_linear, dim3((runs + 255) / 256), dim3(256), 0, s, pl, la);
+  hipLaunchKernelGGL(pl.lanes > 1 ? k_linear<true> : k_linear<false>, run_grid(pl), dim3(256), 0, s, pl, la);
   return hipGetLastError();
 }
 hipError_t launch_scale(const DevPlan& pl, const uint32_t* in, const uint64_t* cin, uint32_t* out, uint64_t* cout, uint32_t a, hipStream_t s) {
-  const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
-  hipLaunchKernelGGL(k_scale, dim3((runs + 255) / 256), dim3(256), 0, s, pl, in, cin, out, cout, a);
+  hipLaunchKernelGGL(pl.lanes > 1 ? k_scale<true> : k_scale<false>, run_grid(pl), dim3(256), 0, s, pl, in, cin, out, cout, a);
   return hipGetLastError();
 }
 hipError_t launch_carry_fix(const DevPlan& pl, uint32_t* digits, const uint64_t* cbuf, hipStream_t s) {
-  const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
-  hipLaunchKernelGGL(k_carry_fix, dim3((runs + 255) / 256), dim3(256), 0, s, pl, digits, cbuf);
+  hipLaunchKernelGGL(pl.lanes > 1 ? k_carry_fix<true> : k_carry_fix<false>, run_grid(pl), dim3(256), 0, s, pl, digits, cbuf);
   return hipGetLastError();
 }
 hipError_t launch_sub_small(const DevPlan& pl, uint32_t* digits, uint32_t a, hipStream_t s) {
-  hipLaunchKernelGGL(k_sub_small, dim3(1), dim3(64), 0, s, pl, digits, a);
+  hipLaunchKernelGGL(pl.lanes > 1 ? k_sub_small<true> : k_sub_small<false>, dim3(1, pl.lanes), dim3(64), 0, s, pl, digits, a);
   return hipGetLastError();
 }
-// the lane launches: the single-lane grid in x, the lanes in y
-hipError_t launch_front_lanes(const DevPlan& pl, const LaneGeom& lg, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s) {
-  const size_t tile = size_t(pl.M1) * pl.C;
-  hipLaunchKernelGGL(k_front_lanes, dim3(pl.M2 / pl.C, lg.lanes), dim3(block_for_small(pl, tile, lg.lanes)), tile * 16, s, pl, lg, digits, cbuf_in, W);
-  return hipGetLastError();
-}
-hipError_t launch_middle_lanes(const DevPlan& pl, const LaneGeom& lg, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout,
-                               int mode, hipStream_t s) {
-  if (mode < 0 || mode > 4) return hipErrorInvalidValue;
-  const dim3 grid(pl.M1, lg.lanes), block(block_for_small(pl, pl.M2, lg.lanes));
-  if (mode == 4) hipLaunchKernelGGL(k_middle_keep_lanes, grid, block, size_t(pl.M2) * 16, s, pl, lg, Win, Wimg, Wout);
-  else hipLaunchKernelGGL(k_middle_lanes, grid, block, size_t(pl.M2) * 16, s, pl, lg, Win, Y, Y2, Wout, mode);
-  return hipGetLastError();
-}
-hipError_t launch_back_lanes(const DevPlan& pl, const LaneGeom& lg, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt* x, hipStream_t s) {
-  const size_t tile = size_t(pl.M1) * pl.C;
-  const dim3 grid(pl.M2 / pl.C, lg.lanes), block(block_for_small(pl, tile, lg.lanes));
-  if (x) hipLaunchKernelGGL(k_back_lanes<true>, grid, block, tile * 16, s, pl, lg, W, digits, cbuf, a, *x);
-  else hipLaunchKernelGGL(k_back_lanes<false>, grid, block, tile * 16, s, pl, lg, W, digits, cbuf, a, BackExt());
-  return hipGetLastError();
-}
-hipError_t launch_linear_lanes(const DevPlan& pl, const LaneGeom& lg, const LinArgs& la, hipStream_t s) {
-  const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
-  hipLaunchKernelGGL(k_linear_lanes, dim3((runs + 255) / 256, lg.lanes), dim3(256), 0, s, pl, lg, la);
-  return hipGetLastError();
-}
-hipError_t launch_scale_lanes(const DevPlan& pl, const LaneGeom& lg, const uint32_t* in, const uint64_t* cin, uint32_t* out, uint64_t* cout, uint32_t a, hipStream_t s) {
-  const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
-  hipLaunchKernelGGL(k_scale_lanes, dim3((runs + 255) / 256, lg.lanes), dim3(256), 0, s, pl, lg, in, cin, out, cout, a);
-  return hipGetLastError();
-}
-hipError_t launch_carry_fix_lanes(const DevPlan& pl, const LaneGeom& lg, uint32_t* digits, const uint64_t* cbuf, hipStream_t s) {
-  const size_t runs = size_t(pl.M1) * (pl.M2 / pl.C);
-  hipLaunchKernelGGL(k_carry_fix_lanes, dim3((runs + 255) / 256, lg.lanes), dim3(256), 0, s, pl, lg, digits, cbuf);
-  return hipGetLastError();
-}
-hipError_t launch_sub_small_lanes(const DevPlan& pl, const LaneGeom& lg, uint32_t* digits, uint32_t a, hipStream_t s) {
-  hipLaunchKernelGGL(k_sub_small_lanes, dim3(1, lg.lanes), dim3(64), 0, s, pl, lg, digits, a);
-  return hipGetLastError();
-}
-hipError_t configure_lane_kernels(size_t lds_front, size_t lds_mid) {
-  const void* cols[3] = {reinterpret_cast<const void*>(k_front_lanes), reinterpret_cast<const void*>(k_back_lanes<false>), reinterpret_cast<const void*>(k_back_lanes<true>)};
-  const void* rows[2] = {reinterpret_cast<const void*>(k_middle_lanes), reinterpret_cast<const void*>(k_middle_keep_lanes)};
-  for (const void* f : cols)
-    if (lds_front > 48 * 1024) { hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_front)); if (e != hipSuccess) return e; }
-  for (const void* f : rows)
-    if (lds_mid > 48 * 1024) { hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_mid)); if (e != hipSuccess) return e; }
+// the dynamic-LDS attribute of the five tile kernels: of the instantiations without lanes for every engine (as before there were lanes),
+// of those with lanes for an engine that has them
+template <bool LANES>
+static hipError_t configure_kernels_of(size_t lds_front, size_t lds_mid) {
+  const struct { const void* fn; size_t lds; } ks[5] = {
+      {reinterpret_cast<const void*>(k_front<LANES>), lds_front}, {reinterpret_cast<const void*>(k_back<false, LANES>), lds_front},
+      {reinterpret_cast<const void*>(k_back<true, LANES>), lds_front}, {reinterpret_cast<const void*>(k_middle<LANES>), lds_mid},
+      {reinterpret_cast<const void*>(k_middle_keep<LANES>), lds_mid}};
+  for (const auto& k : ks)
+    if (k.lds > 48 * 1024) {
+      hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(k.lds));
+      if (e != hipSuccess) return e;
+    }
   return hipSuccess;
 }
-hipError_t configure_kernels(size_t lds_front, size_t lds_mid) {
-  hipError_t e = hipSuccess;
-  if (lds_front > 48 * 1024) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_front), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_front));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_back<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_front));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_back<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_front));
-    if (e != hipSuccess) return e;
-  }
-  if (lds_mid > 48 * 1024) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_middle), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_mid));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_middle_keep), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_mid));
-  }
-  return e;
+hipError_t configure_kernels(size_t lds_front, size_t lds_mid, uint32_t lanes) {
+  hipError_t e = configure_kernels_of<false>(lds_front, lds_mid);
+  return (e != hipSuccess || lanes <= 1) ? e : configure_kernels_of<true>(lds_front, lds_mid);
 }
 
 }  // namespace mi355

@@ -7,12 +7,17 @@ namespace mi355 {
 
 struct DevPlan {
   uint32_t n, m, M1, M2, L1, logL1, logM2, r5, C, logC, q, t, twh;
+  // Residues per register (plan token lanes=B; 1: a plain engine).  A register slot -- and the work buffer, and a multiplicand image -- is
+  // `lanes` single-lane registers 8 n bytes apart, a carry buffer `lanes` x M1 M2 / C words.  The generic kernels (kernels.hip) take the lane
+  // from blockIdx.y and move their pointers, which are those of lane 0, to it (their instantiations k<true>; lanes == 1 launches k<false>,
+  // which leaves the pointers alone); no other kernel set reads this.
+  uint32_t lanes;
   const uint32_t *SA, *SB;
   const uint64_t *TA, *TAi, *TB, *TBi;
   const uint64_t *TAh, *TAi2;   // TA / 2 and 2 TAi, entry by entry: what the sweeps multiply with when the exponent split wraps (no per-thread half / double)
   const uint64_t *TWlo, *TWhi, *UT1, *UT2;
   const uint64_t *S2r, *S2ri, *S1r, *S1ri;   // seam tables of the radix-8 kernels (null when the shape is not served)
-  uint64_t I4, I4inv;
+  uint64_t I4, I4inv;   // no kernel reads them any more (omega_4 = 2^48 is a shift); they stay so that every later member keeps its offset
   uint64_t W5c[4];   // 5-point DFT constants {beta, k1, k2-k1, k1+k2} (kernels.hip dft5)
   const uint64_t *F0f, *F0i, *FBf, *FBi;   // four-step chain starts [tile][thread] and ratios [column] of the v2 column kernels
   const uint32_t* DI;   // digit-info words of the v2 column kernels: [tile][thread] 16 x (width - q, wrap), or null
@@ -86,26 +91,12 @@ typedef hipError_t (*FourStepFn)(const DevPlan& pl, uint64_t* f0f, uint64_t* f0i
 typedef hipError_t (*RowsFn)(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
 struct ColSweeps { FrontFn front; BackFn back; BackExtFn back_ext; FourStepFn build_fourstep; };
 
-// generic set (kernels.hip): tiles in LDS, any shape
-hipError_t configure_kernels(size_t lds_front, size_t lds_mid);
+// generic set (kernels.hip): tiles in LDS, any shape, pl.lanes lanes as grid.y (the run-wise launchers above too)
+hipError_t configure_kernels(size_t lds_front, size_t lds_mid, uint32_t lanes);
 hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s);
 hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
 hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s);
 hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
-// Lane engines (plan token lanes=B, B > 1): a register slot -- and the work buffer, and a multiplicand image -- is `lanes` single-lane
-// registers reg_bytes apart, a carry buffer `lanes` x runs words.  Every launch below is the single-lane one with the lanes as grid.y
-// (kernels.hip k_*_lanes: the same bodies on pointers moved to lane blockIdx.y); pointers are those of lane 0, null stays null.
-// launch_back_lanes: x null for the plain back sweep.
-struct LaneGeom { uint32_t lanes; size_t reg_bytes; size_t runs; };
-hipError_t configure_lane_kernels(size_t lds_front, size_t lds_mid);
-hipError_t launch_front_lanes(const DevPlan& pl, const LaneGeom& lg, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s);
-hipError_t launch_middle_lanes(const DevPlan& pl, const LaneGeom& lg, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout,
-                               int mode, hipStream_t s);
-hipError_t launch_back_lanes(const DevPlan& pl, const LaneGeom& lg, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt* x, hipStream_t s);
-hipError_t launch_linear_lanes(const DevPlan& pl, const LaneGeom& lg, const LinArgs& la, hipStream_t s);
-hipError_t launch_scale_lanes(const DevPlan& pl, const LaneGeom& lg, const uint32_t* in, const uint64_t* cin, uint32_t* out, uint64_t* cout, uint32_t a, hipStream_t s);
-hipError_t launch_carry_fix_lanes(const DevPlan& pl, const LaneGeom& lg, uint32_t* digits, const uint64_t* cbuf, hipStream_t s);
-hipError_t launch_sub_small_lanes(const DevPlan& pl, const LaneGeom& lg, uint32_t* digits, uint32_t a, hipStream_t s);
 // columns of 5 L1 pairs that do not fit LDS (n = 5 * 2^26): the radix-5 stage through a second work buffer U (8 n bytes), C = 1
 hipError_t configure_split(const DevPlan& pl);
 hipError_t launch_front_split(const DevPlan& pl, const uint32_t* digits, uint64_t* U, uint64_t* W, hipStream_t s);

@@ -408,7 +408,7 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
 // The kernels a plan runs: those that serve its shape, narrowed by MI355_KERNELS (A/B tests, debugging): unset or "v2" keeps them,
 // "v2rows" / "v2cols" keep only the register-resident rows / columns, anything else takes the generic ones (the split sweeps stay).
 inline KernelChoice choose_kernels(const Plan& pl, const char* mi355_kernels) {
-  if (pl.lanes > 1) return KernelChoice{};   // lane engines run the generic set, whatever serves the shape (kernels.hip k_*_lanes)
+  if (pl.lanes > 1) return KernelChoice{};   // lane engines run the generic set, whatever serves the shape (the only one that reads DevPlan.lanes)
   KernelChoice k = served_kernels(pl.r5, pl.M1, pl.M2, pl.C, pl.split5);
   const std::string sel = mi355_kernels ? mi355_kernels : "v2";
   if (sel != "v2" && sel != "v2rows") k.rows = RowKernels::kGeneric;

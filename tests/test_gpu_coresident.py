@@ -6,7 +6,7 @@ two and three engines from threads that construct them at the same moment.  Ever
 (When these tests were written every case passed on an MI355X as the library stood: a kernel whose attribute a later engine had set to
 64 KiB still launched with 128 KiB of dynamic LDS, as the HIP header's remark that AMD devices ignore the attribute suggests.  The
 tests pin that; should a runtime start to enforce the attribute, configure_kernels / configure_split have to keep a running maximum.)
-Lane engines (plan token lanes=B) set the same attribute on kernels of their own (configure_lane_kernels); they appear in both parts, beside a
+Lane engines (plan token lanes=B) launch the same generic kernels with the lanes as grid.y and set the same attribute; they appear in both parts, beside a
 plain engine of the same plan and beside a lane engine of another tile size and lane count, and run the program of lane_program.py, every
 lane compared with its integer model.
 One engine used from two threads is not a supported pattern and is not tested.

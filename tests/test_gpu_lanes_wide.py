@@ -280,7 +280,7 @@ def test_one_lane_written_and_read_at_the_edges_of_the_range(p, spec, lanes, mon
 SWITCH_SHAPES = [(9941, "m2=16,c=4", 3), (301447, None, 9), (86243, "c=1", 3),
                  (9815459, None, 2)]    # its single-lane default is the radix-4 set, which lanes must not pick up
 KERNELS = [None, "generic", "v2rows", "v2cols"]
-TUNE = [0, 1, 32, 33]                   # bit 0: the tile order of the back sweep (xcd_tile in k_back_lanes)
+TUNE = [0, 1, 32, 33]                   # bit 0: the tile order of the back sweep (xcd_tile in k_back, lanes as grid.y)
 HOST_CARRY = [None, "1"]                # the host read path lane by lane, and the host branch of the lane writes
 
 
