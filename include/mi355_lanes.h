@@ -13,6 +13,14 @@
  *     are refused ("not with lanes"); the four entry points below read and write one lane.
  * On a handle without lanes (and on a crt handle) there is the one lane 0, which is the register itself.
  *
+ * The plan token onelaunch ("lanes=512,onelaunch"; p <= 204799, that is a transform of at most 8192 digits) makes every product of the
+ * engine -- square_mul, prepare, mul, mul_add, mul_copy, square_mul_copy, mul_sum, square_mul_prepare -- one launch instead of three: a
+ * whole lane, front sweep, row sweep and back sweep, runs in one work-group with its work buffer in LDS, and lanes smaller than a
+ * work-group share one.  Registers, pending carries and multiplicand images are those of an engine without the token, so every other
+ * entry point serves it unchanged; mi355_engine_time_square_mul is refused (there are no phases to time).  It works with any lane count,
+ * 1 included (a plain engine with one-launch products), and is refused, with a message that names it, above p = 204799, with c=1, with
+ * split5 and on "crt..." specs.  It is never chosen by itself.
+ *
  * Conventions as in mi355_engine.h: 1 = ok, 0 = failure with the message in mi355_engine_last_error(); nothing escapes.
  */
 #ifndef MI355_LANES_H

@@ -47,6 +47,7 @@ bool parse_crt_spec(const char* spec, CrtSpec& out) {
   if (!spec || std::strncmp(spec, "crt", 3) != 0 || (spec[3] != 0 && spec[3] != ':')) return false;
   if (const char* l = std::strstr(spec, "lanes="))   // lanes are the Goldilocks family's (plan.hpp)
     if (std::strcmp(l, "lanes=1") != 0) throw std::runtime_error("lanes: not implemented for the crt field family");
+  if (std::strstr(spec, "onelaunch")) throw std::runtime_error("onelaunch: not implemented for the crt field family");   // (plan.hpp: the Goldilocks family's too)
   std::string s = spec[3] ? spec + 4 : "";
   size_t pos = 0;
   bool first = true;

@@ -111,6 +111,8 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
   dp_.M1 = pl_.M1; dp_.M2 = pl_.M2; dp_.L1 = pl_.L1; dp_.logL1 = pl_.logL1; dp_.logM2 = pl_.logM2;
   dp_.r5 = pl_.r5; dp_.C = pl_.C; dp_.logC = 0; while ((1u << dp_.logC) < pl_.C) ++dp_.logC; dp_.q = pl_.q; dp_.t = pl_.t; dp_.twh = pl_.twh;
   dp_.lanes = pl_.lanes;
+  dp_.onelaunch = pl_.onelaunch ? 1u : 0u;
+  one_ = onelaunch_shape(pl_.m, pl_.r5, pl_.lanes);
   dp_.I4 = pl_.I4; dp_.I4inv = pl_.I4inv;
   dp_.DI = nullptr;
   dp_.F0f = dp_.F0i = dp_.FBf = dp_.FBi = nullptr;
@@ -131,13 +133,13 @@ Engine::Engine(uint32_t p, size_t reg_count, int device, bool verbose, const cha
     dp_.boost_rows = from(pl_.M2 == 2048 ? pl_.M1 / 2 : pl_.M1);   // (rows of 2048 go two to a tile on the register-resident row kernel)
     dp_.boost_tiles = lanes_ > 1 ? ~0u : from(pl_.tiles());   // with a lane dimension the last half round of a launch is not the top of blockIdx.x
   }
-  HIPCHK(configure_kernels(pl_.lds_front, pl_.lds_mid, pl_.lanes));
+  HIPCHK(configure_kernels(pl_.lds_front, pl_.lds_mid, pl_.lanes, pl_.onelaunch));
   if (pl_.split5) {
     HIPCHK(configure_split(dp_));
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&split_), reg_bytes_));
   }
   // kernel variants: those that serve the shape (plan.hpp), narrowed by MI355_KERNELS=generic|v2rows|v2cols (A/B tests, debugging);
-  // with lanes always the generic set, whose launches take the lanes as grid.y (kernels.hpp DevPlan.lanes)
+  // with lanes always the generic set, whose launches take the lanes as grid.y (kernels.hpp DevPlan.lanes); with one-launch products too
   kc_ = choose_kernels(pl_, std::getenv("MI355_KERNELS"));
   cols_ = col_sweeps(kc_.cols);
   rows_ = row_sweep(kc_.rows);
@@ -234,6 +236,28 @@ void Engine::run_back(size_t r, uint32_t a, hipEvent_t* ev) {
   if (pl_.C >= 2) pending_carry_[r] = 1;
   else carry_fix_now(r);
   if (ev) HIPCHK(hipEventRecord(ev[1], stream_));
+}
+
+// One-launch products (plan token onelaunch; kernels.hip k_onelaunch): front sweep on digits(r) (+ its pending run carries), the row sweep
+// in `mode` (y, y2: multiplicand images read in modes 1 and 3; img: the image written in modes 2 and 4) and, unless mode 2, the back sweep
+// into digits(r) with factor a and the extras of back_ext, all in one launch.  The new run carries go to a spare buffer: the launch reads
+// the pending ones of r and of the addend, which may be r itself.  Such plans have runs of four digits or more (plan.hpp), so the carries
+// stay pending.
+void Engine::one_launch(size_t r, int mode, const uint64_t* y, const uint64_t* y2, uint64_t* img, uint32_t a, long copy_to, long add_src) {
+  OneLaunchArgs oa;
+  oa.src = digits(r); oa.src_cbuf = pending_carry_[r] ? cbuf(r) : nullptr;
+  oa.y = y; oa.y2 = y2; oa.img = img; oa.a = a; oa.mode = mode;
+  oa.TL = one_.TL; oa.K = one_.K; oa.groups = one_.groups;
+  BackExt x;
+  if (mode == 2) { HIPCHK(launch_onelaunch(dp_, oa, x, stream_)); return; }
+  if (copy_to >= 0 && size_t(copy_to) != r) { x.digits2 = digits(size_t(copy_to)); x.cbuf2 = cbuf(size_t(copy_to)); }
+  if (add_src >= 0) { x.add_digits = digits(size_t(add_src)); x.add_cbuf = pending_carry_[size_t(add_src)] ? cbuf(size_t(add_src)) : nullptr; }
+  uint64_t* fresh = take_spare_cbuf();
+  oa.dst = digits(r); oa.dst_cbuf = fresh;
+  HIPCHK(launch_onelaunch(dp_, oa, x, stream_));
+  adopt_cbuf(r, fresh);
+  kind_[r] = kDigits; pending_carry_[r] = 1;
+  if (x.digits2) { kind_[size_t(copy_to)] = kDigits; pending_carry_[size_t(copy_to)] = 1; }
 }
 
 // ---- host digit I/O -------------------------------------------------------------------------
@@ -460,6 +484,7 @@ void Engine::copy(size_t dst, size_t src) {
 
 void Engine::square_chain(size_t r, uint32_t a, hipEvent_t* ev) {
   if (a > pl_.a_fast) { square_chain(r, 1, ev); scale(r, a); return; }   // beyond the fused carry's bound (plan.hpp fused_factor_limit)
+  if (pl_.onelaunch) { one_launch(r, 0, nullptr, nullptr, nullptr, a, -1, -1); return; }   // (never with events: time_square_mul refuses the plan)
   if (ev) HIPCHK(hipEventRecord(ev[0], stream_));
   run_front(r);
   if (ev) HIPCHK(hipEventRecord(ev[1], stream_));
@@ -484,8 +509,11 @@ void Engine::square_mul_n(size_t r, uint32_t a, size_t count, uint32_t sub) {
 void Engine::set_multiplicand(size_t dst, size_t src) {
   need_residue(src, "set_multiplicand"); need_register(dst, "set_multiplicand");
   HIPCHK(hipSetDevice(device_));
-  run_front(src);
-  run_middle(work(), nullptr, image(dst), 2);
+  if (pl_.onelaunch) one_launch(src, 2, nullptr, nullptr, image(dst), 1, -1, -1);
+  else {
+    run_front(src);
+    run_middle(work(), nullptr, image(dst), 2);
+  }
   kind_[dst] = kImage;
   pending_carry_[dst] = 0;
 }
@@ -493,9 +521,12 @@ void Engine::set_multiplicand(size_t dst, size_t src) {
 void Engine::mul(size_t dst, size_t src, uint32_t a) {
   need_residue(dst, "mul"); need_image(src, "mul"); need_factor(a, "mul");
   HIPCHK(hipSetDevice(device_));
-  run_front(dst);
-  run_middle(work(), image(src), work(), 1);
-  run_back(dst, a > pl_.a_fast ? 1u : a);
+  if (pl_.onelaunch) one_launch(dst, 1, image(src), nullptr, nullptr, a > pl_.a_fast ? 1u : a, -1, -1);
+  else {
+    run_front(dst);
+    run_middle(work(), image(src), work(), 1);
+    run_back(dst, a > pl_.a_fast ? 1u : a);
+  }
   if (a > pl_.a_fast) scale(dst, a);
 }
 
@@ -573,6 +604,7 @@ void Engine::square_mul_copy(size_t src, size_t dst_copy, uint32_t a) {
   need_residue(src, "square_mul_copy"); need_register(dst_copy, "square_mul_copy"); need_factor(a, "square_mul_copy");
   HIPCHK(hipSetDevice(device_));
   if (dst_copy == src || !kc_.fused_back() || a > pl_.a_fast) { RegisterMachine::square_mul_copy(src, dst_copy, a); return; }
+  if (pl_.onelaunch) { one_launch(src, 0, nullptr, nullptr, nullptr, a, long(dst_copy), -1); return; }
   run_front(src);
   run_middle(work(), nullptr, work(), 0);
   back_ext(src, a, long(dst_copy), -1);
@@ -583,6 +615,7 @@ void Engine::mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t a) {
   if (dst_copy == src) throw std::runtime_error("mul_copy: the multiplicand must differ from the outputs");
   HIPCHK(hipSetDevice(device_));
   if (dst_copy == dst || !kc_.fused_back() || a > pl_.a_fast) { RegisterMachine::mul_copy(dst, src, dst_copy, a); return; }
+  if (pl_.onelaunch) { one_launch(dst, 1, image(src), nullptr, nullptr, a, long(dst_copy), -1); return; }
   run_front(dst);
   run_middle(work(), image(src), work(), 1);
   back_ext(dst, a, long(dst_copy), -1);
@@ -597,6 +630,7 @@ void Engine::mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t a) {
                                           : "mul_add: add_src == dst needs the fused sweep, which takes factors up to the plan's fused bound only (mi355_engine.h)");
     RegisterMachine::mul_add(dst, mul_src, add_src, a); return;
   }
+  if (pl_.onelaunch) { one_launch(dst, 1, image(mul_src), nullptr, nullptr, a, -1, long(add_src)); return; }
   run_front(dst);   // reads digits(dst) (+ pending carries) and leaves them in place
   run_middle(work(), image(mul_src), work(), 1);
   back_ext(dst, a, -1, long(add_src));
@@ -607,6 +641,7 @@ void Engine::mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp) {
   if (!pl_.sum_fast) { RegisterMachine::mul_sum(dst, src_a, src_b, tmp); return; }   // the summed operand is beyond the plan's capacity (plan.hpp sum_product_ok)
   check_mul_sum(dst, src_a, src_b, tmp);
   HIPCHK(hipSetDevice(device_));
+  if (pl_.onelaunch) { one_launch(dst, 3, image(src_a), image(src_b), nullptr, 1, -1, -1); return; }
   run_front(dst);   // pending run carries (and a borrowed-through sub) of dst go in exactly as in mul
   run_middle(work(), image(src_a), work(), 3, image(src_b));
   run_back(dst, 1);
@@ -617,11 +652,14 @@ void Engine::mul_sum(size_t dst, size_t src_a, size_t src_b, size_t tmp) {
 void Engine::square_mul_prepare(size_t src, size_t img_out, uint32_t a) {
   check_square_mul_prepare(src, img_out, a);
   HIPCHK(hipSetDevice(device_));
-  run_front(src);
-  run_middle(work(), nullptr, work(), 4, nullptr, image(img_out));
+  if (pl_.onelaunch) one_launch(src, 4, nullptr, nullptr, image(img_out), a > pl_.a_fast ? 1u : a, -1, -1);
+  else {
+    run_front(src);
+    run_middle(work(), nullptr, work(), 4, nullptr, image(img_out));
+  }
   kind_[img_out] = kImage;
   pending_carry_[img_out] = 0;
-  run_back(src, a > pl_.a_fast ? 1u : a);
+  if (!pl_.onelaunch) run_back(src, a > pl_.a_fast ? 1u : a);
   if (a > pl_.a_fast) scale(src, a);   // beyond the fused carry's bound: the rule of square_mul
 }
 
@@ -707,6 +745,7 @@ const char* Engine::stage_name(size_t k) {
 // interval carries one record, ~4-5 us, and a path that launches no kernel between two records shows it as a kernel).
 void Engine::time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, double* total_ms, double* kernel_ms, size_t kcount) {
   no_lanes("time_square_mul");
+  if (pl_.onelaunch) throw std::runtime_error("time_square_mul: not with one-launch products (plan token onelaunch): a squaring has no phases to time");
   need_residue(r, "time_square_mul");
   if (a == 0 || iters == 0) throw std::runtime_error("time_square_mul: factor and iters must be >= 1");
   HIPCHK(hipSetDevice(device_));

@@ -57,7 +57,7 @@ class Engine final : public RegisterMachine {
   void mul_add(size_t dst, size_t mul_src, size_t add_src, uint32_t a) override;
   void square_mul_copy(size_t src, size_t dst_copy, uint32_t a) override;
   void mul_copy(size_t dst, size_t src, size_t dst_copy, uint32_t a) override;
-  // three launches per squaring, straight down square_chain (the benchmark's path)
+  // three launches per squaring, straight down square_chain (the benchmark's path); one with the plan token onelaunch (one_launch below)
   void square_mul_n(size_t r, uint32_t a, size_t count, uint32_t sub) override;
   void square_mul_bits(size_t r, uint32_t factor, const uint8_t* bits, size_t nbits) override;
   // one product through the row sweep's mode 3 where the plan's capacity allows it (plan.hpp sum_product_ok), else the base's two products;
@@ -113,6 +113,8 @@ class Engine final : public RegisterMachine {
   uint64_t* take_spare_cbuf();                      // carry-word buffers are handed around like the register slots
   void adopt_cbuf(size_t r, uint64_t* fresh);       // r's pending carries are now in `fresh`; its old buffer becomes spare
   void back_ext(size_t dst, uint32_t a, long copy_to, long add_src);
+  // a whole product in one launch (plan token onelaunch): front, rows in `mode`, back with factor a and the extras of back_ext
+  void one_launch(size_t r, int mode, const uint64_t* y, const uint64_t* y2, uint64_t* img, uint32_t a, long copy_to, long add_src);
   void normalize(size_t r);          // apply deferred run carries
   void carry_fix_now(size_t r, int excess = -1);   // run carries into the digits right away (plans with runs of two digits cannot defer
                                                    // them); excess: bits of a carry word above the first digit's width (-1: a <= 15)
@@ -129,6 +131,7 @@ class Engine final : public RegisterMachine {
   hipStream_t stream_ = nullptr;
   size_t nregs_ = 0, reg_bytes_ = 0;
   size_t lanes_ = 1;         // residues per register (pl_.lanes)
+  OneLaunchShape one_{};     // lanes per work-group and threads per lane of the one-launch products (plan.hpp onelaunch_shape)
   unsigned char* regs_ = nullptr;            // (reg_count + 1) slots of lanes x 8n bytes; the extra one is the work buffer
   std::vector<unsigned char*> slot_;          // slot_[r]: storage of register r; slot_[reg_count]: work buffer (swappable)
   uint64_t* cbuf_ = nullptr;                  // reg_count + 4 buffers of lanes x runs() carry words

@@ -6,6 +6,7 @@
 //   k_back  : twiddle^-1 -> inverse column DFT (LDS) -> unweight -> base-2^width carry over runs of 2C
 //             digits -> digits(u32) + one carry word per run
 //   k_carry_fix: adds each run's carry word into the first digits of the next run (weak carry)
+//   k_onelaunch: the three sweeps of a small transform (n <= 8192) in one launch, a whole residue per work-group, work buffer in LDS
 // This replaces the reference's kernel chain forward64_0 / forward256 / sqr512 / backward256 /
 // backward64_0 / carry_weight_mul_p1 / carry_weight_p2 (include/marin/engine_gpu.h:1568-1630,
 // kernels/marin.cl:989-1075,1517-1528,1696-1728,2198-2216).  Butterfly algebra follows
@@ -262,7 +263,10 @@ __device__ __forceinline__ uint64_t fourstep_word(const DevPlan& pl, uint32_t po
 // ---------------------------------------------------------------------------------------------
 // body of the front sweep for tile T.  Offsets go onto the pointers one at a time (dg + i1 * C + c, not dg[i1 * C + c], here and in
 // back_body): a 32-bit sum may wrap, and the compiler then no longer merges the neighbouring accesses.
-__device__ __forceinline__ void front_body(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* Wout, uint32_t T,
+// WB: the work buffer's element type as the caller has it -- words of global memory (k_front) or pairs of the LDS array (k_onelaunch, which
+// hands over an offset of smem_raw itself: once inlined, the accesses are LDS accesses, not flat ones).  The same in middle_body and back_body.
+template <class WB>
+__device__ __forceinline__ void front_body(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, WB* Wout, uint32_t T,
                                            P2* X, uint32_t tid, uint32_t nthr) {
   const uint32_t C = pl.C, M1 = pl.M1, tile = M1 * C;
   const uint2* dg = reinterpret_cast<const uint2*>(digits) + size_t(T) * tile;
@@ -317,9 +321,10 @@ __global__ void __launch_bounds__(1024) k_front(DevPlan pl, const uint32_t* __re
 // middle: one work-group per row.  mode 0: square, 1: multiply by image Y, 2: forward only, 3: multiply by the sum of the images Y and Y2.
 // mode 4 (KEEP, k_middle_keep): mode 0 that also stores the forward transform of the operand to Wimg, as mode 2 would store it.
 // ---------------------------------------------------------------------------------------------
-template <bool KEEP = false>
-__device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* Win, const uint64_t* Yimg, const uint64_t* Yimg2, uint64_t* Wout, int mode, uint32_t row,
-                                            P2* X, uint32_t tid, uint32_t nthr, uint64_t* Wimg = nullptr) {
+// live (k_onelaunch: a lane beyond the last one, which only keeps its group's barriers company): false stores nothing to memory.
+template <bool KEEP = false, class WI, class WO>
+__device__ __forceinline__ void middle_body(const DevPlan& pl, const WI* Win, const uint64_t* Yimg, const uint64_t* Yimg2, WO* Wout, int mode, uint32_t row,
+                                            P2* X, uint32_t tid, uint32_t nthr, uint64_t* Wimg = nullptr, bool live = true) {
   const uint32_t M2 = pl.M2;
   const P2* in = reinterpret_cast<const P2*>(Win) + size_t(row) * M2;
   P2* out = reinterpret_cast<P2*>(Wout) + size_t(row) * M2;
@@ -334,13 +339,13 @@ __device__ __forceinline__ void middle_body(const DevPlan& pl, const uint64_t* W
     pre_lo = pl.TWlo[ex & ((1u << pl.twh) - 1)]; pre_hi = pl.TWhi[ex >> pl.twh];
   }
   lds_pow2_dft<false>(X, M2, pl.logM2, 1, 1, 0, pl.UT2, M2, 1, tid, nthr);
-  if (mode == 2) {
-    for (uint32_t e = tid; e < M2; e += nthr) out[e] = X[e];
+  if (mode == 2) {   // (Wout is the image here: memory)
+    if (live) for (uint32_t e = tid; e < M2; e += nthr) out[e] = X[e];
     return;
   }
   if constexpr (KEEP) {   // every thread stores the elements it squares next: no barrier between the two
     P2* img = reinterpret_cast<P2*>(Wimg) + size_t(row) * M2;
-    for (uint32_t e = tid; e < M2; e += nthr) img[e] = X[e];
+    if (live) for (uint32_t e = tid; e < M2; e += nthr) img[e] = X[e];
   }
   const P2* Y = reinterpret_cast<const P2*>(Yimg) + size_t(row) * M2;
   for (uint32_t e = tid; e < M2; e += nthr) {
@@ -412,9 +417,9 @@ __device__ __forceinline__ uint32_t adc_mul(uint64_t u, uint32_t a, uint32_t add
 __device__ __forceinline__ uint32_t xcd_tile(const DevPlan& pl, uint32_t b, uint32_t groups) {
   return (!(pl.tune & 1) && groups % 8 == 0) ? (b & 7) * (groups >> 3) + (b >> 3) : b;
 }
-template <bool EXT>
-__device__ __forceinline__ void back_body(const DevPlan& pl, const uint64_t* Win, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& ext, uint32_t T,
-                                          P2* X, uint32_t tid, uint32_t nthr) {
+template <bool EXT, class WB>
+__device__ __forceinline__ void back_body(const DevPlan& pl, const WB* Win, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& ext, uint32_t T,
+                                          P2* X, uint32_t tid, uint32_t nthr, bool live = true) {
   const uint32_t C = pl.C, M1 = pl.M1, tile = M1 * C;
   const P2* W = reinterpret_cast<const P2*>(Win);
 
@@ -458,9 +463,11 @@ __device__ __forceinline__ void back_body(const DevPlan& pl, const uint64_t* Win
         const uint64_t u = unweigh(pl, uw, b, sb, b ? x.b : x.a, width);
         out[b] = adc_mul(u, a, EXT ? av[b] : 0u, width, carry);
       }
+      if (!live) continue;   // (k_onelaunch, a lane beyond the last one: the chain ran, nothing leaves it)
       *(dg + i1 * C + c) = make_uint2(out[0], out[1]);
       if (EXT && ext.digits2) reinterpret_cast<uint2*>(ext.digits2)[size_t(T) * tile + size_t(i1) * C + c] = make_uint2(out[0], out[1]);
     }
+    if (!live) continue;
     *(cbuf + size_t(T) * M1 + i1) = carry;
     if (EXT && ext.digits2) ext.cbuf2[size_t(T) * M1 + i1] = carry;
   }
@@ -476,6 +483,85 @@ __global__ void __launch_bounds__(1024) k_back(DevPlan pl, const uint64_t* __res
   }
   back_body<EXT>(pl, lane_reg<LANES>(pl, Win), lane_reg<LANES>(pl, digits), lane_cbuf<LANES>(pl, cbuf), a, x, xcd_tile(pl, blockIdx.x, gridDim.x),
                  reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
+}
+
+// ---------------------------------------------------------------------------------------------
+// One launch for a whole product (plan token onelaunch, n <= 8192): front sweep, row sweep and back sweep of a lane in ONE work-group, with
+// the work buffer in LDS instead of memory.  At these sizes the three launches above are dependent launches of almost no arithmetic, and
+// a lane's column tile (8 pairs at p = 1277) leaves most of a wave idle.
+// A work-group holds K whole lanes with TL threads each (plan.hpp onelaunch_shape): the lane is blockIdx.x K + threadIdx.x / TL.  Per lane
+// LDS holds the work buffer (m pairs) and as much transform scratch.  A lane's threads split into teams that run the sweep bodies above
+// side by side, one tile (front, back) or one row a team; every team makes the same number of trips and the bodies' barrier counts depend
+// on the plan alone, so every thread of the group reaches every barrier.  The group's barriers separate the phases: all of a lane's digits
+// are read before the first is written, so dst may be src.
+// A tail group has lanes beyond the last one: they run on the last lane's inputs, reach every barrier and store nothing (live).
+// Registers, carry words and images are those of the three launches: digits and carries bit for bit (exact integers), image words as
+// field elements in the same order.
+// ---------------------------------------------------------------------------------------------
+// lane_reg / lane_cbuf for a lane that is not blockIdx.y.  The pointers come out of the argument block as plain pointers; they are device
+// memory, and saying so keeps the accesses through them global ones instead of flat ones.
+template <class T> __device__ __forceinline__ T* lane_at(T* p, uint32_t lane, uint64_t bytes) {
+  typedef __attribute__((address_space(1))) unsigned char GlobalByte;
+  return p ? (T*)((GlobalByte*)(p) + lane * bytes) : nullptr;
+}
+// The kernel's one argument: plan, operands and the back sweep's extras.  The kernel reads it through args_again(), the argument block
+// behind a pointer the compiler does not see through, once per phase: each phase then loads the members it uses when it starts.  Read from
+// the argument itself, the members of all three phases are loaded at the kernel's entry and stay in scalar registers to its end, more
+// than a wave has (over a hundred of them spilled).  The argument block is constant memory, so these are scalar loads.
+struct OneLaunchPack { DevPlan pl; OneLaunchArgs oa; BackExt x; };
+__device__ __forceinline__ const OneLaunchPack& args_again() {
+  auto p = __builtin_amdgcn_kernarg_segment_ptr();   // the only argument: offset 0
+  asm volatile("" : "+s"(p));
+  return *(const OneLaunchPack*)p;
+}
+template <bool EXT>
+__global__ void __launch_bounds__(1024) k_onelaunch(OneLaunchPack) {
+  uint32_t lane, cteam, cteams, ctid, ct, rteam, rteams, rtid, rt, NT, M1, mode;
+  uint64_t rb, cb;
+  bool live;
+  P2 *W, *Xc, *Xr;
+  {
+    const OneLaunchPack& g = args_again();
+    const DevPlan& pl = g.pl;
+    const uint32_t TL = g.oa.TL, gl = threadIdx.x / TL, lt = threadIdx.x - gl * TL;   // lane of the group, thread of the lane
+    live = blockIdx.x * g.oa.K + gl < pl.lanes;
+    lane = live ? blockIdx.x * g.oa.K + gl : pl.lanes - 1;
+    rb = uint64_t(pl.n) * 8; cb = uint64_t(pl.M1) * (pl.M2 >> pl.logC) * 8;   // bytes of a lane's register, of its carry words
+    W = reinterpret_cast<P2*>(smem_raw) + size_t(gl) * 2 * pl.m;   // the lane's work buffer; its transform scratch follows
+    M1 = pl.M1; NT = pl.M2 >> pl.logC; mode = uint32_t(g.oa.mode);
+    // column teams: TL = r5 2^j threads over NT = 2^i tiles; row teams: over M1 = r5 L1 rows.  Each count divides both.
+    cteams = min(NT, TL / pl.r5); ct = TL / cteams; cteam = lt / ct; ctid = lt - cteam * ct;
+    rteams = min(M1, TL); rt = TL / rteams; rteam = lt / rt; rtid = lt - rteam * rt;
+    Xc = W + pl.m + size_t(cteam) * (M1 << pl.logC);
+    Xr = W + pl.m + size_t(rteam) * pl.M2;
+  }
+
+  for (uint32_t T = cteam; T < NT; T += cteams) {
+    const OneLaunchPack& g = args_again();
+    front_body(g.pl, lane_at(g.oa.src, lane, rb), lane_at(g.oa.src_cbuf, lane, cb), W, T, Xc, ctid, ct);
+    __syncthreads();
+  }
+
+  for (uint32_t row = rteam; row < M1; row += rteams) {
+    const OneLaunchPack& g = args_again();
+    uint64_t* img = lane_at(g.oa.img, lane, rb);
+    if (mode == 2) middle_body(g.pl, W, nullptr, nullptr, img, 2, row, Xr, rtid, rt, nullptr, live);
+    else if (mode == 4) middle_body<true>(g.pl, W, nullptr, nullptr, W, 0, row, Xr, rtid, rt, img, live);
+    else middle_body(g.pl, W, lane_at(g.oa.y, lane, rb), lane_at(g.oa.y2, lane, rb), W, int(mode), row, Xr, rtid, rt);
+    __syncthreads();
+  }
+  if (mode == 2) return;
+
+  for (uint32_t T = cteam; T < NT; T += cteams) {
+    const OneLaunchPack& g = args_again();
+    BackExt x;
+    if (EXT) {
+      x.digits2 = lane_at(g.x.digits2, lane, rb); x.cbuf2 = lane_at(g.x.cbuf2, lane, cb);
+      x.add_digits = lane_at(g.x.add_digits, lane, rb); x.add_cbuf = lane_at(g.x.add_cbuf, lane, cb);
+    }
+    back_body<EXT>(g.pl, W, lane_at(g.oa.dst, lane, rb), lane_at(g.oa.dst_cbuf, lane, cb), g.oa.a, x, T, Xc, ctid, ct, live);
+    __syncthreads();   // the next trip refills the scratch that the carry chains of this one read
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -754,6 +840,14 @@ hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, u
 hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s) {
   return launch_back_of<true>(pl, W, digits, cbuf, a, x, s);
 }
+// one-launch products: `groups` work-groups of K lanes x TL threads, per lane 2 m pairs of LDS (plan.hpp onelaunch_shape)
+constexpr size_t kOneLaunchMaxLds = 128 * 1024;   // n = 8192: 4096 pairs of work buffer and as much scratch
+hipError_t launch_onelaunch(const DevPlan& pl, const OneLaunchArgs& oa, const BackExt& x, hipStream_t s) {
+  const size_t lds = size_t(oa.K) * pl.m * 32;
+  if (oa.mode < 0 || oa.mode > 4 || !oa.TL || !oa.K || oa.K * oa.TL > 1024 || lds > kOneLaunchMaxLds || size_t(oa.groups) * oa.K < pl.lanes) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(x.any() ? k_onelaunch<true> : k_onelaunch<false>, dim3(oa.groups), dim3(oa.K * oa.TL), lds, s, OneLaunchPack{pl, oa, x});
+  return hipGetLastError();
+}
 // the split column sweeps (M1 = 5 L1 beyond LDS): U is a second work buffer of 8 n bytes
 static uint32_t split_log_cb(const DevPlan& pl) { uint32_t l = 0; while ((size_t(pl.L1) << (l + 1)) * 16 <= size_t(128) * 1024 && (2u << l) <= pl.M2 && l < 2) ++l; return l; }
 hipError_t launch_front_split(const DevPlan& pl, const uint32_t* digits, uint64_t* U, uint64_t* W, hipStream_t s) {
@@ -812,9 +906,14 @@ static hipError_t configure_kernels_of(size_t lds_front, size_t lds_mid) {
     }
   return hipSuccess;
 }
-hipError_t configure_kernels(size_t lds_front, size_t lds_mid, uint32_t lanes) {
+// The one-launch entry points get the LDS of their largest size whatever the engine's own: the value is the same for every engine, so
+// engines of different sizes in one process never lower it for one another.
+hipError_t configure_kernels(size_t lds_front, size_t lds_mid, uint32_t lanes, bool onelaunch) {
   hipError_t e = configure_kernels_of<false>(lds_front, lds_mid);
-  return (e != hipSuccess || lanes <= 1) ? e : configure_kernels_of<true>(lds_front, lds_mid);
+  if (e == hipSuccess && lanes > 1) e = configure_kernels_of<true>(lds_front, lds_mid);
+  if (e == hipSuccess && onelaunch) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_onelaunch<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kOneLaunchMaxLds));
+  if (e == hipSuccess && onelaunch) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_onelaunch<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kOneLaunchMaxLds));
+  return e;
 }
 
 }  // namespace mi355

@@ -32,6 +32,7 @@ struct DevPlan {
   uint32_t probe_mod;     // blockIdx.x is taken modulo this (launches of several rounds over the same tiles)
 #endif
   uint32_t tune;   // MI355_TUNE (A/B runs), read by the kernels only: bit 0 plain (not XCD-contiguous) tile order in the back sweeps; bit 5 the other tile order in the front sweeps
+  uint32_t onelaunch;   // plan token onelaunch: products run as one launch of k_onelaunch (kernels.hip).  Last, so that no other member moves.
 };
 
 #if defined(__HIPCC__)
@@ -92,11 +93,25 @@ typedef hipError_t (*RowsFn)(const DevPlan& pl, const uint64_t* Win, const uint6
 struct ColSweeps { FrontFn front; BackFn back; BackExtFn back_ext; FourStepFn build_fourstep; };
 
 // generic set (kernels.hip): tiles in LDS, any shape, pl.lanes lanes as grid.y (the run-wise launchers above too)
-hipError_t configure_kernels(size_t lds_front, size_t lds_mid, uint32_t lanes);
+// (onelaunch: the entry points of the one-launch products too, to the LDS of their largest size)
+hipError_t configure_kernels(size_t lds_front, size_t lds_mid, uint32_t lanes, bool onelaunch);
 hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s);
 hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
 hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s);
 hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
+// One-launch products (plan token onelaunch, n <= 8192; kernels.hip k_onelaunch): front sweep, row sweep and back sweep of a lane in one
+// work-group, the work buffer in LDS.  A group holds K whole lanes with TL threads each (plan.hpp onelaunch_shape), `groups` of them.
+//   src (+ src_cbuf: its pending run carries, nullable) -> front; rows in `mode` (the modes of RowsFn above: y, y2 read in modes 1 and 3, img
+//   written in modes 2 and 4); unless mode 2: back into dst, dst_cbuf with factor a and the extras x.  dst may be src: a lane's digits are all
+//   read before the first is written.  dst_cbuf must not be src_cbuf or x.add_cbuf.
+struct OneLaunchArgs {
+  const uint32_t* src = nullptr; const uint64_t* src_cbuf = nullptr;
+  const uint64_t* y = nullptr; const uint64_t* y2 = nullptr; uint64_t* img = nullptr;
+  uint32_t* dst = nullptr; uint64_t* dst_cbuf = nullptr;
+  uint32_t a = 1; int mode = 0;
+  uint32_t TL = 0, K = 0, groups = 0;
+};
+hipError_t launch_onelaunch(const DevPlan& pl, const OneLaunchArgs& oa, const BackExt& x, hipStream_t s);
 // columns of 5 L1 pairs that do not fit LDS (n = 5 * 2^26): the radix-5 stage through a second work buffer U (8 n bytes), C = 1
 hipError_t configure_split(const DevPlan& pl);
 hipError_t launch_front_split(const DevPlan& pl, const uint32_t* digits, uint64_t* U, uint64_t* W, hipStream_t s);

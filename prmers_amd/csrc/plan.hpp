@@ -56,6 +56,7 @@ struct Plan {
   uint32_t C = 1;           // adjacent columns per front/back tile (runs of 2C digits)
   bool split5 = false;      // columns of 5 L1 pairs beyond LDS: the radix-5 stage runs through memory (kernels.hip k_front_split_*), C = 1
   uint32_t lanes = 1;       // independent residues per register (plan token lanes=B): every operation acts on all of them in one launch
+  bool onelaunch = false;   // plan token onelaunch (n <= 8192): a product is one launch, front, row and back sweep of a lane in one work-group (kernels.hip k_onelaunch)
   uint32_t q = 0, t = 0;    // p = q*n + t
   uint32_t twh = 0;         // omega_m^e = TWlo[e & (2^twh-1)] * TWhi[e >> twh]
   uint32_t a_fast = 1;      // largest factor the back sweeps multiply in themselves (fused_factor_ok); above it: factor 1 + k_scale
@@ -97,7 +98,7 @@ struct Plan {
   std::string describe() const {
     char buf[160];
     std::snprintf(buf, sizeof buf, "marin-hip:n=%zu:m1=%u:m2=%u:c=%u%s", n, M1, M2, C, split5 ? ":split5" : "");
-    return lanes > 1 ? std::string(buf) + ":lanes=" + std::to_string(lanes) : std::string(buf);
+    return std::string(buf) + (lanes > 1 ? ":lanes=" + std::to_string(lanes) : std::string()) + (onelaunch ? ":onelaunch" : "");
   }
 };
 
@@ -221,7 +222,26 @@ inline uint32_t fused_factor_limit(uint32_t q, size_t n, uint32_t C) {
 
 constexpr uint32_t kMaxLanes = 65535;   // the lane is blockIdx.y
 
-// spec: "" (auto) or comma/colon separated "m2=<pow2>", "c=<pow2>", "lanes=<1..65535>"
+// One-launch products (plan token onelaunch; kernels.hip k_onelaunch): a work-group holds K whole lanes with TL threads each, and per lane
+// the work buffer and as much transform scratch, m pairs of 16 bytes each, in LDS.
+//   TL: one thread per pair, up to 1024 threads -- 640 where the transform has a radix-5 stage: TL keeps the factor 5 of m = 5 2^k, so that
+//       the lane's threads split evenly into teams over its M1 = 5 L1 rows as well as over its M2 / C tiles;
+//   K:  the lanes that make a group of about 256 threads where a lane has fewer, but no more than the lane count rounded up to a power of two.
+// 32 m K bytes of LDS: 128 KiB at n = 8192 (K = 1), at most 8 KiB wherever K > 1.
+constexpr size_t kOneLaunchMaxN = 8192;
+struct OneLaunchShape { uint32_t TL, K, groups; size_t lds; };
+inline OneLaunchShape onelaunch_shape(size_t m, uint32_t r5, uint32_t lanes) {
+  OneLaunchShape s;
+  s.TL = uint32_t(std::min<size_t>(m, r5 == 5 ? 640 : 1024));
+  uint32_t cap = 1;
+  while (cap < lanes) cap <<= 1;
+  s.K = std::min(std::max(1u, 256u / s.TL), cap);
+  s.groups = (lanes + s.K - 1) / s.K;
+  s.lds = size_t(s.K) * m * 32;
+  return s;
+}
+
+// spec: "" (auto) or comma/colon separated "m2=<pow2>", "c=<pow2>", "lanes=<1..65535>", "onelaunch"
 inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables = true) {
   if (p < 3) throw std::runtime_error("exponent must be >= 3");
   Plan pl;
@@ -249,11 +269,15 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
           throw std::runtime_error("bad lanes in plan spec: '" + tok + "' (lanes=1 .. lanes=" + std::to_string(kMaxLanes) + ")");
         pl.lanes = uint32_t(std::atol(v.c_str()));
       }
+      else if (tok == "onelaunch") pl.onelaunch = true;
       else if (!tok.empty() && tok != "marin-hip" && tok.rfind("n=", 0) != 0 && tok.rfind("m1=", 0) != 0)
         throw std::runtime_error("unknown plan token '" + tok + "'");
       i = e + 1;
     }
   }
+
+  if (pl.onelaunch && pl.n > kOneLaunchMaxN)
+    throw std::runtime_error("onelaunch: a residue and its work buffer must fit the LDS of one CU, n <= " + std::to_string(kOneLaunchMaxN) + " (p <= 204799); n = " + std::to_string(pl.n) + " here");
 
   // rows vs columns: balance the work-group counts of the row sweep (M1 groups) and the column
   // sweeps (M2/C groups), keep a row <= 4096 pairs (64 KiB of LDS) and a column <= 1024 (x r5)
@@ -303,6 +327,8 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
     if ((C & (C - 1)) != 0 || C > pl.M2 || size_t(pl.M1) * C > 10240) throw std::runtime_error("bad c in plan spec");
   }
   pl.C = C;
+  if (pl.onelaunch && pl.split5) throw std::runtime_error("onelaunch: not with the split column sweeps (split5)");
+  if (pl.onelaunch && pl.C < 2) throw std::runtime_error("onelaunch: not with runs of two digits (c=1), whose carries go in at once through passes of their own");
   pl.lds_front = pl.split5 ? 0 : size_t(pl.M1) * pl.C * 16;
   pl.lds_mid = size_t(pl.M2) * 16;
   pl.q = uint32_t(p / pl.n);
@@ -345,7 +371,7 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
   const uint64_t om1 = gf::pow(om, pl.M2), om2 = gf::pow(om, pl.M1);
   pl.UT1.resize(pl.M1); pl.UT1[0] = 1; for (uint32_t i = 1; i < pl.M1; ++i) pl.UT1[i] = gf::mul(pl.UT1[i - 1], om1);
   pl.UT2.resize(pl.M2); pl.UT2[0] = 1; for (uint32_t i = 1; i < pl.M2; ++i) pl.UT2[i] = gf::mul(pl.UT2[i - 1], om2);
-  const KernelChoice kc = pl.lanes > 1 ? KernelChoice{} : served_kernels(pl.r5, pl.M1, pl.M2, pl.C, pl.split5);   // (choose_kernels)
+  const KernelChoice kc = (pl.lanes > 1 || pl.onelaunch) ? KernelChoice{} : served_kernels(pl.r5, pl.M1, pl.M2, pl.C, pl.split5);   // (choose_kernels)
   if (kc.rows == RowKernels::kRadix8 || kc.rows == RowKernels::kRadix8Wide) {   // rows of 8192 = one radix-2 level over two 4096-point transforms
     const uint32_t st = pl.M2 / 4096;       // omega_4096 = omega_M2^st
     pl.S2r.resize(4096); pl.S2ri.resize(4096);
@@ -409,6 +435,7 @@ inline Plan make_plan(uint32_t p, const char* spec = nullptr, bool build_tables 
 // "v2rows" / "v2cols" keep only the register-resident rows / columns, anything else takes the generic ones (the split sweeps stay).
 inline KernelChoice choose_kernels(const Plan& pl, const char* mi355_kernels) {
   if (pl.lanes > 1) return KernelChoice{};   // lane engines run the generic set, whatever serves the shape (the only one that reads DevPlan.lanes)
+  if (pl.onelaunch) return KernelChoice{};   // one-launch products are built from the generic bodies and write their registers and images
   KernelChoice k = served_kernels(pl.r5, pl.M1, pl.M2, pl.C, pl.split5);
   const std::string sel = mi355_kernels ? mi355_kernels : "v2";
   if (sel != "v2" && sel != "v2rows") k.rows = RowKernels::kGeneric;

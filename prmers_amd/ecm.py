@@ -1,6 +1,6 @@
 """ECM factoring of a Mersenne number 2^p - 1 on the engine: Montgomery curves, stages 1 and 2 (the reference: src/modes/RunEcm.cpp).
 
-    python -m prmers_amd.ecm P B1 [B2] [--sigma S] [--curves N] [--lanes B] [--D 30|210|2310] [--plan SPEC] [--device N]
+    python -m prmers_amd.ecm P B1 [B2] [--sigma S] [--curves N] [--lanes B] [--D 30|210|2310] [--plan SPEC] [--onelaunch] [--device N]
 
 Curve:    Suyama's parametrisation from sigma: u = sigma^2 - 5, v = 4 sigma, the point (u^3 : v^3) on B y^2 = x^3 + A x^2 + x with
           a24 = (A + 2) / 4 = (v - u)^3 (3 u + v) / (16 u^3 v).  The start is taken affine, x0 = u^3 / v^3 and Z = 1: one modular inversion
@@ -371,16 +371,19 @@ def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None):
     return _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, True)
 
 
-def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0, lanes=1):
+def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0, lanes=1, onelaunch=False):
     """`curves` curves of run() on a fresh prmers_amd.Engine sized for the chosen D, until one finds a factor.  sigma: the first curve's
     (None: drawn like the others, from random.Random(seed)).  -> the result of the last curve run, with "sigmas": every sigma used.
     lanes = B > 1: the curves run B at a time through run_lanes() on one engine with B lanes (whole batches: `curves` rounded up to a
     multiple of B), sigmas drawn from the same generator in the same order, until a batch in which some lane finds a factor.  -> the
     result of that batch's first curve with a factor (of the last curve run when there is none), "factors": those of all its lanes,
-    "sigmas": every sigma of every batch run, "batch": the last batch's results, one per lane."""
+    "sigmas": every sigma of every batch run, "batch": the last batch's results, one per lane.
+    onelaunch: the engine is created with the plan token of that name (every product one launch; p <= 204799)."""
     from .engine import Engine, resolve_plan
     if lanes < 1:
         raise ValueError("lanes must be at least 1")
+    if onelaunch:
+        plan = (plan + "," if plan else "") + "onelaunch"
     if b2 > b1 and D is None:
         n = int(resolve_plan(p, plan).split("n=")[1].split(":")[0])
         D = choose_D(n, b1, b2, budget // lanes)
@@ -426,8 +429,9 @@ def main(argv=None):
     ap.add_argument("--plan", default=None)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--lanes", type=int, default=1, help="curves per batch: an engine with this many lanes runs them in one launch sequence")
+    ap.add_argument("--onelaunch", action="store_true", help="plan token onelaunch: every product of the engine is one launch (p <= 204799)")
     a = ap.parse_args(argv)
-    res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed, a.lanes)
+    res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed, a.lanes, a.onelaunch)
     print(json.dumps(res))
     return 0 if res["factors"] else 1
 

@@ -164,12 +164,15 @@ def u32_arg(name, v):
 class Engine:
     """engine::create_gpu(p, reg_count, device, verbose) on an MI355X (include/marin/engine.h:301)."""
 
-    def __init__(self, p, reg_count=8, device=0, verbose=False, plan=None, lanes=1):
+    def __init__(self, p, reg_count=8, device=0, verbose=False, plan=None, lanes=1, onelaunch=False):
         """lanes = B > 1: B independent residues per register, every operation on all of them in one launch (include/mi355_lanes.h);
-        reads then take lane=l, writes lane=l or None for every lane."""
+        reads then take lane=l, writes lane=l or None for every lane.
+        onelaunch: the plan token of that name -- a product is one launch, the whole lane in one work-group (p <= 204799)."""
         self.L = load_library()
         if lanes != 1:
             plan = (plan + "," if plan else "") + "lanes=%d" % operator.index(lanes)
+        if onelaunch:
+            plan = (plan + "," if plan else "") + "onelaunch"
         self.h = self.L.mi355_engine_create(p, reg_count, device, int(verbose), plan.encode() if plan else None, None)
         if not self.h:
             raise EngineError(self.L.mi355_engine_last_error().decode())
