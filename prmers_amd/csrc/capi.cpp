@@ -2,6 +2,7 @@
 // reports through last_error, as the reference's plugin does (third_party/aevum/src/EngineApi.cpp:447-517).
 #include "../../include/mi355_engine.h"
 #include "../../include/mi355_lanes.h"
+#include "../../include/mi355_batch.h"
 
 #include <cctype>
 #include <cstring>
@@ -231,6 +232,12 @@ int mi355_lanes_get_words(mi355_engine_handle h, size_t lane, size_t src, uint32
 }
 int mi355_lanes_res64(mi355_engine_handle h, size_t lane, size_t src, uint64_t* out) {
   return guarded([&] { if (!out) throw std::runtime_error("res64: null output"); *out = m(h)->res64_lane(lane, src); });
+}
+// ---- include/mi355_batch.h ----
+int mi355_batch_begin(mi355_engine_handle h) { return guarded([&] { m(h)->batch_begin(); }); }
+int mi355_batch_end(mi355_engine_handle h) { return guarded([&] { m(h)->batch_end(); }); }
+int mi355_batch_stats(mi355_engine_handle h, uint64_t out[4]) {
+  return guarded([&] { if (!out) throw std::runtime_error("batch_stats: null output"); m(h)->batch_stats(out); });
 }
 size_t mi355_engine_algorithmic_bytes(mi355_engine_handle h) { size_t r = 0; guarded([&] { r = m(h)->algorithmic_bytes(); }); return r; }
 

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 
 #include "host_digits.hpp"
 
@@ -182,18 +183,23 @@ Engine::~Engine() {
   if (f0_) (void)hipFree(f0_);
   if (split_) (void)hipFree(split_);
   if (canon_) (void)hipFree(canon_);
+  for (int h = 0; h < 2; ++h) {   // (what a batch still had queued is dropped: nothing of it was launched)
+    if (batch_read_[h]) (void)hipEventDestroy(batch_read_[h]);
+    if (batch_stage_[h]) (void)hipHostFree(batch_stage_[h]);
+  }
+  if (batch_dev_) (void)hipFree(batch_dev_);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
 void Engine::sync() {
   HIPCHK(hipSetDevice(device_));
-  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipStreamSynchronize(stream()));
 }
 
 void Engine::normalize(size_t r) {
   if (kind_[r] != kDigits) return;
   if (pending_carry_[r]) {
-    HIPCHK(launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
+    HIPCHK(launch_carry_fix(dp_, digits(r), cbuf(r), stream()));
     pending_carry_[r] = 0;
   }
 }
@@ -203,14 +209,14 @@ void Engine::normalize(size_t r) {
 // run's second digit, log2(n) - 2 (+ log2 a) bits above its width -- too much for the next squaring once that exceeds w.
 // Local carry passes (canon.hip k_relax) take w bits off per pass; as many as it takes to get below the width follow.
 void Engine::carry_fix_now(size_t r, int excess) {
-  HIPCHK(launch_carry_fix(dp_, digits(r), cbuf(r), stream_));
+  HIPCHK(launch_carry_fix(dp_, digits(r), cbuf(r), stream()));
   pending_carry_[r] = 0;
   if (pl_.C >= 2) return;
   if (excess < 0) excess = ilog2(pl_.n) + 1 + 4 - 2;   // log2(n) rounded up, factor a up to 15 (plan.hpp a_fast)
   const int w = int(pl_.q);                 // the narrower digit width
   while (excess > w - 2) {
     for (size_t l = 0; l < lanes_; ++l)   // (lane by lane: runs of two digits are not the ladder's plans)
-      HIPCHK(canon_relax(dp_, pl_.p, digits(r, l), digits(nregs_, l), stream_));
+      HIPCHK(canon_relax(dp_, pl_.p, digits(r, l), digits(nregs_, l), stream()));
     swap_with_work(r);
     excess -= w;
   }
@@ -219,23 +225,23 @@ void Engine::carry_fix_now(size_t r, int excess) {
 // digits(r) (+ its pending run carries) -> work(); digits(r) stay as they are.  (Runs of two digits never leave carries pending:
 // every operation that writes run carries on a plan with C < 2 takes them in at once, carry_fix_now.)
 void Engine::run_front(size_t r) {
-  if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_front_split(dp_, digits(r), split_, work(), stream_));
-  else HIPCHK(cols_.front(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, work(), stream_));
+  if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_front_split(dp_, digits(r), split_, work(), stream()));
+  else HIPCHK(cols_.front(dp_, digits(r), pending_carry_[r] ? cbuf(r) : nullptr, work(), stream()));
 }
 
 void Engine::run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, const uint64_t* y2, uint64_t* img) {
-  HIPCHK(rows_(dp_, in, y, y2, img, out, mode, stream_));
+  HIPCHK(rows_(dp_, in, y, y2, img, out, mode, stream()));
 }
 
 // work() -> digits(r) + run carries in cbuf(r): runs of 2C >= 4 digits leave them to the next sweep, which folds them in, runs of two
 // digits take them at once.  ev (nullable): two events recorded around that carry fix (time_square_mul)
 void Engine::run_back(size_t r, uint32_t a, hipEvent_t* ev) {
-  if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_back_split(dp_, work(), split_, digits(r), cbuf(r), a, stream_));
-  else HIPCHK(cols_.back(dp_, work(), digits(r), cbuf(r), a, stream_));
-  if (ev) HIPCHK(hipEventRecord(ev[0], stream_));
+  if (kc_.cols == ColKernels::kSplit) HIPCHK(launch_back_split(dp_, work(), split_, digits(r), cbuf(r), a, stream()));
+  else HIPCHK(cols_.back(dp_, work(), digits(r), cbuf(r), a, stream()));
+  if (ev) HIPCHK(hipEventRecord(ev[0], stream()));
   if (pl_.C >= 2) pending_carry_[r] = 1;
   else carry_fix_now(r);
-  if (ev) HIPCHK(hipEventRecord(ev[1], stream_));
+  if (ev) HIPCHK(hipEventRecord(ev[1], stream()));
 }
 
 // One-launch products (plan token onelaunch; kernels.hip k_onelaunch): front sweep on digits(r) (+ its pending run carries), the row sweep
@@ -249,12 +255,17 @@ void Engine::one_launch(size_t r, int mode, const uint64_t* y, const uint64_t* y
   oa.y = y; oa.y2 = y2; oa.img = img; oa.a = a; oa.mode = mode;
   oa.TL = one_.TL; oa.K = one_.K; oa.groups = one_.groups;
   BackExt x;
-  if (mode == 2) { HIPCHK(launch_onelaunch(dp_, oa, x, stream_)); return; }
+  if (mode == 2) {
+    if (batching_) { BatchOp& op = batch_slot(); op.kind = BatchOp::kProduct; op.oa = oa; }
+    else HIPCHK(launch_onelaunch(dp_, oa, x, stream()));
+    return;
+  }
   if (copy_to >= 0 && size_t(copy_to) != r) { x.digits2 = digits(size_t(copy_to)); x.cbuf2 = cbuf(size_t(copy_to)); }
   if (add_src >= 0) { x.add_digits = digits(size_t(add_src)); x.add_cbuf = pending_carry_[size_t(add_src)] ? cbuf(size_t(add_src)) : nullptr; }
   uint64_t* fresh = take_spare_cbuf();
   oa.dst = digits(r); oa.dst_cbuf = fresh;
-  HIPCHK(launch_onelaunch(dp_, oa, x, stream_));
+  if (batching_) { BatchOp& op = batch_slot(); op.kind = BatchOp::kProduct; op.oa = oa; op.x = x; }   // the pointers as they are resolved now
+  else HIPCHK(launch_onelaunch(dp_, oa, x, stream()));
   adopt_cbuf(r, fresh);
   kind_[r] = kDigits; pending_carry_[r] = 1;
   if (x.digits2) { kind_[size_t(copy_to)] = kDigits; pending_carry_[size_t(copy_to)] = 1; }
@@ -265,11 +276,11 @@ void Engine::one_launch(size_t r, int mode, const uint64_t* y, const uint64_t* y
 void Engine::write_values(size_t dst, const std::vector<uint32_t>& natural) {
   // natural order goes up as it is; the tile-major order is made on the device (canon.hip k_scatter)
   HIPCHK(hipSetDevice(device_));
-  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipStreamSynchronize(stream()));
   uint32_t* nat = reinterpret_cast<uint32_t*>(work());
   HIPCHK(hipMemcpy(nat, natural.data(), pl_.n * 4, hipMemcpyHostToDevice));
-  for (size_t l = 0; l < lanes_; ++l) HIPCHK(canon_scatter(dp_, pl_.p, nat, digits(dst, l), stream_));   // every lane
-  HIPCHK(hipStreamSynchronize(stream_));
+  for (size_t l = 0; l < lanes_; ++l) HIPCHK(canon_scatter(dp_, pl_.p, nat, digits(dst, l), stream()));   // every lane
+  HIPCHK(hipStreamSynchronize(stream()));
   kind_[dst] = kDigits;
   pending_carry_[dst] = 0;
 }
@@ -281,20 +292,20 @@ uint32_t* Engine::canon_digits(size_t r, int slot, size_t lane) {
   const size_t sw = canon_scratch_bytes<uint32_t>(cg_) / 4;
   if (!canon_) {
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&canon_), (sw + 2 * pl_.n) * 4));
-    HIPCHK(hipMemsetAsync(canon_flags<uint32_t>(cg_, canon_), 0, 16 * 4, stream_));
+    HIPCHK(hipMemsetAsync(canon_flags<uint32_t>(cg_, canon_), 0, 16 * 4, stream()));
   }
   normalize(r);
   uint32_t* out = canon_ + sw + size_t(slot) * pl_.n;
-  HIPCHK(canon_launch(cg_, digits(r, lane), out, canon_, stream_));
+  HIPCHK(canon_launch(cg_, digits(r, lane), out, canon_, stream()));
   return out;
 }
 
 // flags: [0] all ones, [1] chain too wide (fall back), [2] compare differs; clears the sticky ones for the next use
 bool Engine::canon_flags_ok(uint32_t (&flags)[4]) {
   uint32_t* df = canon_flags<uint32_t>(cg_, canon_);
-  HIPCHK(hipMemcpyAsync(flags, df, 16, hipMemcpyDeviceToHost, stream_));
-  HIPCHK(hipMemsetAsync(df, 0, 16 * 4, stream_));
-  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipMemcpyAsync(flags, df, 16, hipMemcpyDeviceToHost, stream()));
+  HIPCHK(hipMemsetAsync(df, 0, 16 * 4, stream()));
+  HIPCHK(hipStreamSynchronize(stream()));
   return flags[1] == 0;
 }
 
@@ -303,7 +314,7 @@ void Engine::read_values(size_t src, std::vector<uint64_t>& v) {
   uint32_t* d = canon_digits(src, 0);
   uint32_t flags[4];
   stage_.resize(pl_.n);
-  HIPCHK(hipMemcpyAsync(stage_.data(), d, pl_.n * 4, hipMemcpyDeviceToHost, stream_));
+  HIPCHK(hipMemcpyAsync(stage_.data(), d, pl_.n * 4, hipMemcpyDeviceToHost, stream()));
   if (!canon_flags_ok(flags)) { read_values_host(src, v); return; }
   v.resize(pl_.n);
   if (flags[0]) {   // 2^p - 1: the reference's get() leaves the digits all ones (engine.h:188-196 maps them to 0 later)
@@ -318,7 +329,7 @@ void Engine::read_values_host(size_t src, std::vector<uint64_t>& v, size_t lane)
   stage_.resize(pl_.n);
   HIPCHK(hipSetDevice(device_));
   normalize(src);
-  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipStreamSynchronize(stream()));
   HIPCHK(hipMemcpy(stage_.data(), digits(src, lane), pl_.n * 4, hipMemcpyDeviceToHost));
   v.resize(pl_.n);
   const size_t M2 = pl_.M2, C = pl_.C, M1 = pl_.M1;
@@ -337,8 +348,8 @@ void Engine::set_u32(size_t dst, uint32_t value) {
   // spread the constant over the first digits (the reference stores it whole in digit 0,
   // engine_gpu.h:1444-1449; same value, but never an over-wide digit); every lane gets it
   for (size_t l = 0; l < lanes_; ++l) {
-    HIPCHK(hipMemsetAsync(digits(dst, l), 0, pl_.n * 4, stream_));
-    if (value) HIPCHK(canon_set_small(dp_, pl_.p, digits(dst, l), value, stream_));
+    HIPCHK(hipMemsetAsync(digits(dst, l), 0, pl_.n * 4, stream()));
+    if (value) HIPCHK(canon_set_small(dp_, pl_.p, digits(dst, l), value, stream()));
   }
   kind_[dst] = kDigits;
   pending_carry_[dst] = 0;
@@ -373,7 +384,7 @@ uint64_t Engine::res64_of(size_t src, size_t lane) {
     uint32_t* d = canon_digits(src, 0, lane);
     have = std::min<size_t>(pl_.n, 16);
     uint32_t head[16], flags[4];
-    HIPCHK(hipMemcpyAsync(head, d, have * 4, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(head, d, have * 4, hipMemcpyDeviceToHost, stream()));
     if (!canon_flags_ok(flags)) { read_values_host(src, v, lane); have = pl_.n; }
     else { v.resize(have); for (size_t k = 0; k < have; ++k) v[k] = flags[0] ? host_digits::ones(width_[k]) : head[k]; }
   }
@@ -390,8 +401,8 @@ void Engine::words_of(size_t src, size_t lane, uint32_t* w, size_t count) {
   if (!host_carry_) {
     uint32_t* d = canon_digits(src, 0, lane);
     uint32_t* dw = canon_;   // the pipeline's first work array (n words >= word_count(): widths are below 32) is free once the digits are out
-    HIPCHK(canon_pack_words(cg_, d, dw, stream_));
-    HIPCHK(hipMemcpyAsync(w, dw, count * 4, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(canon_pack_words(cg_, d, dw, stream()));
+    HIPCHK(hipMemcpyAsync(w, dw, count * 4, hipMemcpyDeviceToHost, stream()));
     uint32_t flags[4];
     if (canon_flags_ok(flags)) return;
   }
@@ -419,7 +430,7 @@ void Engine::set_words_lane(size_t lane, size_t dst, const uint32_t* w, size_t c
     throw std::runtime_error("set_words: the register holds a multiplicand image, and the kind is the register's, not the lane's (write a value to every lane first)");
   if (pending_carry_[dst]) {
     HIPCHK(hipSetDevice(device_));
-    HIPCHK(hipMemsetAsync(cbuf(dst) + lane * pl_.runs(), 0, pl_.runs() * 8, stream_));
+    HIPCHK(hipMemsetAsync(cbuf(dst) + lane * pl_.runs(), 0, pl_.runs() * 8, stream()));
   }
   put_words(dst, w, count, lane, lane + 1);
 }
@@ -437,19 +448,19 @@ void Engine::put_words(size_t dst, const uint32_t* w, size_t count, size_t lane0
   if (!host_carry_) {
     // the words go up as they are and are cut into digits on the device (canon.hip k_unpack_words), straight into tile-major order
     uint32_t* dw = reinterpret_cast<uint32_t*>(work());
-    HIPCHK(hipMemcpyAsync(dw, w, count * 4, hipMemcpyHostToDevice, stream_));
-    for (size_t l = lane0; l < lane1; ++l) HIPCHK(canon_unpack_words(cg_, dw, digits(dst, l), stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
+    HIPCHK(hipMemcpyAsync(dw, w, count * 4, hipMemcpyHostToDevice, stream()));
+    for (size_t l = lane0; l < lane1; ++l) HIPCHK(canon_unpack_words(cg_, dw, digits(dst, l), stream()));
+    HIPCHK(hipStreamSynchronize(stream()));
     return;
   }
   std::vector<uint64_t> v(pl_.n);
   host_digits::unpack_words(w, count, width_, v.data());
   const std::vector<uint32_t> natural(v.begin(), v.end());
-  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipStreamSynchronize(stream()));
   uint32_t* nat = reinterpret_cast<uint32_t*>(work());
   HIPCHK(hipMemcpy(nat, natural.data(), pl_.n * 4, hipMemcpyHostToDevice));
-  for (size_t l = lane0; l < lane1; ++l) HIPCHK(canon_scatter(dp_, pl_.p, nat, digits(dst, l), stream_));
-  HIPCHK(hipStreamSynchronize(stream_));
+  for (size_t l = lane0; l < lane1; ++l) HIPCHK(canon_scatter(dp_, pl_.p, nat, digits(dst, l), stream()));
+  HIPCHK(hipStreamSynchronize(stream()));
 }
 
 bool Engine::equal(size_t lhs, size_t rhs) {
@@ -459,7 +470,7 @@ bool Engine::equal(size_t lhs, size_t rhs) {
     // registers back and carries them on the host: engine.h:148-157 via engine_gpu.h:1534-1561)
     uint32_t* a = canon_digits(lhs, 0);
     uint32_t* b = canon_digits(rhs, 1);
-    HIPCHK(canon_compare(a, b, uint32_t(pl_.n), canon_flags<uint32_t>(cg_, canon_) + 2, stream_));
+    HIPCHK(canon_compare(a, b, uint32_t(pl_.n), canon_flags<uint32_t>(cg_, canon_) + 2, stream()));
     uint32_t flags[4];
     if (canon_flags_ok(flags)) return flags[2] == 0;
   }
@@ -475,9 +486,18 @@ void Engine::copy(size_t dst, size_t src) {
   // the register is copied as it stands: digits with their pending run carries (no carry sweep),
   // a multiplicand image whole; with lanes the whole slot (a lane's digits are the first half of its 8n bytes)
   const size_t bytes = lanes_ > 1 ? lanes_ * reg_bytes_ : (kind_[src] == kDigits) ? pl_.n * 4 : reg_bytes_;
-  HIPCHK(hipMemcpyAsync(slot_[dst], slot_[src], bytes, hipMemcpyDeviceToDevice, stream_));
-  if (kind_[src] == kDigits && pending_carry_[src])
-    HIPCHK(hipMemcpyAsync(cbuf(dst), cbuf(src), lanes_ * pl_.runs() * 8, hipMemcpyDeviceToDevice, stream_));
+  const bool carries = kind_[src] == kDigits && pending_carry_[src];
+  if (batching_) {   // the same bytes, lane by lane, by the lane's threads
+    const size_t per_lane = bytes / lanes_;
+    if (per_lane % 16 || per_lane > 0xFFFFFFFFu) throw std::runtime_error("internal: batch copy of a register that is no multiple of 16 bytes");
+    BatchOp& op = batch_slot();
+    op.kind = BatchOp::kCopy; op.copy_bytes = uint32_t(per_lane);
+    op.la.a = digits(src); op.la.s1 = digits(dst);
+    if (carries) { op.la.ca = cbuf(src); op.la.cs1 = cbuf(dst); }
+  } else {
+    HIPCHK(hipMemcpyAsync(slot_[dst], slot_[src], bytes, hipMemcpyDeviceToDevice, stream()));
+    if (carries) HIPCHK(hipMemcpyAsync(cbuf(dst), cbuf(src), lanes_ * pl_.runs() * 8, hipMemcpyDeviceToDevice, stream()));
+  }
   pending_carry_[dst] = (kind_[src] == kDigits) ? pending_carry_[src] : 0;
   kind_[dst] = kind_[src];
 }
@@ -485,11 +505,11 @@ void Engine::copy(size_t dst, size_t src) {
 void Engine::square_chain(size_t r, uint32_t a, hipEvent_t* ev) {
   if (a > pl_.a_fast) { square_chain(r, 1, ev); scale(r, a); return; }   // beyond the fused carry's bound (plan.hpp fused_factor_limit)
   if (pl_.onelaunch) { one_launch(r, 0, nullptr, nullptr, nullptr, a, -1, -1); return; }   // (never with events: time_square_mul refuses the plan)
-  if (ev) HIPCHK(hipEventRecord(ev[0], stream_));
+  if (ev) HIPCHK(hipEventRecord(ev[0], stream()));
   run_front(r);
-  if (ev) HIPCHK(hipEventRecord(ev[1], stream_));
+  if (ev) HIPCHK(hipEventRecord(ev[1], stream()));
   run_middle(work(), nullptr, work(), 0);
-  if (ev) HIPCHK(hipEventRecord(ev[2], stream_));
+  if (ev) HIPCHK(hipEventRecord(ev[2], stream()));
   run_back(r, a, ev ? ev + 3 : nullptr);
 }
 
@@ -535,7 +555,7 @@ void Engine::scale(size_t r, uint32_t a) {
   need_residue(r, "scale");
   uint64_t* fresh = take_spare_cbuf();
   const uint64_t* cin = pending_carry_[r] ? cbuf(r) : nullptr;
-  HIPCHK(launch_scale(dp_, digits(r), cin, digits(r), fresh, a, stream_));
+  HIPCHK(launch_scale(dp_, digits(r), cin, digits(r), fresh, a, stream()));
   adopt_cbuf(r, fresh);
   pending_carry_[r] = 1;
   // runs of two digits: the carry words (below 2^34: digit < 2^(q+2) after the passes, times a < 2^32) go in at once
@@ -571,7 +591,8 @@ void Engine::addsub(long s1, long s2, long d1, long d2, size_t a, size_t b) {
   if (d1 >= 0) { la.d1 = digits(size_t(d1)); la.cd1 = fresh[2]; }
   if (d2 >= 0) { la.d2 = digits(size_t(d2)); la.cd2 = fresh[3]; }
   if ((s2 >= 0 && s1 < 0) || (d2 >= 0 && d1 < 0)) throw std::runtime_error("internal: copy output without a primary output");
-  HIPCHK(launch_linear(dp_, la, stream_));
+  if (batching_) { BatchOp& op = batch_slot(); op.kind = BatchOp::kLinear; op.la = la; }
+  else HIPCHK(launch_linear(dp_, la, stream()));
   for (int i = 0; i < 4; ++i)
     if (outs[i] >= 0) {
       const size_t r = size_t(outs[i]);
@@ -590,7 +611,7 @@ void Engine::back_ext(size_t dst, uint32_t a, long copy_to, long add_src) {
   if (copy_to >= 0 && size_t(copy_to) != dst) { x.digits2 = digits(size_t(copy_to)); x.cbuf2 = cbuf(size_t(copy_to)); }
   if (add_src >= 0) { x.add_digits = digits(size_t(add_src)); x.add_cbuf = pending_carry_[size_t(add_src)] ? cbuf(size_t(add_src)) : nullptr; }
   uint64_t* fresh = take_spare_cbuf();   // the addend may be dst itself: its pending carries are read while the new ones are written
-  HIPCHK(cols_.back_ext(dp_, work(), digits(dst), fresh, a, x, stream_));
+  HIPCHK(cols_.back_ext(dp_, work(), digits(dst), fresh, a, x, stream()));
   adopt_cbuf(dst, fresh);
   const size_t outs[2] = {dst, x.digits2 ? size_t(copy_to) : dst};
   for (int i = 0; i < (x.digits2 ? 2 : 1); ++i) {
@@ -677,7 +698,56 @@ void Engine::sub_u32(size_t r, uint32_t v) {
   // then go negative, which the unsigned back sweep reads as values near the field prime; the borrow below is exact for every register)
   // the small subtraction only touches the digit vector (cyclic borrow), so run carries that are still pending
   // for the next front sweep can stay pending: value = digits + carries - v either way
-  HIPCHK(launch_sub_small(dp_, digits(r), v, stream_));
+  HIPCHK(launch_sub_small(dp_, digits(r), v, stream()));
+}
+
+// ---- batches ----------------------------------------------------------------------------------
+
+void Engine::batch_begin() {
+  if (!pl_.onelaunch) throw std::runtime_error("batch_begin: batches need one-launch products (plan token onelaunch): only there does a lane stay inside one work-group");
+  if (batching_) throw std::runtime_error("batch_begin: a batch is open already (batch_end comes first)");
+  HIPCHK(hipSetDevice(device_));
+  if (!batch_dev_) {
+    for (int h = 0; h < 2; ++h) {
+      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&batch_stage_[h]), kBatchCapacity * sizeof(BatchOp), hipHostMallocDefault));
+      HIPCHK(hipEventCreateWithFlags(&batch_read_[h], hipEventDisableTiming));
+    }
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&batch_dev_), kBatchCapacity * sizeof(BatchOp)));
+  }
+  batching_ = true;
+}
+
+void Engine::batch_end() {
+  if (!batching_) throw std::runtime_error("batch_end: no batch is open (batch_begin comes first)");
+  batching_ = false;   // first: the batch is closed whatever the flush says
+  HIPCHK(hipSetDevice(device_));
+  flush_batch();
+}
+
+void Engine::batch_stats(uint64_t out[4]) const {
+  out[0] = batch_ops_; out[1] = batch_launches_; out[2] = kBatchCapacity; out[3] = batch_pending_;
+}
+
+BatchOp& Engine::batch_slot() {
+  if (batch_pending_ == kBatchCapacity) flush_batch();
+  ++batch_ops_;
+  return *new (&batch_stage_[batch_half_][batch_pending_++]) BatchOp();
+}
+
+// The descriptors of the half just filled go to the device buffer and run, both on the stream: the copy waits for the launch before it,
+// which read the buffer.  Then the other half is the one to fill, once the launch that read it last is over.
+void Engine::flush_batch() {
+  if (!batch_pending_) return;
+  const int h = batch_half_;
+  const size_t count = batch_pending_;
+  batch_pending_ = 0;   // (stream_, not stream(): this is the flush)
+  HIPCHK(hipMemcpyAsync(batch_dev_, batch_stage_[h], count * sizeof(BatchOp), hipMemcpyHostToDevice, stream_));
+  HIPCHK(launch_batch(dp_, batch_dev_, uint32_t(count), one_.TL, one_.K, one_.groups, stream_));
+  HIPCHK(hipEventRecord(batch_read_[h], stream_));
+  batch_in_flight_[h] = true;
+  ++batch_launches_;
+  batch_half_ = h ^ 1;
+  if (batch_in_flight_[batch_half_]) { HIPCHK(hipEventSynchronize(batch_read_[batch_half_])); batch_in_flight_[batch_half_] = false; }
 }
 
 // ---- raw images -----------------------------------------------------------------------------
@@ -688,7 +758,7 @@ void Engine::get_data(size_t src, void* data, size_t size) {
   if (size != register_data_size()) throw std::runtime_error("get_data: size mismatch");
   HIPCHK(hipSetDevice(device_));
   normalize(src);
-  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipStreamSynchronize(stream()));
   HIPCHK(hipMemcpy(data, slot_[src], reg_bytes_, hipMemcpyDeviceToHost));
   const uint64_t tag = register_tag(pl_, kc_, kind_[src] == kImage);
   std::memcpy(static_cast<unsigned char*>(data) + reg_bytes_, &tag, 8);
@@ -713,7 +783,7 @@ void Engine::set_data(size_t dst, const void* data, size_t size) {
   uint64_t tag = 0;
   std::memcpy(&tag, static_cast<const unsigned char*>(data) + reg_bytes_, 8);
   HIPCHK(hipSetDevice(device_));
-  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipStreamSynchronize(stream()));
   HIPCHK(hipMemcpy(slot_[dst], data, reg_bytes_, hipMemcpyHostToDevice));
   kind_[dst] = (tag & 1) ? kImage : kDigits;
   pending_carry_[dst] = 0;
@@ -751,10 +821,10 @@ void Engine::time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, d
   HIPCHK(hipSetDevice(device_));
   EventPool pool;   // destroys its events on every way out (a HIPCHK that throws mid-batch used to leak them)
   const hipEvent_t e0 = pool.make(), e1 = pool.make();
-  HIPCHK(hipStreamSynchronize(stream_));
-  HIPCHK(hipEventRecord(e0, stream_));
+  HIPCHK(hipStreamSynchronize(stream()));
+  HIPCHK(hipEventRecord(e0, stream()));
   square_mul_n(r, a, iters, sub);
-  HIPCHK(hipEventRecord(e1, stream_));
+  HIPCHK(hipEventRecord(e1, stream()));
   HIPCHK(hipEventSynchronize(e1));
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, e0, e1));
@@ -772,8 +842,8 @@ void Engine::time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, d
       constexpr size_t kBatch = 64, kSkip = 8;   // the first records carry the queue start-up
       std::vector<hipEvent_t> oe(kBatch);
       for (auto& x : oe) x = pool.make();
-      for (size_t i = 0; i < kBatch; ++i) HIPCHK(hipEventRecord(oe[i], stream_));
-      HIPCHK(hipStreamSynchronize(stream_));
+      for (size_t i = 0; i < kBatch; ++i) HIPCHK(hipEventRecord(oe[i], stream()));
+      HIPCHK(hipStreamSynchronize(stream()));
       float t = 0;
       HIPCHK(hipEventElapsedTime(&t, oe[kSkip], oe[kBatch - 1]));
       overhead = double(t) / double(kBatch - 1 - kSkip);
@@ -781,9 +851,9 @@ void Engine::time_square_mul(size_t r, uint32_t a, uint32_t sub, size_t iters, d
     for (size_t i = 0; i < reps; ++i) {
       square_chain(r, a, &ev[i * per]);
       if (sub) sub_u32(r, sub);
-      HIPCHK(hipEventRecord(ev[i * per + 5], stream_));
+      HIPCHK(hipEventRecord(ev[i * per + 5], stream()));
     }
-    HIPCHK(hipStreamSynchronize(stream_));
+    HIPCHK(hipStreamSynchronize(stream()));
     for (size_t i = 0; i < reps; ++i)
       for (size_t k = 0; k < 5 && k < kcount; ++k) {
         float t = 0;
@@ -825,15 +895,15 @@ void Engine::probe(int kind, int grid_mult, int extra_lds, int boost_pct, size_t
   HIPCHK(hipMemset(dtl, 0, grid * 64));
   uint32_t* dout = reinterpret_cast<uint32_t*>(slot_[0]);   // register 0 is scratch here
   auto launch = [&](const DevPlan& dd) {
-    HIPCHK((v5 ? v5_probe_launch : v2_probe_launch)(dd, kind, grid_mult, extra_lds, digits(1 % nregs_), kind == 2 ? cbuf(0) : nullptr, work(), dout, stream_));
+    HIPCHK((v5 ? v5_probe_launch : v2_probe_launch)(dd, kind, grid_mult, extra_lds, digits(1 % nregs_), kind == 2 ? cbuf(0) : nullptr, work(), dout, stream()));
   };
   for (int w = 0; w < 3; ++w) launch(d);
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-  HIPCHK(hipStreamSynchronize(stream_));
-  HIPCHK(hipEventRecord(e0, stream_));
+  HIPCHK(hipStreamSynchronize(stream()));
+  HIPCHK(hipEventRecord(e0, stream()));
   for (size_t i = 0; i < iters; ++i) launch(d);
-  HIPCHK(hipEventRecord(e1, stream_));
+  HIPCHK(hipEventRecord(e1, stream()));
   HIPCHK(hipEventSynchronize(e1));
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, e0, e1));
@@ -842,9 +912,9 @@ void Engine::probe(int kind, int grid_mult, int extra_lds, int boost_pct, size_t
   if (tl) {
     d.probe = dtl;
     // (boost_pct < 0: the instrumented launch follows a launch of ANOTHER kernel, as in a squaring, instead of a launch of itself)
-    if (boost_pct < 0) { if (kind == 1) HIPCHK(cols_.back(dp_, work(), dout, cbuf(0), 1, stream_)); else run_middle(work(), nullptr, work(), 0); }
+    if (boost_pct < 0) { if (kind == 1) HIPCHK(cols_.back(dp_, work(), dout, cbuf(0), 1, stream())); else run_middle(work(), nullptr, work(), 0); }
     launch(d);
-    HIPCHK(hipStreamSynchronize(stream_));
+    HIPCHK(hipStreamSynchronize(stream()));
     HIPCHK(hipMemcpy(tl, dtl, grid * 64, hipMemcpyDeviceToHost));
   }
   HIPCHK(hipFree(dtl));

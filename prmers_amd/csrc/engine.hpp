@@ -69,6 +69,16 @@ class Engine final : public RegisterMachine {
   void square_mul_prepare(size_t src, size_t img_out, uint32_t a) override;
   bool square_mul_prepare_is_fused() const override { return true; }
 
+  // Batches (plan token onelaunch only): between batch_begin and batch_end the register operations that are products,
+  // run-wise sums and differences or copies -- copy, add, sub_reg, addsub, every form one_launch serves, the loops of square_mul_n
+  // (sub == 0) and square_mul_bits -- are checked and booked as always and then queued; the queue runs as ONE launch (kernels.hip
+  // k_batch).  Anything else the engine puts on its stream flushes the queue first (stream()), a full queue flushes by itself, and
+  // batch_end flushes.  Destroying the engine discards what is queued.
+  static constexpr size_t kBatchCapacity = 256;   // descriptors a launch takes
+  void batch_begin() override;
+  void batch_end() override;
+  void batch_stats(uint64_t out[4]) const override;
+
   size_t register_data_size() const override { return reg_bytes_ + 8; }
   void get_data(size_t src, void* data, size_t size) override;
   void set_data(size_t dst, const void* data, size_t size) override;
@@ -122,6 +132,11 @@ class Engine final : public RegisterMachine {
   void run_front(size_t r);          // digits(r) (+ pending run carries) -> work_
   void run_middle(const uint64_t* in, const uint64_t* y, uint64_t* out, int mode, const uint64_t* y2 = nullptr, uint64_t* img = nullptr);
   void run_back(size_t r, uint32_t a, hipEvent_t* ev = nullptr);
+  // The engine's stream for everything that is not queued: the one place where a batch is flushed.  Whatever is put on the stream --
+  // a launch, a copy, a memset, a synchronisation before a host copy -- asks for it here, so it runs behind the operations queued before it.
+  hipStream_t stream() { if (batch_pending_) flush_batch(); return stream_; }
+  void flush_batch();            // the queue as one launch of k_batch; then the other staging half is filled
+  BatchOp& batch_slot();         // the next free descriptor of the queue (a full queue is flushed first)
 
   Plan pl_;
   DevPlan dp_{};
@@ -149,6 +164,16 @@ class Engine final : public RegisterMachine {
   std::vector<uint32_t> stage_;  // host staging (one register of digits)
   uint32_t* canon_ = nullptr;    // device scratch of the canonicalisation: work arrays + two outputs of n digits (lazy)
   bool host_carry_ = false;      // MI355_HOST_CARRY=1: compare / res64 / read-back through the host (A/B tests)
+  // batches: descriptors are written into one of two pinned halves, go to the device buffer by a copy on the stream and are read there by
+  // the launch behind it; a half is written again only after the event recorded behind the launch that read it
+  bool batching_ = false;        // between batch_begin and batch_end
+  size_t batch_pending_ = 0;     // descriptors in the half being filled
+  int batch_half_ = 0;
+  BatchOp* batch_stage_[2] = {nullptr, nullptr};   // pinned, kBatchCapacity descriptors each (made by the first batch_begin)
+  hipEvent_t batch_read_[2] = {nullptr, nullptr};  // recorded behind the launch that read the half; null until there was one
+  bool batch_in_flight_[2] = {false, false};
+  BatchOp* batch_dev_ = nullptr;
+  uint64_t batch_ops_ = 0, batch_launches_ = 0;    // batch_stats
 };
 
 }  // namespace mi355

@@ -7,6 +7,7 @@
 //             digits -> digits(u32) + one carry word per run
 //   k_carry_fix: adds each run's carry word into the first digits of the next run (weak carry)
 //   k_onelaunch: the three sweeps of a small transform (n <= 8192) in one launch, a whole residue per work-group, work buffer in LDS
+//   k_batch: a queue of such products, run-wise sums and differences and copies in one launch, every work-group for its own residues
 // This replaces the reference's kernel chain forward64_0 / forward256 / sqr512 / backward256 /
 // backward64_0 / carry_weight_mul_p1 / carry_weight_p2 (include/marin/engine_gpu.h:1568-1630,
 // kernels/marin.cl:989-1075,1517-1528,1696-1728,2198-2216).  Butterfly algebra follows
@@ -514,53 +515,155 @@ __device__ __forceinline__ const OneLaunchPack& args_again() {
   asm volatile("" : "+s"(p));
   return *(const OneLaunchPack*)p;
 }
-template <bool EXT>
-__global__ void __launch_bounds__(1024) k_onelaunch(OneLaunchPack) {
-  uint32_t lane, cteam, cteams, ctid, ct, rteam, rteams, rtid, rt, NT, M1, mode;
-  uint64_t rb, cb;
+// A thread's place in its group: its lane, whether that lane exists (live), the lane's LDS, and its team and thread of the team in the
+// column phases (c...) and the row phase (r...).  Plan and block shape alone decide it: k_batch works it out once for all its operations.
+struct LanePlace {
+  uint32_t lane, lt, TL, cteam, cteams, ctid, ct, rteam, rteams, rtid, rt, NT, M1;
+  uint64_t rb, cb;   // bytes of a lane's register, of its carry words
   bool live;
-  P2 *W, *Xc, *Xr;
-  {
-    const OneLaunchPack& g = args_again();
-    const DevPlan& pl = g.pl;
-    const uint32_t TL = g.oa.TL, gl = threadIdx.x / TL, lt = threadIdx.x - gl * TL;   // lane of the group, thread of the lane
-    live = blockIdx.x * g.oa.K + gl < pl.lanes;
-    lane = live ? blockIdx.x * g.oa.K + gl : pl.lanes - 1;
-    rb = uint64_t(pl.n) * 8; cb = uint64_t(pl.M1) * (pl.M2 >> pl.logC) * 8;   // bytes of a lane's register, of its carry words
-    W = reinterpret_cast<P2*>(smem_raw) + size_t(gl) * 2 * pl.m;   // the lane's work buffer; its transform scratch follows
-    M1 = pl.M1; NT = pl.M2 >> pl.logC; mode = uint32_t(g.oa.mode);
-    // column teams: TL = r5 2^j threads over NT = 2^i tiles; row teams: over M1 = r5 L1 rows.  Each count divides both.
-    cteams = min(NT, TL / pl.r5); ct = TL / cteams; cteam = lt / ct; ctid = lt - cteam * ct;
-    rteams = min(M1, TL); rt = TL / rteams; rteam = lt / rt; rtid = lt - rteam * rt;
-    Xc = W + pl.m + size_t(cteam) * (M1 << pl.logC);
-    Xr = W + pl.m + size_t(rteam) * pl.M2;
-  }
-
-  for (uint32_t T = cteam; T < NT; T += cteams) {
-    const OneLaunchPack& g = args_again();
-    front_body(g.pl, lane_at(g.oa.src, lane, rb), lane_at(g.oa.src_cbuf, lane, cb), W, T, Xc, ctid, ct);
+  P2 *W, *Xc, *Xr;   // the lane's work buffer; its team's transform scratch in the column and in the row phases
+};
+__device__ __forceinline__ LanePlace lane_place(const DevPlan& pl, uint32_t TL, uint32_t K) {
+  LanePlace t;
+  const uint32_t gl = threadIdx.x / TL, lt = threadIdx.x - gl * TL;   // lane of the group, thread of the lane
+  t.lt = lt; t.TL = TL;
+  t.live = blockIdx.x * K + gl < pl.lanes;
+  t.lane = t.live ? blockIdx.x * K + gl : pl.lanes - 1;
+  t.rb = uint64_t(pl.n) * 8; t.cb = uint64_t(pl.M1) * (pl.M2 >> pl.logC) * 8;
+  t.W = reinterpret_cast<P2*>(smem_raw) + size_t(gl) * 2 * pl.m;   // the lane's work buffer; its transform scratch follows
+  t.M1 = pl.M1; t.NT = pl.M2 >> pl.logC;
+  // column teams: TL = r5 2^j threads over NT = 2^i tiles; row teams: over M1 = r5 L1 rows.  Each count divides both.
+  t.cteams = min(t.NT, TL / pl.r5); t.ct = TL / t.cteams; t.cteam = lt / t.ct; t.ctid = lt - t.cteam * t.ct;
+  t.rteams = min(t.M1, TL); t.rt = TL / t.rteams; t.rteam = lt / t.rt; t.rtid = lt - t.rteam * t.rt;
+  t.Xc = t.W + pl.m + size_t(t.cteam) * (t.M1 << pl.logC);
+  t.Xr = t.W + pl.m + size_t(t.rteam) * pl.M2;
+  return t;
+}
+// The three phases of a product for the thread at t, for k_onelaunch and k_batch alike.  again() hands out plan, operands and extras anew
+// (a view of three references behind a pointer the compiler does not see through); every trip of every phase asks for them, so nothing of
+// one phase is held in scalar registers through another.  Every thread of the group reaches every barrier; mode 2 ends after the rows.
+template <bool EXT, class Again>
+__device__ __forceinline__ void product_phases(const LanePlace& t, Again again) {
+  for (uint32_t T = t.cteam; T < t.NT; T += t.cteams) {
+    const auto& g = again();
+    front_body(g.pl, lane_at(g.oa.src, t.lane, t.rb), lane_at(g.oa.src_cbuf, t.lane, t.cb), t.W, T, t.Xc, t.ctid, t.ct);
     __syncthreads();
   }
 
-  for (uint32_t row = rteam; row < M1; row += rteams) {
-    const OneLaunchPack& g = args_again();
-    uint64_t* img = lane_at(g.oa.img, lane, rb);
-    if (mode == 2) middle_body(g.pl, W, nullptr, nullptr, img, 2, row, Xr, rtid, rt, nullptr, live);
-    else if (mode == 4) middle_body<true>(g.pl, W, nullptr, nullptr, W, 0, row, Xr, rtid, rt, img, live);
-    else middle_body(g.pl, W, lane_at(g.oa.y, lane, rb), lane_at(g.oa.y2, lane, rb), W, int(mode), row, Xr, rtid, rt);
+  for (uint32_t row = t.rteam; row < t.M1; row += t.rteams) {
+    const auto& g = again();
+    const uint32_t mode = uint32_t(g.oa.mode);
+    uint64_t* img = lane_at(g.oa.img, t.lane, t.rb);
+    if (mode == 2) middle_body(g.pl, t.W, nullptr, nullptr, img, 2, row, t.Xr, t.rtid, t.rt, nullptr, t.live);
+    else if (mode == 4) middle_body<true>(g.pl, t.W, nullptr, nullptr, t.W, 0, row, t.Xr, t.rtid, t.rt, img, t.live);
+    else middle_body(g.pl, t.W, lane_at(g.oa.y, t.lane, t.rb), lane_at(g.oa.y2, t.lane, t.rb), t.W, int(mode), row, t.Xr, t.rtid, t.rt);
     __syncthreads();
   }
-  if (mode == 2) return;
+  if (again().oa.mode == 2) return;
 
-  for (uint32_t T = cteam; T < NT; T += cteams) {
-    const OneLaunchPack& g = args_again();
+  for (uint32_t T = t.cteam; T < t.NT; T += t.cteams) {
+    const auto& g = again();
     BackExt x;
     if (EXT) {
-      x.digits2 = lane_at(g.x.digits2, lane, rb); x.cbuf2 = lane_at(g.x.cbuf2, lane, cb);
-      x.add_digits = lane_at(g.x.add_digits, lane, rb); x.add_cbuf = lane_at(g.x.add_cbuf, lane, cb);
+      x.digits2 = lane_at(g.x.digits2, t.lane, t.rb); x.cbuf2 = lane_at(g.x.cbuf2, t.lane, t.cb);
+      x.add_digits = lane_at(g.x.add_digits, t.lane, t.rb); x.add_cbuf = lane_at(g.x.add_cbuf, t.lane, t.cb);
     }
-    back_body<EXT>(g.pl, W, lane_at(g.oa.dst, lane, rb), lane_at(g.oa.dst_cbuf, lane, cb), g.oa.a, x, T, Xc, ctid, ct, live);
+    back_body<EXT>(g.pl, t.W, lane_at(g.oa.dst, t.lane, t.rb), lane_at(g.oa.dst_cbuf, t.lane, t.cb), g.oa.a, x, T, t.Xc, t.ctid, t.ct, t.live);
     __syncthreads();   // the next trip refills the scratch that the carry chains of this one read
+  }
+}
+struct OneLaunchAgain { __device__ __forceinline__ const OneLaunchPack& operator()() const { return args_again(); } };
+template <bool EXT>
+__global__ void __launch_bounds__(1024) k_onelaunch(OneLaunchPack) {
+  LanePlace t;
+  {
+    const OneLaunchPack& g = args_again();
+    t = lane_place(g.pl, g.oa.TL, g.oa.K);
+  }
+  product_phases<EXT>(t, OneLaunchAgain());
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batches: a queue of register operations of a one-launch engine in ONE launch.  A lane lives in one work-group for every
+// operation (the shape is the plan's and the block's, lane_place), so no operation of a lane waits on another group: each group walks the
+// descriptors in order for its own lanes, with a group barrier after every operation.
+//   Memory.  Unlike k_onelaunch, an operation here reads digits, carry words and images that OTHER waves of the group stored a few
+//   operations earlier in the same launch.  The barrier between operations is __syncthreads(), a workgroup-scope release / acquire (the
+//   stores of every wave have completed and are visible to the group's loads behind it), never a bare s_barrier.  None of that data is
+//   read through the scalar cache, which vector stores do not update: every such address depends on the thread index, and nothing here
+//   declares it const __restrict__, read-only or non-temporal.  Plan tables and the descriptors do not change during the launch; the
+//   descriptors are read as constant memory (scalar loads), anew in every phase like the argument block of k_onelaunch.
+//   Carry buffers.  The host resolved every carry buffer when the operation was issued (engine.hip take_spare_cbuf / adopt_cbuf): a
+//   product writes its new words to a spare buffer while carry_in_of reads the neighbouring runs' words of the old one, and the buffer
+//   one operation releases may be the spare the next one writes.  That is safe because a lane never leaves its group and a barrier stands
+//   between the two operations.
+//   Barriers.  Every thread of a group walks every descriptor; kind and mode are the same for all of them.  A lane beyond the last one
+//   (live == false) runs the products on the last lane's inputs for the barriers' sake, skips the other kinds, and stores nothing.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void linear_body(const DevPlan& pl, const LinArgs& la, uint32_t run);   // (with the run-wise kernels, below)
+struct BatchPack { DevPlan pl; const BatchOp* ops; uint32_t count; };
+__device__ __forceinline__ const BatchPack& batch_args_again() {
+  auto p = __builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const BatchPack*)p;
+}
+// descriptor i, read anew: constant for the launch, so constant address space (scalar loads), behind a pointer the compiler does not see through
+__device__ __forceinline__ const BatchOp& batch_op_again(const BatchOp* ops, uint32_t i) {
+  typedef const __attribute__((address_space(4))) BatchOp* ConstOp;
+  ConstOp p = (ConstOp)(ops) + i;
+  asm volatile("" : "+s"(p));
+  return *(const BatchOp*)p;
+}
+struct ProductView { const DevPlan& pl; const OneLaunchArgs& oa; const BackExt& x; };
+struct BatchAgain {   // plan and product i of the queue, for product_phases
+  uint32_t i;
+  __device__ __forceinline__ ProductView operator()() const {
+    const BatchPack& g = batch_args_again();
+    const BatchOp& op = batch_op_again(g.ops, i);
+    return ProductView{g.pl, op.oa, op.x};
+  }
+};
+__global__ void __launch_bounds__(1024) k_batch(BatchPack) {
+  LanePlace t0;
+  uint32_t live0;
+  {
+    const BatchPack& g = batch_args_again();
+    const uint32_t TL = min(g.pl.m, g.pl.r5 == 5 ? 640u : 1024u);   // plan.hpp onelaunch_shape; K is what the block holds
+    t0 = lane_place(g.pl, TL, blockDim.x / TL);
+    live0 = t0.live;
+  }
+  // (the count, too, is read where it is needed: only i is held through an operation)
+  for (uint32_t i = 0; i < batch_args_again().count; ++i) {
+    // The thread's own numbers pass through an empty asm in every round: the lane masks of the conditions on them (thread below the tile
+    // size, team below the tile count, live) are then worked out where they are used.  As loop invariants they were hoisted out of the
+    // loop and held in scalar registers through all of it, six more than a wave has (spilled to a vector register).
+    LanePlace t = t0;
+    uint32_t live = live0;
+    asm volatile("" : "+v"(t.lt), "+v"(t.cteam), "+v"(t.ctid), "+v"(t.rteam), "+v"(t.rtid), "+v"(live));
+    t.live = live != 0;
+    const uint32_t kind = batch_op_again(batch_args_again().ops, i).kind;
+    if (kind == BatchOp::kProduct) {
+      product_phases<true>(t, BatchAgain{i});
+    } else if (kind == BatchOp::kLinear) {
+      if (t.live) {
+        const BatchPack& g = batch_args_again();
+        const LinArgs& la = batch_op_again(g.ops, i).la;
+        LinArgs l;
+        l.a = lane_at(la.a, t.lane, t.rb); l.ca = lane_at(la.ca, t.lane, t.cb); l.b = lane_at(la.b, t.lane, t.rb); l.cb = lane_at(la.cb, t.lane, t.cb);
+        l.s1 = lane_at(la.s1, t.lane, t.rb); l.cs1 = lane_at(la.cs1, t.lane, t.cb); l.s2 = lane_at(la.s2, t.lane, t.rb); l.cs2 = lane_at(la.cs2, t.lane, t.cb);
+        l.d1 = lane_at(la.d1, t.lane, t.rb); l.cd1 = lane_at(la.cd1, t.lane, t.cb); l.d2 = lane_at(la.d2, t.lane, t.rb); l.cd2 = lane_at(la.cd2, t.lane, t.cb);
+        for (uint32_t run = t.lt; run < t.M1 * t.NT; run += t.TL) linear_body(g.pl, l, run);
+      }
+    } else if (t.live) {   // kCopy: the register as it stands, 16 bytes a thread and trip, then its pending carry words
+      const BatchOp& op = batch_op_again(batch_args_again().ops, i);
+      const uint4* src = reinterpret_cast<const uint4*>(lane_at(op.la.a, t.lane, t.rb));
+      uint4* dst = reinterpret_cast<uint4*>(lane_at(op.la.s1, t.lane, t.rb));
+      for (uint32_t e = t.lt, ne = op.copy_bytes / 16; e < ne; e += t.TL) dst[e] = src[e];
+      const uint64_t* csrc = lane_at(op.la.ca, t.lane, t.cb);
+      uint64_t* cdst = lane_at(op.la.cs1, t.lane, t.cb);
+      if (csrc) for (uint32_t run = t.lt; run < t.M1 * t.NT; run += t.TL) cdst[run] = csrc[run];
+    }
+    __syncthreads();   // the next operation reads what this one stored
   }
 }
 
@@ -659,21 +762,23 @@ __global__ void __launch_bounds__(256) k_back_split_a(DevPlan pl, const uint64_t
 // run-wise kernels: one thread per run (T, i1) of 2C digits
 // ---------------------------------------------------------------------------------------------
 struct RunHead { uint32_t T, i1; size_t ci, off; };   // ci: index of the run's carry word; off: of its first digit
-// the thread's run; false beyond the last one
-__device__ __forceinline__ bool run_head(const DevPlan& pl, RunHead& r) {
-  const uint32_t run = blockIdx.x * blockDim.x + threadIdx.x, M1 = pl.M1;
+// run number `run` of a lane (as the sweep bodies take (tid, nthr): the caller says which); false beyond the last one
+__device__ __forceinline__ bool run_head(const DevPlan& pl, RunHead& r, uint32_t run) {
+  const uint32_t M1 = pl.M1;
   if (run >= M1 * (pl.M2 / pl.C)) return false;
   r.T = run / M1; r.i1 = run - r.T * M1;
   r.ci = size_t(r.T) * M1 + r.i1; r.off = r.ci * pl.C * 2;
   return true;
 }
+// the run-wise kernels' own: one thread per run
+__device__ __forceinline__ bool run_head(const DevPlan& pl, RunHead& r) { return run_head(pl, r, blockIdx.x * blockDim.x + threadIdx.x); }
 
 // a, b (+ their pending carry words) -> sum and / or difference, each written to up to two
 // registers, with the run's carry-out word left pending (kernels.hpp LinArgs).  The difference is a - b + 2 Mp
 // digit by digit (neg2_mp4, marin.cl:246-256), so nothing goes negative: digits are below 2^width + a small excess.
-__device__ __forceinline__ void linear_body(const DevPlan& pl, const LinArgs& la) {
+__device__ __forceinline__ void linear_body(const DevPlan& pl, const LinArgs& la, uint32_t run) {
   RunHead r;
-  if (!run_head(pl, r)) return;
+  if (!run_head(pl, r, run)) return;
   const uint32_t C = pl.C, sa = pl.SA[r.i1];
   const size_t off = r.off;
   uint64_t ca = la.ca ? carry_in_of(pl, la.ca, r.T, r.i1) : 0, cb = la.cb ? carry_in_of(pl, la.cb, r.T, r.i1) : 0;
@@ -708,7 +813,7 @@ __global__ void __launch_bounds__(256) k_linear(DevPlan pl, LinArgs la) {
   l.a = lane_reg<LANES>(pl, la.a); l.ca = lane_cbuf<LANES>(pl, la.ca); l.b = lane_reg<LANES>(pl, la.b); l.cb = lane_cbuf<LANES>(pl, la.cb);
   l.s1 = lane_reg<LANES>(pl, la.s1); l.cs1 = lane_cbuf<LANES>(pl, la.cs1); l.s2 = lane_reg<LANES>(pl, la.s2); l.cs2 = lane_cbuf<LANES>(pl, la.cs2);
   l.d1 = lane_reg<LANES>(pl, la.d1); l.cd1 = lane_cbuf<LANES>(pl, la.cd1); l.d2 = lane_reg<LANES>(pl, la.d2); l.cd2 = lane_cbuf<LANES>(pl, la.cd2);
-  linear_body(pl, l);
+  linear_body(pl, l, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // x a for the factors above the plan's fused bound (plan.hpp fused_factor_limit; Engine::scale): the run's digits with their pending
@@ -848,6 +953,15 @@ hipError_t launch_onelaunch(const DevPlan& pl, const OneLaunchArgs& oa, const Ba
   hipLaunchKernelGGL(x.any() ? k_onelaunch<true> : k_onelaunch<false>, dim3(oa.groups), dim3(oa.K * oa.TL), lds, s, OneLaunchPack{pl, oa, x});
   return hipGetLastError();
 }
+// a batch: `count` descriptors in device memory, the grid, block and LDS of the one-launch products
+hipError_t launch_batch(const DevPlan& pl, const BatchOp* ops, uint32_t count, uint32_t TL, uint32_t K, uint32_t groups, hipStream_t s) {
+  const size_t lds = size_t(K) * pl.m * 32;
+  const uint32_t cap = pl.r5 == 5 ? 640u : 1024u;   // the kernel takes TL from the plan (plan.hpp onelaunch_shape) and K from the block
+  if (!ops || !count || !TL || !K || K * TL > 1024 || lds > kOneLaunchMaxLds || size_t(groups) * K < pl.lanes || TL != (pl.m < cap ? pl.m : cap))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_batch, dim3(groups), dim3(K * TL), lds, s, BatchPack{pl, ops, count});
+  return hipGetLastError();
+}
 // the split column sweeps (M1 = 5 L1 beyond LDS): U is a second work buffer of 8 n bytes
 static uint32_t split_log_cb(const DevPlan& pl) { uint32_t l = 0; while ((size_t(pl.L1) << (l + 1)) * 16 <= size_t(128) * 1024 && (2u << l) <= pl.M2 && l < 2) ++l; return l; }
 hipError_t launch_front_split(const DevPlan& pl, const uint32_t* digits, uint64_t* U, uint64_t* W, hipStream_t s) {
@@ -913,6 +1027,7 @@ hipError_t configure_kernels(size_t lds_front, size_t lds_mid, uint32_t lanes, b
   if (e == hipSuccess && lanes > 1) e = configure_kernels_of<true>(lds_front, lds_mid);
   if (e == hipSuccess && onelaunch) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_onelaunch<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kOneLaunchMaxLds));
   if (e == hipSuccess && onelaunch) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_onelaunch<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kOneLaunchMaxLds));
+  if (e == hipSuccess && onelaunch) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch), hipFuncAttributeMaxDynamicSharedMemorySize, int(kOneLaunchMaxLds));
   return e;
 }
 

@@ -93,7 +93,7 @@ typedef hipError_t (*RowsFn)(const DevPlan& pl, const uint64_t* Win, const uint6
 struct ColSweeps { FrontFn front; BackFn back; BackExtFn back_ext; FourStepFn build_fourstep; };
 
 // generic set (kernels.hip): tiles in LDS, any shape, pl.lanes lanes as grid.y (the run-wise launchers above too)
-// (onelaunch: the entry points of the one-launch products too, to the LDS of their largest size)
+// (onelaunch: the entry points of the one-launch products and of the batches too, to the LDS of their largest size)
 hipError_t configure_kernels(size_t lds_front, size_t lds_mid, uint32_t lanes, bool onelaunch);
 hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s);
 hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
@@ -112,6 +112,20 @@ struct OneLaunchArgs {
   uint32_t TL = 0, K = 0, groups = 0;
 };
 hipError_t launch_onelaunch(const DevPlan& pl, const OneLaunchArgs& oa, const BackExt& x, hipStream_t s);
+// Batches (kernels.hip k_batch): a run of register operations of a one-launch engine as ONE launch with the grid, block and
+// LDS of k_onelaunch.  Every work-group walks the descriptors in order for its own lanes, a group barrier after each.  All pointers are
+// those of lane 0, resolved by the host when the operation was issued (carry buffers included), exactly as the single launches take them.
+//   kProduct: oa and x, as launch_onelaunch takes them (oa.TL, oa.K, oa.groups are not read: the launch has its own)
+//   kLinear:  la, as launch_linear takes it
+//   kCopy:    la.s1 <- la.a, copy_bytes bytes a lane (a multiple of 16); la.cs1 <- la.ca, a lane's carry words, where la.ca is not null
+struct BatchOp {
+  enum : uint32_t { kProduct = 0, kLinear = 1, kCopy = 2 };
+  uint32_t kind = kProduct, copy_bytes = 0;
+  OneLaunchArgs oa;
+  BackExt x;
+  LinArgs la;
+};
+hipError_t launch_batch(const DevPlan& pl, const BatchOp* ops, uint32_t count, uint32_t TL, uint32_t K, uint32_t groups, hipStream_t s);
 // columns of 5 L1 pairs that do not fit LDS (n = 5 * 2^26): the radix-5 stage through a second work buffer U (8 n bytes), C = 1
 hipError_t configure_split(const DevPlan& pl);
 hipError_t launch_front_split(const DevPlan& pl, const uint32_t* digits, uint64_t* U, uint64_t* W, hipStream_t s);

@@ -56,6 +56,12 @@ class RegisterMachine {
   virtual void get_words_lane(size_t lane, size_t src, uint32_t* w, size_t count) { need_lane(lane, "get_words"); get_words(src, w, count); }
   virtual uint64_t res64_lane(size_t lane, size_t src) { need_lane(lane, "res64"); return res64(src); }
 
+  // Batches (include/mi355_batch.h): the register operations between batch_begin and batch_end run as one launch.  Only the Goldilocks
+  // engine with one-launch products has them (engine.hpp); stats: operations queued so far, batch launches so far, capacity, pending now.
+  virtual void batch_begin() { throw std::runtime_error("batch_begin: batches are not implemented for the crt field family"); }
+  virtual void batch_end() { throw std::runtime_error("batch_end: no batch is open (batch_begin comes first)"); }
+  virtual void batch_stats(uint64_t out[4]) const { out[0] = out[1] = out[2] = out[3] = 0; }
+
   virtual size_t register_data_size() const = 0;                              // raw register images (engine.h:134-146)
   virtual void get_data(size_t src, void* data, size_t size) = 0;
   virtual void set_data(size_t dst, const void* data, size_t size) = 0;

@@ -1,6 +1,6 @@
 """ECM factoring of a Mersenne number 2^p - 1 on the engine: Montgomery curves, stages 1 and 2 (the reference: src/modes/RunEcm.cpp).
 
-    python -m prmers_amd.ecm P B1 [B2] [--sigma S] [--curves N] [--lanes B] [--D 30|210|2310] [--plan SPEC] [--onelaunch] [--device N]
+    python -m prmers_amd.ecm P B1 [B2] [--sigma S] [--curves N] [--lanes B] [--D 30|210|2310] [--plan SPEC] [--onelaunch] [--batch] [--device N]
 
 Curve:    Suyama's parametrisation from sigma: u = sigma^2 - 5, v = 4 sigma, the point (u^3 : v^3) on B y^2 = x^3 + A x^2 + x with
           a24 = (A + 2) / 4 = (v - u)^3 (3 u + v) / (16 u^3 v).  The start is taken affine, x0 = u^3 / v^3 and Z = 1: one modular inversion
@@ -26,10 +26,15 @@ and replaced by the compositions they stand for when it has not.
 Lanes:    all curves of a batch make the same engine calls (the ladder bits come from B1, the stage-2 pairs from B1, B2 and D); only x0 and
           a24 differ.  run_lanes() puts curve l into lane l of an engine with lanes (Engine(..., lanes=B), include/mi355_lanes.h) and
           issues the calls of one run(): B curves per launch sequence.  --lanes B / ecm(lanes=B) batches the curves that way.
+Batches:  on an engine with one-launch products (--onelaunch) every ladder step is some twenty launches and copies of almost no work.
+          batch=True / --batch runs the stage-1 ladder and the stage-2 loops inside Engine.batch() (include/mi355_batch.h): the engine
+          queues the calls and runs each queue as one launch.  Writes of constants inside those loops run the queue first; the x0, a24
+          and start point go in before the first batch and Z, the accumulator and the stage-1 point are read after the last has ended.
 Not here: twisted Edwards curves, PRAC chains,
 checkpoints, ECM= worktodo lines, the PrimeNet JSON, a C++ twin.
 """
 import argparse
+import contextlib
 import ctypes
 import json
 import random
@@ -226,10 +231,11 @@ class _Curve:
                 self.add(r1, r0, r1, pt); self.dbl(r0, r0)
 
 
-def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane):
+def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=False):
     """The curves of `sigmas` through one sequence of engine calls: the ladder bits come from B1 and the stage-2 pairs from (B1, B2, D),
     so only the data differ.  by_lane=False: one curve on an engine used as it is (run).  by_lane=True: curve l in lane l of an engine
-    with len(sigmas) lanes (run_lanes); every engine call then acts on all of them.  -> one result per curve"""
+    with len(sigmas) lanes (run_lanes); every engine call then acts on all of them.  batch: the ladder and the stage-2 loops run inside
+    eng.batch() where the object has one (else as without).  -> one result per curve"""
     if b1 < 2:
         raise ValueError("B1 must be at least 2")
     if min(sigmas) < SIGMA_MIN:
@@ -249,6 +255,11 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane):
     ops = _Ops(eng, use_fused)
     cv = _Curve(ops)
     lanes = range(len(sigmas))
+    batching = bool(batch and getattr(eng, "batch", None))
+    launches0 = eng.batch_stats()[1] if batching else 0
+
+    def batched():
+        return eng.batch() if batching else contextlib.nullcontext()
 
     def put(reg, values):
         if not by_lane:
@@ -262,9 +273,10 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane):
         return [eng.get_int(reg, lane=l) for l in lanes] if by_lane else [eng.get_int(reg)]
 
     def results(g1, g2):
+        more = {"launches": eng.batch_stats()[1] - launches0} if batching else {}
         return [{"p": p, "b1": b1, "b2": b2 if stage2 else 0, "D": D if stage2 else None, "sigma": sigmas[l],
                  "factors": [f for f in (g1[l], g2[l]) if 1 < f < mp], "g1": g1[l], "g2": g2[l],
-                 "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused} for l in lanes]
+                 "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused, **more} for l in lanes]
 
     setup = [suyama(s, mp, use_gmp) for s in sigmas]
     failed = [g != 1 for _, _, g in setup]   # the inversion failed: its argument shares g with Mp, which is the curve's result
@@ -288,14 +300,15 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane):
     put(R_X0, [c[0] for c in setup]); ops.prep(R_X0, R_X0)
     a, b = (R_XA, R_ZA), (R_XB, R_ZB)
     put(R_XA, [c[0] for c in setup]); eng.set(R_ZA, 1)
-    cv.dbl(b, a)                                 # (a, b) = (P, 2 P)
-    for i in range(e.bit_length() - 2, -1, -1):
-        if (e >> i) & 1:
-            cv.ladder_step(b, a)
-        else:
-            cv.ladder_step(a, b)
     Q = (R_XQ, R_ZQ)
-    eng.copy(R_XQ, a[0]); eng.copy(R_ZQ, a[1])
+    with batched():
+        cv.dbl(b, a)                             # (a, b) = (P, 2 P)
+        for i in range(e.bit_length() - 2, -1, -1):
+            if (e >> i) & 1:
+                cv.ladder_step(b, a)
+            else:
+                cv.ladder_step(a, b)
+        eng.copy(R_XQ, a[0]); eng.copy(R_ZQ, a[1])
     for l, z in enumerate(get(R_ZQ)):
         if not failed[l]:
             g1[l] = mp if z == 0 else big_gcd(z, mp, use_gmp)
@@ -306,44 +319,45 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane):
         slot = {j: (FIXED_REGISTERS + 2 * i, FIXED_REGISTERS + 2 * i + 1) for i, j in enumerate(J)}
         pairs = stage2_pairs(b1, b2, D)
         if pairs:
-            two = (R_X2, R_Z2)
-            cv.dbl(two, Q)
-            # baby points: the odd multiples of Q; cur = j Q, prev = (j - 2) Q ((-1) Q has the x of Q)
-            prev, cur, nxt = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
-            for r in (0, 1):
-                eng.copy(prev[r], Q[r]); eng.copy(cur[r], Q[r])
-            for j in range(1, J[-1] + 1, 2):
-                if j in slot:
-                    ops.prep(slot[j][0], cur[0]); ops.prep(slot[j][1], cur[1])
-                if j + 2 <= J[-1]:
-                    cv.add(nxt, cur, two, prev)
-                    prev, cur, nxt = cur, nxt, prev
-            # giant steps: cur = k D Q, nxt = (k + 1) D Q
-            DQ = (R_XD, R_ZD)
-            cv.small_ladder(DQ, (R_XG0, R_ZG0), D, Q)
-            k0, k1 = min(pairs), max(pairs)
-            cur, nxt, spare = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
-            if k0 == 0:
-                eng.set(cur[0], 1); eng.set(cur[1], 0)
-                eng.copy(nxt[0], DQ[0]); eng.copy(nxt[1], DQ[1])
-            else:
-                cv.small_ladder(cur, nxt, k0, DQ)
-            eng.set(R_A, 1)
-            for k in range(k0, k1 + 1):
-                for j in pairs.get(k, ()):
-                    eng.copy(R_T, cur[0]); ops.mul(R_T, slot[j][1])      # X_k Z_j
-                    eng.copy(R_W, cur[1]); ops.mul(R_W, slot[j][0])      # Z_k X_j
-                    eng.sub_reg(R_T, R_W)
-                    ops.prep(R_T, R_T)
-                    ops.mul(R_A, R_T)
-                if k + 1 < k1:
-                    if k == 0:
-                        cv.dbl(spare, DQ)        # the difference would be 0 Q
-                    else:
-                        cv.add(spare, nxt, DQ, cur)
-                    cur, nxt, spare = nxt, spare, cur
+            with batched():
+                two = (R_X2, R_Z2)
+                cv.dbl(two, Q)
+                # baby points: the odd multiples of Q; cur = j Q, prev = (j - 2) Q ((-1) Q has the x of Q)
+                prev, cur, nxt = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
+                for r in (0, 1):
+                    eng.copy(prev[r], Q[r]); eng.copy(cur[r], Q[r])
+                for j in range(1, J[-1] + 1, 2):
+                    if j in slot:
+                        ops.prep(slot[j][0], cur[0]); ops.prep(slot[j][1], cur[1])
+                    if j + 2 <= J[-1]:
+                        cv.add(nxt, cur, two, prev)
+                        prev, cur, nxt = cur, nxt, prev
+                # giant steps: cur = k D Q, nxt = (k + 1) D Q
+                DQ = (R_XD, R_ZD)
+                cv.small_ladder(DQ, (R_XG0, R_ZG0), D, Q)
+                k0, k1 = min(pairs), max(pairs)
+                cur, nxt, spare = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
+                if k0 == 0:
+                    eng.set(cur[0], 1); eng.set(cur[1], 0)
+                    eng.copy(nxt[0], DQ[0]); eng.copy(nxt[1], DQ[1])
                 else:
-                    cur, nxt = nxt, cur
+                    cv.small_ladder(cur, nxt, k0, DQ)
+                eng.set(R_A, 1)
+                for k in range(k0, k1 + 1):
+                    for j in pairs.get(k, ()):
+                        eng.copy(R_T, cur[0]); ops.mul(R_T, slot[j][1])      # X_k Z_j
+                        eng.copy(R_W, cur[1]); ops.mul(R_W, slot[j][0])      # Z_k X_j
+                        eng.sub_reg(R_T, R_W)
+                        ops.prep(R_T, R_T)
+                        ops.mul(R_A, R_T)
+                    if k + 1 < k1:
+                        if k == 0:
+                            cv.dbl(spare, DQ)        # the difference would be 0 Q
+                        else:
+                            cv.add(spare, nxt, DQ, cur)
+                        cur, nxt, spare = nxt, spare, cur
+                    else:
+                        cur, nxt = nxt, cur
             for l, acc in enumerate(get(R_A)):
                 if not failed[l] and g1[l] != mp:   # (a curve whose stage 1 gave Mp itself has no stage 2)
                     g = mp if acc == 0 else big_gcd(acc, mp, use_gmp)
@@ -351,15 +365,16 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane):
     return results(g1, g2)
 
 
-def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None):
+def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None, batch=False):
     """One curve of ECM on 2^p - 1 with bounds B1 and B2 (B2 <= B1: stage 1 only) on `eng`, an engine for exponent p with at least
     FIXED_REGISTERS registers (stage 1) or registers_needed(D) (stage 2).  use_fused=False forces set_multiplicand + square_mul in
-    place of square_mul_prepare.  Afterwards registers R_XQ, R_ZQ hold the stage-1 point.
+    place of square_mul_prepare.  Afterwards registers R_XQ, R_ZQ hold the stage-1 point.  batch=True: the ladder and the stage-2 loops
+    run inside eng.batch() (an engine with one-launch products); the result then has "launches", the batch launches it took.
     -> {p, b1, b2, D, sigma, factors, g1, g2, squarings, products, prepares, fused}"""
-    return _run_curves(eng, p, b1, b2, [sigma], D, use_fused, use_gmp, False)[0]
+    return _run_curves(eng, p, b1, b2, [sigma], D, use_fused, use_gmp, False, batch)[0]
 
 
-def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None):
+def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None, batch=False):
     """len(sigmas) == eng.lanes curves at once on an engine with lanes (Engine(..., lanes=B)), curve l in lane l: the engine calls of ONE
     run(), each of which acts on every lane.  x0 and a24 are written lane by lane, the stage-1 Z and the stage-2 accumulator read back
     and gcd'd lane by lane.  A curve whose inversion fails reports that factor as run() does; its lane carries a valid curve whose
@@ -368,20 +383,23 @@ def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None):
     sigmas = list(sigmas)
     if len(sigmas) != getattr(eng, "lanes", 1) or not sigmas:
         raise ValueError("run_lanes needs one sigma per lane: %d given, the engine has %d lanes" % (len(sigmas), getattr(eng, "lanes", 1)))
-    return _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, True)
+    return _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, True, batch)
 
 
-def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0, lanes=1, onelaunch=False):
+def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0, lanes=1, onelaunch=False, batch=False):
     """`curves` curves of run() on a fresh prmers_amd.Engine sized for the chosen D, until one finds a factor.  sigma: the first curve's
     (None: drawn like the others, from random.Random(seed)).  -> the result of the last curve run, with "sigmas": every sigma used.
     lanes = B > 1: the curves run B at a time through run_lanes() on one engine with B lanes (whole batches: `curves` rounded up to a
     multiple of B), sigmas drawn from the same generator in the same order, until a batch in which some lane finds a factor.  -> the
     result of that batch's first curve with a factor (of the last curve run when there is none), "factors": those of all its lanes,
     "sigmas": every sigma of every batch run, "batch": the last batch's results, one per lane.
-    onelaunch: the engine is created with the plan token of that name (every product one launch; p <= 204799)."""
+    onelaunch: the engine is created with the plan token of that name (every product one launch; p <= 204799).
+    batch: run() / run_lanes() with batch=True; needs onelaunch (or the token in `plan`) and implies nothing."""
     from .engine import Engine, resolve_plan
     if lanes < 1:
         raise ValueError("lanes must be at least 1")
+    if batch and not (onelaunch or "onelaunch" in (plan or "")):
+        raise ValueError("batch needs an engine with one-launch products: say onelaunch=True (--onelaunch) as well")
     if onelaunch:
         plan = (plan + "," if plan else "") + "onelaunch"
     if b2 > b1 and D is None:
@@ -399,17 +417,17 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
     if lanes == 1:
         with Engine(p, regs, device=device, plan=plan) as eng:
             for c in range(max(1, curves)):
-                res = run(eng, p, b1, b2, draw(), D)
+                res = run(eng, p, b1, b2, draw(), D, batch=batch)
                 if res["factors"]:
                     break
     else:
         with Engine(p, regs, device=device, plan=plan, lanes=lanes) as eng:
             for c in range(0, max(1, curves), lanes):
-                batch = run_lanes(eng, p, b1, b2, [draw() for _ in range(lanes)], D)
-                found = [r for r in batch if r["factors"]]
-                res = dict(found[0] if found else batch[-1])
-                res["factors"] = sorted({f for r in batch for f in r["factors"]})
-                res["batch"] = batch
+                out = run_lanes(eng, p, b1, b2, [draw() for _ in range(lanes)], D, batch=batch)
+                found = [r for r in out if r["factors"]]
+                res = dict(found[0] if found else out[-1])
+                res["factors"] = sorted({f for r in out for f in r["factors"]})
+                res["batch"] = out
                 if found:
                     break
     res["sigmas"] = sigmas
@@ -430,8 +448,10 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--lanes", type=int, default=1, help="curves per batch: an engine with this many lanes runs them in one launch sequence")
     ap.add_argument("--onelaunch", action="store_true", help="plan token onelaunch: every product of the engine is one launch (p <= 204799)")
+    ap.add_argument("--batch", action="store_true", help="the ladder and the stage-2 loops as batches, one launch for a run of operations (needs --onelaunch)")
     a = ap.parse_args(argv)
-    res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed, a.lanes, a.onelaunch)
+    res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed, a.lanes, a.onelaunch,
+              **({"batch": True} if a.batch else {}))
     print(json.dumps(res))
     return 0 if res["factors"] else 1
 

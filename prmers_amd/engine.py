@@ -6,6 +6,7 @@ sub_reg / get_mpz / set_mpz / digit / checkpoint), same names, same argument mea
 as EngineError where the reference throws std::runtime_error.  There is no CPU fallback: without the
 built HIP library or without a GPU, construction fails.
 """
+import contextlib
 import ctypes as C
 import operator
 import os
@@ -93,10 +94,14 @@ def load_library():
         "mi355_lanes_set_words": (C.c_int, [vp, sz, sz, vp, sz]),
         "mi355_lanes_get_words": (C.c_int, [vp, sz, sz, vp, sz]),
         "mi355_lanes_res64": (C.c_int, [vp, sz, sz, u64p]),
+        # include/mi355_batch.h
+        "mi355_batch_begin": (C.c_int, [vp]),
+        "mi355_batch_end": (C.c_int, [vp]),
+        "mi355_batch_stats": (C.c_int, [vp, u64p]),
     }
     for name, (res, args) in sig.items():
-        if name in LANE_EXPORTS and os.environ.get("MI355_ENGINE_LIB") and not hasattr(L, name):
-            continue           # an A/B library from before the lanes (tools/time_lanes.py): plain engines only, Engine.lanes reads 1
+        if name in LANE_EXPORTS + BATCH_EXPORTS and os.environ.get("MI355_ENGINE_LIB") and not hasattr(L, name):
+            continue           # an A/B library from before the lanes or the batches (tools/time_lanes.py): Engine.lanes reads 1, batch() raises
         f = getattr(L, name)   # AttributeError here = the library does not export what the header declares
         f.restype, f.argtypes = res, args
     _lib = L
@@ -123,6 +128,10 @@ EXPORTS = [
 
 # include/mi355_lanes.h: per-lane I/O of engines created with the plan token lanes=B
 LANE_EXPORTS = ["mi355_lanes_count", "mi355_lanes_set_words", "mi355_lanes_get_words", "mi355_lanes_res64"]
+
+
+# include/mi355_batch.h: a run of register operations of a one-launch engine as one launch
+BATCH_EXPORTS = ["mi355_batch_begin", "mi355_batch_end", "mi355_batch_stats"]
 
 
 def resolve_plan(p, spec=None):
@@ -254,6 +263,35 @@ class Engine:
     def square_mul_prepare_is_fused(self):
         """True if square_mul_prepare runs as one squaring (False: set_multiplicand + square_mul, same result)"""
         return bool(self.L.mi355_engine_square_mul_prepare_is_fused(self.h))
+
+    # --- batches (include/mi355_batch.h): engines made with onelaunch=True ---
+    def _batch_fn(self, name):
+        f = getattr(self.L, name, None)
+        if f is None:
+            raise EngineError("batch: %s does not export %s (a library from before the batches)" % (LIB_PATH, name))
+        return f
+
+    @contextlib.contextmanager
+    def batch(self):
+        """with e.batch(): the copies, sums and differences and one-launch products issued inside are queued and run as ONE launch, in
+        order, with the results of the same calls issued one by one.  Anything else (sub, set, a read, sync, a factor above the fused
+        bound) runs the queue first and then itself; a full queue runs by itself.  The batch ends on an exception too."""
+        begin, end = self._batch_fn("mi355_batch_begin"), self._batch_fn("mi355_batch_end")
+        self._ok(begin(self.h))
+        try:
+            yield self
+        except BaseException:
+            if getattr(self, "h", None):
+                end(self.h)              # the first error is the one to report
+            raise
+        else:
+            self._ok(end(self.h))
+
+    def batch_stats(self):
+        """(operations queued so far, batch launches so far, capacity of the queue, operations pending now)"""
+        out = (C.c_uint64 * 4)()
+        self._ok(self._batch_fn("mi355_batch_stats")(self.h, out))
+        return tuple(int(v) for v in out)
 
     def is_equal(self, lhs, rhs):
         out = C.c_int(0)

@@ -1,13 +1,14 @@
 """Ladder throughput of engines with lanes (needs an MI355X); one JSON line per lane count.
 
-  python tools/time_lanes.py P B1 [--lanes 1,8,64,512] [--rounds 3] [--plan SPEC] [--baseline-lib PATH]
+  python tools/time_lanes.py P B1 [--lanes 1,8,64,512] [--rounds 3] [--plan SPEC] [--batch] [--baseline-lib PATH]
 
 The metric is Montgomery-ladder steps per second, summed over lanes: the stage-1 ladder of ECM with bound B1 (ecm._Curve.ladder_step
 over the bits of ecm.stage1_exponent(B1)) on an engine with B lanes does B curves' steps per call.  The baseline is a plain Engine --
 from the library at --baseline-lib (a build of the parent commit, loaded through MI355_ENGINE_LIB) when given, else from this build.
 Every measurement is a fresh child process (one engine, warm-up, timed ladders, host clock between two syncs); the rounds alternate
 baseline, B1, B2, ... so that every lane count is measured next to the baseline in time.  The figure reported per lane count is the
-median over the rounds, and its ratio to the baseline's median."""
+median over the rounds, and its ratio to the baseline's median.  --batch (with --plan onelaunch): every timed ladder runs inside
+Engine.batch(), a run of register operations per launch (include/mi355_batch.h); the baseline stays what it is."""
 import argparse
 import json
 import os
@@ -21,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def child(p, b1, lanes, plan, min_seconds):
+def child(p, b1, lanes, plan, min_seconds, batch=False):
     from prmers_amd import Engine, ecm
     import prmers_amd
     bits = ecm.stage1_exponent(b1).bit_length() - 1
@@ -34,12 +35,19 @@ def child(p, b1, lanes, plan, min_seconds):
         ops.prep(ecm.R_A24, ecm.R_A24); ops.prep(ecm.R_X0, ecm.R_X0)
         a, b = (ecm.R_XA, ecm.R_ZA), (ecm.R_XB, ecm.R_ZB)
 
-        def ladder():
+        def steps_of_a_ladder():
             for i in range(bits):
                 if i & 1:
                     cv.ladder_step(b, a)
                 else:
                     cv.ladder_step(a, b)
+
+        def ladder():
+            if batch:
+                with e.batch():
+                    steps_of_a_ladder()
+            else:
+                steps_of_a_ladder()
         ladder(); e.sync()                                # code objects, clocks
         steps, t0 = 0, time.perf_counter()
         while True:
@@ -50,10 +58,10 @@ def child(p, b1, lanes, plan, min_seconds):
                 break
         print(json.dumps({"p": p, "b1": b1, "lanes": lanes, "plan": e.describe(), "fused": ops.fused, "steps_per_ladder": bits,
                           "steps": steps, "seconds": round(dt, 4), "lane_steps_per_s": round(steps * lanes / dt, 1),
-                          "lib": prmers_amd.LIB_PATH}))
+                          "lib": prmers_amd.LIB_PATH, **({"batch": True, "launches": e.batch_stats()[1]} if batch else {})}))
 
 
-def measure(p, b1, lanes, plan, min_seconds, lib):
+def measure(p, b1, lanes, plan, min_seconds, lib, batch=False):
     env = dict(os.environ)
     env.pop("MI355_ENGINE_LIB", None)
     if lib:
@@ -61,6 +69,8 @@ def measure(p, b1, lanes, plan, min_seconds, lib):
     cmd = [sys.executable, os.path.abspath(__file__), str(p), str(b1), "--child", str(lanes), "--min-seconds", str(min_seconds)]
     if plan:
         cmd += ["--plan", plan]
+    if batch:
+        cmd += ["--batch"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     if out.returncode != 0:
         return {"lanes": lanes, "error": (out.stderr.strip().splitlines() or ["exit %d" % out.returncode])[-1]}
@@ -75,18 +85,19 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--plan", default=None)
     ap.add_argument("--baseline-lib", default=None, help="libmi355_engine.so of the parent commit (default: this build, without lanes)")
+    ap.add_argument("--batch", action="store_true", help="the timed ladders run inside Engine.batch() (needs --plan onelaunch); never the baseline")
     ap.add_argument("--min-seconds", type=float, default=0.5)
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
     if a.child is not None:
-        child(a.p, a.b1, a.child, a.plan, a.min_seconds)
+        child(a.p, a.b1, a.child, a.plan, a.min_seconds, a.batch)
         return 0
     lane_counts = [int(x) for x in a.lanes.split(",")]
     runs = {"baseline": []}
     runs.update({b: [] for b in lane_counts})
     for _ in range(a.rounds):
         for key, b, lib in [("baseline", 1, a.baseline_lib)] + [(b, b, None) for b in lane_counts]:
-            runs[key].append(measure(a.p, a.b1, b, a.plan, a.min_seconds, lib))
+            runs[key].append(measure(a.p, a.b1, b, a.plan, a.min_seconds, lib, a.batch and key != "baseline"))
             if "error" in runs[key][-1]:                 # a fault or a refusal ends the session: nothing more is started on the device
                 print(json.dumps(runs[key][-1]))
                 return 1
