@@ -13,6 +13,12 @@
 //   k_apply       resolves the chain inside each block
 // Widths are recomputed from ceil(p j / n) (ibdwt.h:127-132), no table.  HBM-bound, ~6 sweeps of 4n bytes: a Gerbicz
 // check moves a few words over PCIe instead of two registers.
+//
+// Lanes: every kernel of the pipeline, k_compare and k_pack_words take the lane from blockIdx.y and move their pointers, which are those
+// of lane 0, to it.  Lane strides: the input register `in_stride` digits (an engine with lanes: 8n bytes), every natural-order array n
+// digits, the block aggregates and block carries one word per block of the lane, the flags kFlagWords words, the packed words wc words.
+// The one-lane launchers launch grid.y = 1, where all of this is lane 0 as before; canon_launch_lanes and its companions launch a chunk
+// of lanes at once (an engine's lane-wise equal and get_words: engine.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -20,6 +26,8 @@
 
 namespace mi355 {
 namespace {
+
+constexpr uint32_t kFlagWords = 16;   // flag words of a lane
 
 __device__ __forceinline__ uint64_t ceil_pj_n(const CanonGeom& g, uint64_t j) {
   const uint64_t x = uint64_t(g.p) * j + (g.n - 1);
@@ -39,8 +47,9 @@ __device__ __forceinline__ size_t pos_of(const CanonGeom& g, uint32_t j) {
 
 // T: digit type, uint32_t (Goldilocks engine, widths < 32) or uint64_t (the GF(M61^2) x GF(M31^2) engine: widths up to 39 bits)
 template <class T>
-__global__ void __launch_bounds__(256) k_gather(CanonGeom g, const T* __restrict__ digits, T* __restrict__ nat) {
+__global__ void __launch_bounds__(256) k_gather(CanonGeom g, const T* __restrict__ digits, size_t in_stride, T* __restrict__ nat) {
   const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+  digits += size_t(blockIdx.y) * in_stride; nat += size_t(blockIdx.y) * g.n;
   if (j < g.n) nat[j] = digits[pos_of(g, j)];
 }
 
@@ -48,6 +57,7 @@ template <class T>
 __global__ void __launch_bounds__(256) k_local(CanonGeom g, const T* __restrict__ in, T* __restrict__ out) {
   const uint32_t j = blockIdx.x * 256 + threadIdx.x;
   if (j >= g.n) return;
+  in += size_t(blockIdx.y) * g.n; out += size_t(blockIdx.y) * g.n;
   const uint32_t jp = j ? j - 1 : g.n - 1;
   const uint64_t o0 = ceil_pj_n(g, jp), o1 = ceil_pj_n(g, uint64_t(jp) + 1), o2 = ceil_pj_n(g, uint64_t(j) + 1);
   const uint32_t wp = uint32_t(o1 - o0);
@@ -62,6 +72,7 @@ template <class T>
 __global__ void __launch_bounds__(256) k_scan_blocks(CanonGeom g, const T* __restrict__ nat, uint32_t* __restrict__ agg, uint32_t* __restrict__ err) {
   __shared__ uint32_t sg[256], sp[256];
   const uint32_t t = threadIdx.x, j0 = blockIdx.x * kBlockDigits + t * kPerThread;
+  nat += size_t(blockIdx.y) * g.n; agg += size_t(blockIdx.y) * gridDim.x; err += size_t(blockIdx.y) * kFlagWords;
   uint32_t G = 0, Pm = 1;
   uint64_t o = (j0 < g.n) ? ceil_pj_n(g, j0) : 0;
   for (int k = 0; k < kPerThread; ++k) {
@@ -91,6 +102,7 @@ __global__ void __launch_bounds__(256) k_scan_blocks(CanonGeom g, const T* __res
 __global__ void __launch_bounds__(256) k_scan_top(const uint32_t* __restrict__ agg, uint32_t nblocks, uint32_t* __restrict__ cin, uint32_t* __restrict__ flags) {
   __shared__ uint32_t sg[256], sp[256], sc[256];
   if (blockIdx.x != 0) return;
+  agg += size_t(blockIdx.y) * nblocks; cin += size_t(blockIdx.y) * nblocks; flags += size_t(blockIdx.y) * kFlagWords;
   const uint32_t t = threadIdx.x, per = (nblocks + 255) / 256;
   const uint32_t b0 = t * per, b1 = min(b0 + per, nblocks);
   uint32_t G = 0, Pm = 1;
@@ -114,6 +126,8 @@ __global__ void __launch_bounds__(256) k_apply(CanonGeom g, const T* __restrict_
                                                T* __restrict__ out) {
   __shared__ uint32_t sg[256], sp[256], sc[256];
   const uint32_t t = threadIdx.x, j0 = blockIdx.x * kBlockDigits + t * kPerThread;
+  nat += size_t(blockIdx.y) * g.n; out += size_t(blockIdx.y) * g.n;
+  cin += size_t(blockIdx.y) * gridDim.x; flags += size_t(blockIdx.y) * kFlagWords;
   T v[kPerThread];
   uint32_t w[kPerThread];
   uint32_t G = 0, Pm = 1;
@@ -195,6 +209,7 @@ __global__ void k_set_small(CanonGeom g, uint32_t* __restrict__ digits, uint32_t
 template <class T>
 __global__ void __launch_bounds__(256) k_compare(const T* __restrict__ a, const T* __restrict__ b, uint32_t n, uint32_t* __restrict__ diff) {
   const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+  a += size_t(blockIdx.y) * n; b += size_t(blockIdx.y) * n; diff += size_t(blockIdx.y) * kFlagWords;
   const bool ne = (j < n) && (a[j] != b[j]);
   if (__any(ne) && (threadIdx.x & 63) == 0) atomicOr(diff, 1u);
 }
@@ -221,6 +236,7 @@ template <class T>
 __global__ void __launch_bounds__(256) k_pack_words(CanonGeom g, const T* __restrict__ nat, uint32_t* __restrict__ words, uint32_t wc) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= wc) return;
+  nat += size_t(blockIdx.y) * g.n; words += size_t(blockIdx.y) * wc;
   const uint64_t b0 = uint64_t(i) * 32, b1 = b0 + 32;
   uint64_t k = (b0 * g.n) / g.p;          // 32 i < p: k < n
   uint64_t o = ceil_pj_n(g, k);
@@ -252,17 +268,18 @@ __global__ void __launch_bounds__(256) k_unpack_words(CanonGeom g, const uint32_
 
 // the whole pipeline on an array in natural order or tile-major order (g.M1)
 template <class T>
-void launch_pipeline(const CanonGeom& g, const T* digits, T* out, T* A, T* B, uint32_t* agg, uint32_t* cin, uint32_t* flags, hipStream_t s) {
+void launch_pipeline(const CanonGeom& g, const T* digits, size_t in_stride, uint32_t lanes, T* out, T* A, T* B, uint32_t* agg, uint32_t* cin,
+                     uint32_t* flags, hipStream_t s) {
   const uint32_t n = g.n, nb = (n + kBlockDigits - 1) / kBlockDigits, ge = (n + 255) / 256;
-  const T* first = digits;
-  if (g.M1 != 0) { hipLaunchKernelGGL(k_gather<T>, dim3(ge), dim3(256), 0, s, g, digits, A); first = A; }
+  const T* first = digits;   // (a register in natural order is read where it lies: one lane only, whose stride is never used)
+  if (g.M1 != 0) { hipLaunchKernelGGL(k_gather<T>, dim3(ge, lanes), dim3(256), 0, s, g, digits, in_stride, A); first = A; }
   CanonGeom gn = g; gn.M1 = 0;   // from here on everything is in natural order
-  hipLaunchKernelGGL(k_local<T>, dim3(ge), dim3(256), 0, s, gn, first, B);
-  hipLaunchKernelGGL(k_local<T>, dim3(ge), dim3(256), 0, s, gn, B, A);
-  hipLaunchKernelGGL(k_local<T>, dim3(ge), dim3(256), 0, s, gn, A, B);
-  hipLaunchKernelGGL(k_scan_blocks<T>, dim3(nb), dim3(256), 0, s, gn, B, agg, flags + 1);
-  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, agg, nb, cin, flags);
-  hipLaunchKernelGGL(k_apply<T>, dim3(nb), dim3(256), 0, s, gn, B, cin, flags, out);
+  hipLaunchKernelGGL(k_local<T>, dim3(ge, lanes), dim3(256), 0, s, gn, first, B);
+  hipLaunchKernelGGL(k_local<T>, dim3(ge, lanes), dim3(256), 0, s, gn, B, A);
+  hipLaunchKernelGGL(k_local<T>, dim3(ge, lanes), dim3(256), 0, s, gn, A, B);
+  hipLaunchKernelGGL(k_scan_blocks<T>, dim3(nb, lanes), dim3(256), 0, s, gn, B, agg, flags + 1);
+  hipLaunchKernelGGL(k_scan_top, dim3(1, lanes), dim3(256), 0, s, agg, nb, cin, flags);
+  hipLaunchKernelGGL(k_apply<T>, dim3(nb, lanes), dim3(256), 0, s, gn, B, cin, flags, out);
 }
 
 constexpr size_t blocks_of(uint32_t n) { return (size_t(n) + kBlockDigits - 1) / kBlockDigits; }
@@ -291,7 +308,7 @@ template <class T> hipError_t canon_launch(const CanonGeom& g, const T* digits, 
   T* A = static_cast<T*>(scratch);
   uint32_t* agg = reinterpret_cast<uint32_t*>(A + 2 * size_t(g.n));
   const size_t nb = blocks_of(g.n);
-  launch_pipeline<T>(g, digits, out, A, A + g.n, agg, agg + nb, agg + 2 * nb, s);
+  launch_pipeline<T>(g, digits, 0, 1, out, A, A + g.n, agg, agg + nb, agg + 2 * nb, s);
   return hipGetLastError();
 }
 template <class T> hipError_t canon_compare(const T* a, const T* b, uint32_t n, uint32_t* diff_flag, hipStream_t s) {
@@ -318,6 +335,46 @@ template <class T> hipError_t canon_unpack_words(const CanonGeom& g, const uint3
 MI355_CANON_FOR(uint32_t)
 MI355_CANON_FOR(uint64_t)
 #undef MI355_CANON_FOR
+
+// ---- a chunk of lanes at once (tile-major u32 registers: the engines that have lanes) ----
+// Scratch of a chunk of L lanes: work arrays A and B, outputs 0 and 1 (L x n digits each), L x nb aggregates, L x nb carries, L x 16 flags.
+size_t canon_lane_bytes(size_t n) { return 4 * n * 4 + (2 * blocks_of(uint32_t(n)) + kFlagWords) * 4; }
+size_t canon_chunk_lanes(size_t n, size_t lanes) {
+  const size_t fit = kCanonLanesScratchBytes / canon_lane_bytes(n);
+  return fit < 1 ? 1 : (fit < lanes ? fit : lanes);
+}
+namespace {
+struct LaneScratch { uint32_t *A, *B, *out[2], *agg, *cin, *flags; };
+LaneScratch lane_scratch(const CanonGeom& g, void* scratch, size_t L) {
+  LaneScratch s;
+  const size_t n = g.n, nb = blocks_of(g.n);
+  s.A = static_cast<uint32_t*>(scratch); s.B = s.A + L * n; s.out[0] = s.B + L * n; s.out[1] = s.out[0] + L * n;
+  s.agg = s.out[1] + L * n; s.cin = s.agg + L * nb; s.flags = s.cin + L * nb;
+  return s;
+}
+}  // namespace
+uint32_t* canon_lanes_flags(const CanonGeom& g, void* scratch, size_t L) { return lane_scratch(g, scratch, L).flags; }
+hipError_t canon_launch_lanes(const CanonGeom& g, const uint32_t* digits, size_t in_stride, size_t L, int slot, void* scratch, hipStream_t s) {
+  if (g.M1 == 0 || L == 0 || L > 65535) return hipErrorInvalidValue;
+  const LaneScratch w = lane_scratch(g, scratch, L);
+  launch_pipeline<uint32_t>(g, digits, in_stride, uint32_t(L), w.out[slot & 1], w.A, w.B, w.agg, w.cin, w.flags, s);
+  return hipGetLastError();
+}
+hipError_t canon_compare_lanes(const CanonGeom& g, size_t L, void* scratch, hipStream_t s) {
+  if (L == 0 || L > 65535) return hipErrorInvalidValue;
+  const LaneScratch w = lane_scratch(g, scratch, L);
+  hipLaunchKernelGGL(k_compare<uint32_t>, dim3((g.n + 255) / 256, uint32_t(L)), dim3(256), 0, s, w.out[0], w.out[1], g.n, w.flags + 2);
+  return hipGetLastError();
+}
+hipError_t canon_pack_words_lanes(const CanonGeom& g, size_t L, int slot, void* scratch, uint32_t** words, hipStream_t s) {
+  if (L == 0 || L > 65535) return hipErrorInvalidValue;
+  const LaneScratch w = lane_scratch(g, scratch, L);
+  CanonGeom gn = g; gn.M1 = 0;
+  const uint32_t wc = word_count_of(g);   // wc <= n: the words of L lanes fit the first work array
+  hipLaunchKernelGGL(k_pack_words<uint32_t>, dim3((wc + 255) / 256, uint32_t(L)), dim3(256), 0, s, gn, w.out[slot & 1], w.A, wc);
+  *words = w.A;
+  return hipGetLastError();
+}
 
 hipError_t canon_local_pass(const CanonGeom& g, const uint64_t* in, uint64_t* out, hipStream_t s) {
   hipLaunchKernelGGL(k_local<uint64_t>, dim3((g.n + 255) / 256), dim3(256), 0, s, g, in, out);

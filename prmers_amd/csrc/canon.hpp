@@ -28,6 +28,19 @@ template <class T> hipError_t canon_compare(const T* a, const T* b, uint32_t n, 
 template <class T> hipError_t canon_pack_words(const CanonGeom& g, const T* canon, uint32_t* words, hipStream_t s);
 // words: ceil(p / 32) words of a value below 2^p -> the digits of a register in the geometry's layout
 template <class T> hipError_t canon_unpack_words(const CanonGeom& g, const uint32_t* words, T* digits, hipStream_t s);
+
+// ---- a chunk of lanes in one launch sequence (tile-major uint32_t registers; lane l of the register lies in_stride digits behind lane 0) ----
+// The scratch of the lane-wise pipeline is bounded: an engine with more lanes than canon_chunk_lanes takes them chunk by chunk.
+constexpr size_t kCanonLanesScratchBytes = size_t(64) << 20;
+size_t canon_lane_bytes(size_t n);                    // scratch of one lane: four arrays of n digits, block aggregates, block carries, 16 flag words
+size_t canon_chunk_lanes(size_t n, size_t lanes);     // lanes per chunk: as many as fit kCanonLanesScratchBytes, at least 1, at most `lanes`
+// scratch: L * canon_lane_bytes(n); canonical digits go to output slot 0 or 1 of the scratch.  flags: 16 words a lane, [0] [1] [2] as above (the caller clears them)
+uint32_t* canon_lanes_flags(const CanonGeom& g, void* scratch, size_t L);
+hipError_t canon_launch_lanes(const CanonGeom& g, const uint32_t* digits, size_t in_stride, size_t L, int slot, void* scratch, hipStream_t s);
+hipError_t canon_compare_lanes(const CanonGeom& g, size_t L, void* scratch, hipStream_t s);   // slot 0 against slot 1 -> flag [2] of each lane
+// slot's canonical digits -> ceil(p / 32) words a lane, lane after lane, in *words (inside the scratch: the work arrays are free by then)
+hipError_t canon_pack_words_lanes(const CanonGeom& g, size_t L, int slot, void* scratch, uint32_t** words, hipStream_t s);
+
 // natural order only (uint64_t): one local carry pass in -> out (digits of up to w + e bits come out below 2^w + 2^e), and
 // dst += the digit-wise complement of a canonical residue, i.e. dst - canon mod 2^p - 1
 hipError_t canon_local_pass(const CanonGeom& g, const uint64_t* in, uint64_t* out, hipStream_t s);

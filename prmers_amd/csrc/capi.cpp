@@ -3,6 +3,7 @@
 #include "../../include/mi355_engine.h"
 #include "../../include/mi355_lanes.h"
 #include "../../include/mi355_batch.h"
+#include "../../include/mi355_lanewise.h"
 
 #include <cctype>
 #include <cstring>
@@ -233,6 +234,15 @@ int mi355_lanes_get_words(mi355_engine_handle h, size_t lane, size_t src, uint32
 int mi355_lanes_res64(mi355_engine_handle h, size_t lane, size_t src, uint64_t* out) {
   return guarded([&] { if (!out) throw std::runtime_error("res64: null output"); *out = m(h)->res64_lane(lane, src); });
 }
+// ---- include/mi355_lanewise.h ----
+int mi355_lanewise_equal(mi355_engine_handle h, size_t lhs, size_t rhs, uint8_t* out, size_t count) {
+  return guarded([&] { if (!out) throw std::runtime_error("lanewise_equal: null output"); m(h)->equal_lanes(lhs, rhs, out, count); });
+}
+int mi355_lanewise_get_words(mi355_engine_handle h, size_t src, uint32_t* w, size_t count) {
+  return guarded([&] { if (!w) throw std::runtime_error("lanewise_get_words: null buffer"); m(h)->get_words_lanes(src, w, count); });
+}
+size_t mi355_lanewise_chunk_lanes(size_t n, size_t lanes) { return mi355::canon_chunk_lanes(n, lanes); }
+
 // ---- include/mi355_batch.h ----
 int mi355_batch_begin(mi355_engine_handle h) { return guarded([&] { m(h)->batch_begin(); }); }
 int mi355_batch_end(mi355_engine_handle h) { return guarded([&] { m(h)->batch_end(); }); }

@@ -183,6 +183,7 @@ Engine::~Engine() {
   if (f0_) (void)hipFree(f0_);
   if (split_) (void)hipFree(split_);
   if (canon_) (void)hipFree(canon_);
+  if (canon_lanes_) (void)hipFree(canon_lanes_);
   for (int h = 0; h < 2; ++h) {   // (what a batch still had queued is dropped: nothing of it was launched)
     if (batch_read_[h]) (void)hipEventDestroy(batch_read_[h]);
     if (batch_stage_[h]) (void)hipHostFree(batch_stage_[h]);
@@ -475,6 +476,79 @@ bool Engine::equal(size_t lhs, size_t rhs) {
     if (canon_flags_ok(flags)) return flags[2] == 0;
   }
   return equal_words(lhs, rhs);
+}
+
+// ---- every lane at once (include/mi355_lanewise.h) -------------------------------------------
+// The pipeline of canon.hip with the lanes as grid.y: a chunk of lanes (canon_chunk_lanes: the scratch stays within
+// kCanonLanesScratchBytes) is one launch sequence and one read of its flag words, where lane by lane it is seven launches and a
+// synchronising read for each.  Pending run carries are folded in first, for all lanes in one launch (normalize).
+
+void* Engine::lanes_scratch(size_t chunk) {
+  if (!canon_lanes_) {   // the chunk size is a function of the engine's n and lane count: one size for good
+    HIPCHK(hipMalloc(&canon_lanes_, chunk * canon_lane_bytes(pl_.n)));
+    canon_lanes_chunk_ = chunk;
+  }
+  if (chunk > canon_lanes_chunk_) throw std::runtime_error("internal: lane-wise scratch made for " + std::to_string(canon_lanes_chunk_) + " lanes, asked for " + std::to_string(chunk));
+  lane_flags_.resize(chunk * 16);
+  return canon_lanes_;
+}
+
+void Engine::words_host(size_t src, size_t lane, uint32_t* w) {
+  std::vector<uint64_t> v;
+  read_values_host(src, v, lane);
+  host_digits::pack_words(v.data(), width_, w, word_count());
+}
+
+void Engine::equal_lanes(size_t lhs, size_t rhs, uint8_t* out, size_t count) {
+  if (lanes_ == 1) { RegisterMachine::equal_lanes(lhs, rhs, out, count); return; }
+  if (count != lanes_) throw std::runtime_error("lanewise_equal: count must equal the lane count (" + std::to_string(lanes_) + ")");
+  need_residue(lhs, "lanewise_equal"); need_residue(rhs, "lanewise_equal");
+  HIPCHK(hipSetDevice(device_));
+  std::vector<uint32_t> a(word_count()), b(word_count());
+  auto on_host = [&](size_t l) { words_host(lhs, l, a.data()); words_host(rhs, l, b.data()); out[l] = a == b ? 1 : 0; };
+  if (host_carry_) { for (size_t l = 0; l < lanes_; ++l) on_host(l); return; }
+  normalize(lhs); normalize(rhs);
+  const size_t chunk = canon_chunk_lanes(pl_.n, lanes_), stride = reg_bytes_ / 4;
+  void* scratch = lanes_scratch(chunk);
+  for (size_t l0 = 0; l0 < lanes_; l0 += chunk) {
+    const size_t L = std::min(chunk, lanes_ - l0);
+    uint32_t* df = canon_lanes_flags(cg_, scratch, L);
+    HIPCHK(hipMemsetAsync(df, 0, L * 16 * 4, stream()));
+    HIPCHK(canon_launch_lanes(cg_, digits(lhs, l0), stride, L, 0, scratch, stream()));
+    HIPCHK(canon_launch_lanes(cg_, digits(rhs, l0), stride, L, 1, scratch, stream()));
+    HIPCHK(canon_compare_lanes(cg_, L, scratch, stream()));
+    HIPCHK(hipMemcpyAsync(lane_flags_.data(), df, L * 16 * 4, hipMemcpyDeviceToHost, stream()));
+    HIPCHK(hipStreamSynchronize(stream()));
+    for (size_t l = 0; l < L; ++l) {
+      if (lane_flags_[l * 16 + 1]) on_host(l0 + l);   // a digit was too wide for the 0/1 chain: this lane through the host carry
+      else out[l0 + l] = lane_flags_[l * 16 + 2] == 0 ? 1 : 0;
+    }
+  }
+}
+
+void Engine::get_words_lanes(size_t src, uint32_t* w, size_t count) {
+  if (lanes_ == 1) { RegisterMachine::get_words_lanes(src, w, count); return; }
+  const size_t wc = word_count();
+  if (count != lanes_ * wc) throw std::runtime_error("lanewise_get_words: count must equal lanes x word_count()");
+  need_residue(src, "lanewise_get_words");
+  HIPCHK(hipSetDevice(device_));
+  if (host_carry_) { for (size_t l = 0; l < lanes_; ++l) words_host(src, l, w + l * wc); return; }
+  normalize(src);
+  const size_t chunk = canon_chunk_lanes(pl_.n, lanes_), stride = reg_bytes_ / 4;
+  void* scratch = lanes_scratch(chunk);
+  for (size_t l0 = 0; l0 < lanes_; l0 += chunk) {
+    const size_t L = std::min(chunk, lanes_ - l0);
+    uint32_t* df = canon_lanes_flags(cg_, scratch, L);
+    uint32_t* dw = nullptr;
+    HIPCHK(hipMemsetAsync(df, 0, L * 16 * 4, stream()));
+    HIPCHK(canon_launch_lanes(cg_, digits(src, l0), stride, L, 0, scratch, stream()));
+    HIPCHK(canon_pack_words_lanes(cg_, L, 0, scratch, &dw, stream()));
+    HIPCHK(hipMemcpyAsync(w + l0 * wc, dw, L * wc * 4, hipMemcpyDeviceToHost, stream()));
+    HIPCHK(hipMemcpyAsync(lane_flags_.data(), df, L * 16 * 4, hipMemcpyDeviceToHost, stream()));
+    HIPCHK(hipStreamSynchronize(stream()));
+    for (size_t l = 0; l < L; ++l)
+      if (lane_flags_[l * 16 + 1]) words_host(src, l0 + l, w + (l0 + l) * wc);
+  }
 }
 
 // ---- register operations -------------------------------------------------------------------

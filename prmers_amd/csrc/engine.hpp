@@ -42,6 +42,10 @@ class Engine final : public RegisterMachine {
   void set_words_lane(size_t lane, size_t dst, const uint32_t* w, size_t count) override;
   void get_words_lane(size_t lane, size_t src, uint32_t* w, size_t count) override;
   uint64_t res64_lane(size_t lane, size_t src) override;
+  // every lane in one launch sequence per chunk of lanes (canon.hip canon_launch_lanes); a lane whose chain reports an over-wide digit,
+  // and every lane under MI355_HOST_CARRY=1, goes through the host carry
+  void equal_lanes(size_t lhs, size_t rhs, uint8_t* out, size_t count) override;
+  void get_words_lanes(size_t src, uint32_t* w, size_t count) override;
   void copy(size_t dst, size_t src) override;
   void set_multiplicand(size_t dst, size_t src) override;
   void square_mul(size_t r, uint32_t a) override;
@@ -117,6 +121,8 @@ class Engine final : public RegisterMachine {
   // fold w mod 2^p - 1 where it has bits at or above p, upload it to the work buffer and cut it into the digits of lanes [lane0, lane1) of dst
   void put_words(size_t dst, const uint32_t* w, size_t count, size_t lane0, size_t lane1);
   bool canon_flags_ok(uint32_t (&flags)[4]);    // reads the flag words; false: fall back to the host carry
+  void words_host(size_t src, size_t lane, uint32_t* w);   // the canonical words of one lane through read_values_host
+  void* lanes_scratch(size_t chunk);            // device scratch of the lane-wise pipeline for `chunk` lanes (made at first use)
   void write_values(size_t dst, const std::vector<uint32_t>& natural);
   void square_chain(size_t r, uint32_t a, hipEvent_t* ev);
   uint64_t* cbuf(size_t r) { return cb_[r]; }
@@ -163,6 +169,9 @@ class Engine final : public RegisterMachine {
   std::vector<uint8_t> width_;   // natural order
   std::vector<uint32_t> stage_;  // host staging (one register of digits)
   uint32_t* canon_ = nullptr;    // device scratch of the canonicalisation: work arrays + two outputs of n digits (lazy)
+  void* canon_lanes_ = nullptr;  // the same for a chunk of lanes (canon.hpp canon_chunk_lanes; lazy)
+  size_t canon_lanes_chunk_ = 0; // lanes canon_lanes_ was made for
+  std::vector<uint32_t> lane_flags_;   // host copy of a chunk's flag words
   bool host_carry_ = false;      // MI355_HOST_CARRY=1: compare / res64 / read-back through the host (A/B tests)
   // batches: descriptors are written into one of two pinned halves, go to the device buffer by a copy on the stream and are read there by
   // the launch behind it; a half is written again only after the event recorded behind the launch that read it

@@ -55,6 +55,18 @@ class RegisterMachine {
   virtual void set_words_lane(size_t lane, size_t dst, const uint32_t* w, size_t count) { need_lane(lane, "set_words"); set_words(dst, w, count); }
   virtual void get_words_lane(size_t lane, size_t src, uint32_t* w, size_t count) { need_lane(lane, "get_words"); get_words(src, w, count); }
   virtual uint64_t res64_lane(size_t lane, size_t src) { need_lane(lane, "res64"); return res64(src); }
+  // Every lane at once (include/mi355_lanewise.h): out[l] = lane l of lhs and of rhs are the same value mod 2^p - 1, and the canonical words
+  // of every lane, lane l at l * word_count().  A machine without lanes answers for its one lane through equal / get_words.
+  virtual void equal_lanes(size_t lhs, size_t rhs, uint8_t* out, size_t count) {
+    if (count != lanes()) throw std::runtime_error("lanewise_equal: count must equal the lane count (" + std::to_string(lanes()) + ")");
+    need_residue(lhs, "lanewise_equal"); need_residue(rhs, "lanewise_equal");
+    out[0] = equal(lhs, rhs) ? 1 : 0;
+  }
+  virtual void get_words_lanes(size_t src, uint32_t* w, size_t count) {
+    if (count != lanes() * word_count()) throw std::runtime_error("lanewise_get_words: count must equal lanes x word_count()");
+    need_residue(src, "lanewise_get_words");
+    get_words(src, w, count);
+  }
 
   // Batches (include/mi355_batch.h): the register operations between batch_begin and batch_end run as one launch.  Only the Goldilocks
   // engine with one-launch products has them (engine.hpp); stats: operations queued so far, batch launches so far, capacity, pending now.

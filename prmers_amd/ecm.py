@@ -1,6 +1,7 @@
 """ECM factoring of a Mersenne number 2^p - 1 on the engine: Montgomery curves, stages 1 and 2 (the reference: src/modes/RunEcm.cpp).
 
     python -m prmers_amd.ecm P B1 [B2] [--sigma S] [--curves N] [--lanes B] [--D 30|210|2310] [--plan SPEC] [--onelaunch] [--batch] [--device N]
+                             [--curve montgomery|edwards] [--check-every N]
 
 Curve:    Suyama's parametrisation from sigma: u = sigma^2 - 5, v = 4 sigma, the point (u^3 : v^3) on B y^2 = x^3 + A x^2 + x with
           a24 = (A + 2) / 4 = (v - u)^3 (3 u + v) / (16 u^3 v).  The start is taken affine, x0 = u^3 / v^3 and Z = 1: one modular inversion
@@ -30,8 +31,12 @@ Batches:  on an engine with one-launch products (--onelaunch) every ladder step 
           batch=True / --batch runs the stage-1 ladder and the stage-2 loops inside Engine.batch() (include/mi355_batch.h): the engine
           queues the calls and runs each queue as one launch.  Writes of constants inside those loops run the queue first; the x0, a24
           and start point go in before the first batch and Z, the accumulator and the stage-1 point are read after the last has ended.
-Not here: twisted Edwards curves, PRAC chains,
-checkpoints, ECM= worktodo lines, the PrimeNet JSON, a C++ twin.
+Edwards:  --curve edwards / ecm(curve="edwards") runs stage 1 in twisted Edwards extended coordinates (prmers_amd/ecm_edwards.py), the
+          same group as the Montgomery curve of that sigma, where a X^2 + Y^2 = Z^2 + d T^2 is tested every --check-every NAF digits and
+          at the end, on all lanes at once (Engine.equal_lanes), with a roll-back to the last point that passed.  It costs more sweeps
+          per bit than the ladder: it buys the check, not speed.  Stage 2 is the one below for both (_stage2).  The
+          per-lane reads at the end of a stage go through Engine.get_ints where the object has it: one launch sequence for all lanes.
+Not here: PRAC chains, checkpoints, ECM= worktodo lines, the PrimeNet JSON, a C++ twin.
 """
 import argparse
 import contextlib
@@ -132,6 +137,10 @@ def suyama(sigma, n, use_gmp=None):
 
 # ---- engine operations, with the compositions for objects that lack the fused ones ---------------------------------------------------
 
+def _factor(a):
+    return () if a == 1 else (a,)
+
+
 class _Ops:
     def __init__(self, eng, use_fused=True):
         self.e = eng
@@ -139,26 +148,36 @@ class _Ops:
         self.has_prepare = bool(use_fused and getattr(eng, "square_mul_prepare", None))
         self.fused = bool(self.has_prepare and getattr(eng, "square_mul_prepare_is_fused", lambda: False)())
         self.has_addsub = getattr(eng, "addsub", None) is not None
+        self.has_mul_copy = getattr(eng, "mul_copy", None) is not None
 
-    def sq(self, r):
-        self.e.square_mul(r)
+    # a: the small factor of the engine's products; a call without one is issued without one
+    def sq(self, r, a=1):
+        self.e.square_mul(r, *_factor(a))
         self.squarings += 1
 
-    def mul(self, dst, img):
-        self.e.mul(dst, img)
+    def mul(self, dst, img, a=1):
+        self.e.mul(dst, img, *_factor(a))
+        self.products += 1
+
+    def mul_copy(self, dst, img, dst_copy, a=1):
+        """dst = a dst img, dst_copy = the same"""
+        if self.has_mul_copy:
+            self.e.mul_copy(dst, img, dst_copy, *_factor(a))
+        else:
+            self.e.mul(dst, img, *_factor(a)); self.e.copy(dst_copy, dst)
         self.products += 1
 
     def prep(self, dst, src):
         self.e.set_multiplicand(dst, src)
         self.prepares += 1
 
-    def sq_prep(self, src, img):
-        """img = the image of src, src = src^2"""
+    def sq_prep(self, src, img, a=1):
+        """img = the image of src, src = a src^2"""
         if self.has_prepare:
-            self.e.square_mul_prepare(src, img)
+            self.e.square_mul_prepare(src, img, *_factor(a))
         else:
             self.prep(img, src)
-            self.e.square_mul(src)
+            self.e.square_mul(src, *_factor(a))
         self.squarings += 1
 
     def addsub(self, s, d, a, b):
@@ -171,6 +190,36 @@ class _Ops:
 
     def sub_to(self, dst, a, b):
         self.e.copy(dst, a); self.e.sub_reg(dst, b)
+
+
+class _IO:
+    """what a run of curves reads and writes on its engine, for both drivers: by_lane=False, one curve on the engine as it is; by_lane=True,
+    curve l in lane l of an engine with `count` lanes.  batch: stretches of calls run inside eng.batch() where the object has one."""
+
+    def __init__(self, eng, count, by_lane, batch):
+        self.e, self.lanes, self.by_lane = eng, range(count), by_lane
+        self.batching = bool(batch and getattr(eng, "batch", None))
+        self.launches0 = eng.batch_stats()[1] if self.batching else 0
+
+    def batched(self):
+        return self.e.batch() if self.batching else contextlib.nullcontext()
+
+    def launches(self):
+        """{"launches": batch launches since the start} of a batched run, nothing otherwise"""
+        return {"launches": self.e.batch_stats()[1] - self.launches0} if self.batching else {}
+
+    def put(self, reg, values):
+        if not self.by_lane:
+            self.e.set_int(reg, values[0])
+            return
+        self.e.set(reg, 0)       # a lane is written into a register of residues; the register may hold an image of the last batch
+        for l in self.lanes:
+            self.e.set_int(reg, values[l], lane=l)
+
+    def get(self, reg):
+        if self.by_lane and getattr(self.e, "get_ints", None):
+            return self.e.get_ints(reg)          # every lane in one launch sequence (include/mi355_lanewise.h)
+        return [self.e.get_int(reg, lane=l) for l in self.lanes] if self.by_lane else [self.e.get_int(reg)]
 
 
 class _Curve:
@@ -231,6 +280,64 @@ class _Curve:
                 self.add(r1, r0, r1, pt); self.dbl(r0, r0)
 
 
+def _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp):
+    """Stage 2 on the stage-1 point in (R_XQ, R_ZQ) of the Montgomery curve whose a24 is the image in R_A24, for both drivers (this one
+    and ecm_edwards): the table of baby points, the giant steps and the accumulator, then g2[l] for every lane that has a stage 2.
+    batched() opens a batch or nothing, get(reg) reads every lane."""
+    mp = (1 << p) - 1
+    lanes = range(len(failed))
+    Q = (R_XQ, R_ZQ)
+    if not any(g1[l] != mp for l in lanes if not failed[l]):
+        return
+    J = residues(D)
+    slot = {j: (FIXED_REGISTERS + 2 * i, FIXED_REGISTERS + 2 * i + 1) for i, j in enumerate(J)}
+    pairs = stage2_pairs(b1, b2, D)
+    if pairs:
+        with batched():
+            two = (R_X2, R_Z2)
+            cv.dbl(two, Q)
+            # baby points: the odd multiples of Q; cur = j Q, prev = (j - 2) Q ((-1) Q has the x of Q)
+            prev, cur, nxt = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
+            for r in (0, 1):
+                eng.copy(prev[r], Q[r]); eng.copy(cur[r], Q[r])
+            for j in range(1, J[-1] + 1, 2):
+                if j in slot:
+                    ops.prep(slot[j][0], cur[0]); ops.prep(slot[j][1], cur[1])
+                if j + 2 <= J[-1]:
+                    cv.add(nxt, cur, two, prev)
+                    prev, cur, nxt = cur, nxt, prev
+            # giant steps: cur = k D Q, nxt = (k + 1) D Q
+            DQ = (R_XD, R_ZD)
+            cv.small_ladder(DQ, (R_XG0, R_ZG0), D, Q)
+            k0, k1 = min(pairs), max(pairs)
+            cur, nxt, spare = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
+            if k0 == 0:
+                eng.set(cur[0], 1); eng.set(cur[1], 0)
+                eng.copy(nxt[0], DQ[0]); eng.copy(nxt[1], DQ[1])
+            else:
+                cv.small_ladder(cur, nxt, k0, DQ)
+            eng.set(R_A, 1)
+            for k in range(k0, k1 + 1):
+                for j in pairs.get(k, ()):
+                    eng.copy(R_T, cur[0]); ops.mul(R_T, slot[j][1])      # X_k Z_j
+                    eng.copy(R_W, cur[1]); ops.mul(R_W, slot[j][0])      # Z_k X_j
+                    eng.sub_reg(R_T, R_W)
+                    ops.prep(R_T, R_T)
+                    ops.mul(R_A, R_T)
+                if k + 1 < k1:
+                    if k == 0:
+                        cv.dbl(spare, DQ)        # the difference would be 0 Q
+                    else:
+                        cv.add(spare, nxt, DQ, cur)
+                    cur, nxt, spare = nxt, spare, cur
+                else:
+                    cur, nxt = nxt, cur
+        for l, acc in enumerate(get(R_A)):
+            if not failed[l] and g1[l] != mp:   # (a curve whose stage 1 gave Mp itself has no stage 2)
+                g = mp if acc == 0 else big_gcd(acc, mp, use_gmp)
+                g2[l] = g // big_gcd(g, g1[l], use_gmp)
+
+
 def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=False):
     """The curves of `sigmas` through one sequence of engine calls: the ladder bits come from B1 and the stage-2 pairs from (B1, B2, D),
     so only the data differ.  by_lane=False: one curve on an engine used as it is (run).  by_lane=True: curve l in lane l of an engine
@@ -255,25 +362,11 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=Fa
     ops = _Ops(eng, use_fused)
     cv = _Curve(ops)
     lanes = range(len(sigmas))
-    batching = bool(batch and getattr(eng, "batch", None))
-    launches0 = eng.batch_stats()[1] if batching else 0
-
-    def batched():
-        return eng.batch() if batching else contextlib.nullcontext()
-
-    def put(reg, values):
-        if not by_lane:
-            eng.set_int(reg, values[0])
-            return
-        eng.set(reg, 0)          # a lane is written into a register of residues; the register may hold an image of the last batch
-        for l in lanes:
-            eng.set_int(reg, values[l], lane=l)
-
-    def get(reg):
-        return [eng.get_int(reg, lane=l) for l in lanes] if by_lane else [eng.get_int(reg)]
+    io = _IO(eng, len(sigmas), by_lane, batch)
+    batched, put, get = io.batched, io.put, io.get
 
     def results(g1, g2):
-        more = {"launches": eng.batch_stats()[1] - launches0} if batching else {}
+        more = io.launches()
         return [{"p": p, "b1": b1, "b2": b2 if stage2 else 0, "D": D if stage2 else None, "sigma": sigmas[l],
                  "factors": [f for f in (g1[l], g2[l]) if 1 < f < mp], "g1": g1[l], "g2": g2[l],
                  "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused, **more} for l in lanes]
@@ -300,7 +393,6 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=Fa
     put(R_X0, [c[0] for c in setup]); ops.prep(R_X0, R_X0)
     a, b = (R_XA, R_ZA), (R_XB, R_ZB)
     put(R_XA, [c[0] for c in setup]); eng.set(R_ZA, 1)
-    Q = (R_XQ, R_ZQ)
     with batched():
         cv.dbl(b, a)                             # (a, b) = (P, 2 P)
         for i in range(e.bit_length() - 2, -1, -1):
@@ -313,55 +405,8 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=Fa
         if not failed[l]:
             g1[l] = mp if z == 0 else big_gcd(z, mp, use_gmp)
 
-    # ---- stage 2 ----
-    if stage2 and any(g1[l] != mp for l in lanes if not failed[l]):
-        J = residues(D)
-        slot = {j: (FIXED_REGISTERS + 2 * i, FIXED_REGISTERS + 2 * i + 1) for i, j in enumerate(J)}
-        pairs = stage2_pairs(b1, b2, D)
-        if pairs:
-            with batched():
-                two = (R_X2, R_Z2)
-                cv.dbl(two, Q)
-                # baby points: the odd multiples of Q; cur = j Q, prev = (j - 2) Q ((-1) Q has the x of Q)
-                prev, cur, nxt = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
-                for r in (0, 1):
-                    eng.copy(prev[r], Q[r]); eng.copy(cur[r], Q[r])
-                for j in range(1, J[-1] + 1, 2):
-                    if j in slot:
-                        ops.prep(slot[j][0], cur[0]); ops.prep(slot[j][1], cur[1])
-                    if j + 2 <= J[-1]:
-                        cv.add(nxt, cur, two, prev)
-                        prev, cur, nxt = cur, nxt, prev
-                # giant steps: cur = k D Q, nxt = (k + 1) D Q
-                DQ = (R_XD, R_ZD)
-                cv.small_ladder(DQ, (R_XG0, R_ZG0), D, Q)
-                k0, k1 = min(pairs), max(pairs)
-                cur, nxt, spare = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
-                if k0 == 0:
-                    eng.set(cur[0], 1); eng.set(cur[1], 0)
-                    eng.copy(nxt[0], DQ[0]); eng.copy(nxt[1], DQ[1])
-                else:
-                    cv.small_ladder(cur, nxt, k0, DQ)
-                eng.set(R_A, 1)
-                for k in range(k0, k1 + 1):
-                    for j in pairs.get(k, ()):
-                        eng.copy(R_T, cur[0]); ops.mul(R_T, slot[j][1])      # X_k Z_j
-                        eng.copy(R_W, cur[1]); ops.mul(R_W, slot[j][0])      # Z_k X_j
-                        eng.sub_reg(R_T, R_W)
-                        ops.prep(R_T, R_T)
-                        ops.mul(R_A, R_T)
-                    if k + 1 < k1:
-                        if k == 0:
-                            cv.dbl(spare, DQ)        # the difference would be 0 Q
-                        else:
-                            cv.add(spare, nxt, DQ, cur)
-                        cur, nxt, spare = nxt, spare, cur
-                    else:
-                        cur, nxt = nxt, cur
-            for l, acc in enumerate(get(R_A)):
-                if not failed[l] and g1[l] != mp:   # (a curve whose stage 1 gave Mp itself has no stage 2)
-                    g = mp if acc == 0 else big_gcd(acc, mp, use_gmp)
-                    g2[l] = g // big_gcd(g, g1[l], use_gmp)
+    if stage2:
+        _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp)
     return results(g1, g2)
 
 
@@ -386,7 +431,8 @@ def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None, batc
     return _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, True, batch)
 
 
-def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0, lanes=1, onelaunch=False, batch=False):
+def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0, lanes=1, onelaunch=False, batch=False,
+        curve="montgomery", check_every=0):
     """`curves` curves of run() on a fresh prmers_amd.Engine sized for the chosen D, until one finds a factor.  sigma: the first curve's
     (None: drawn like the others, from random.Random(seed)).  -> the result of the last curve run, with "sigmas": every sigma used.
     lanes = B > 1: the curves run B at a time through run_lanes() on one engine with B lanes (whole batches: `curves` rounded up to a
@@ -394,8 +440,29 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
     result of that batch's first curve with a factor (of the last curve run when there is none), "factors": those of all its lanes,
     "sigmas": every sigma of every batch run, "batch": the last batch's results, one per lane.
     onelaunch: the engine is created with the plan token of that name (every product one launch; p <= 204799).
-    batch: run() / run_lanes() with batch=True; needs onelaunch (or the token in `plan`) and implies nothing."""
+    batch: run() / run_lanes() with batch=True; needs onelaunch (or the token in `plan`) and implies nothing.
+    curve: "montgomery" (the ladder of this module) or "edwards": stage 1 in twisted Edwards coordinates with an on-curve check every
+    check_every NAF digits and at its end (prmers_amd/ecm_edwards.py: slower per bit, but a wrong result is seen); the results then carry
+    that driver's further keys."""
     from .engine import Engine, resolve_plan
+    if curve not in ("montgomery", "edwards"):
+        raise ValueError('curve must be "montgomery" or "edwards"')
+    if check_every and curve != "edwards":
+        raise ValueError("check_every belongs to curve=\"edwards\": a Montgomery ladder has no invariant to check")
+    if curve == "edwards":
+        from . import ecm_edwards
+
+        def run_one(eng, s):
+            return ecm_edwards.run(eng, p, b1, b2, s, D, check_every=check_every, batch=batch)
+
+        def run_many(eng, ss):
+            return ecm_edwards.run_lanes(eng, p, b1, b2, ss, D, check_every=check_every, batch=batch)
+    else:
+        def run_one(eng, s):
+            return run(eng, p, b1, b2, s, D, batch=batch)
+
+        def run_many(eng, ss):
+            return run_lanes(eng, p, b1, b2, ss, D, batch=batch)
     if lanes < 1:
         raise ValueError("lanes must be at least 1")
     if batch and not (onelaunch or "onelaunch" in (plan or "")):
@@ -417,13 +484,13 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
     if lanes == 1:
         with Engine(p, regs, device=device, plan=plan) as eng:
             for c in range(max(1, curves)):
-                res = run(eng, p, b1, b2, draw(), D, batch=batch)
+                res = run_one(eng, draw())
                 if res["factors"]:
                     break
     else:
         with Engine(p, regs, device=device, plan=plan, lanes=lanes) as eng:
             for c in range(0, max(1, curves), lanes):
-                out = run_lanes(eng, p, b1, b2, [draw() for _ in range(lanes)], D, batch=batch)
+                out = run_many(eng, [draw() for _ in range(lanes)])
                 found = [r for r in out if r["factors"]]
                 res = dict(found[0] if found else out[-1])
                 res["factors"] = sorted({f for r in out for f in r["factors"]})
@@ -449,9 +516,16 @@ def main(argv=None):
     ap.add_argument("--lanes", type=int, default=1, help="curves per batch: an engine with this many lanes runs them in one launch sequence")
     ap.add_argument("--onelaunch", action="store_true", help="plan token onelaunch: every product of the engine is one launch (p <= 204799)")
     ap.add_argument("--batch", action="store_true", help="the ladder and the stage-2 loops as batches, one launch for a run of operations (needs --onelaunch)")
+    ap.add_argument("--curve", choices=("montgomery", "edwards"), default="montgomery",
+                    help="edwards: stage 1 in twisted Edwards coordinates with an on-curve check and roll-back (slower per bit)")
+    ap.add_argument("--check-every", type=int, default=0, help="with --curve edwards: NAF digits between two checks (0: only at the end of stage 1)")
     a = ap.parse_args(argv)
-    res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed, a.lanes, a.onelaunch,
-              **({"batch": True} if a.batch else {}))
+    more = {"batch": True} if a.batch else {}
+    if a.curve != "montgomery":
+        more["curve"] = a.curve
+    if a.check_every:
+        more["check_every"] = a.check_every
+    res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed, a.lanes, a.onelaunch, **more)
     print(json.dumps(res))
     return 0 if res["factors"] else 1
 

@@ -98,10 +98,15 @@ def load_library():
         "mi355_batch_begin": (C.c_int, [vp]),
         "mi355_batch_end": (C.c_int, [vp]),
         "mi355_batch_stats": (C.c_int, [vp, u64p]),
+        # include/mi355_lanewise.h
+        "mi355_lanewise_equal": (C.c_int, [vp, sz, sz, vp, sz]),
+        "mi355_lanewise_get_words": (C.c_int, [vp, sz, vp, sz]),
+        "mi355_lanewise_chunk_lanes": (sz, [sz, sz]),
     }
     for name, (res, args) in sig.items():
-        if name in LANE_EXPORTS + BATCH_EXPORTS and os.environ.get("MI355_ENGINE_LIB") and not hasattr(L, name):
-            continue           # an A/B library from before the lanes or the batches (tools/time_lanes.py): Engine.lanes reads 1, batch() raises
+        if name in LANE_EXPORTS + BATCH_EXPORTS + LANEWISE_EXPORTS and os.environ.get("MI355_ENGINE_LIB") and not hasattr(L, name):
+            continue           # an A/B library from before the lanes, the batches or the lane-wise reads (tools/time_lanes.py): Engine.lanes
+                               # reads 1, batch() and equal_lanes() raise
         f = getattr(L, name)   # AttributeError here = the library does not export what the header declares
         f.restype, f.argtypes = res, args
     _lib = L
@@ -132,6 +137,10 @@ LANE_EXPORTS = ["mi355_lanes_count", "mi355_lanes_set_words", "mi355_lanes_get_w
 
 # include/mi355_batch.h: a run of register operations of a one-launch engine as one launch
 BATCH_EXPORTS = ["mi355_batch_begin", "mi355_batch_end", "mi355_batch_stats"]
+
+
+# include/mi355_lanewise.h: compare, or read, every lane of a register in one launch sequence
+LANEWISE_EXPORTS = ["mi355_lanewise_equal", "mi355_lanewise_get_words", "mi355_lanewise_chunk_lanes"]
 
 
 def resolve_plan(p, spec=None):
@@ -299,6 +308,30 @@ class Engine:
         return bool(out.value)
 
     equal = is_equal        # the names prmers_amd/proof.py uses
+
+    # --- every lane at once (include/mi355_lanewise.h) ---
+    def _lanewise_fn(self, name):
+        f = getattr(self.L, name, None)
+        if f is None:
+            raise EngineError("%s does not export %s (a library from before the lane-wise reads)" % (LIB_PATH, name))
+        return f
+
+    def equal_lanes(self, lhs, rhs):
+        """[lane l of lhs == lane l of rhs mod 2^p - 1 for every lane], one launch sequence for all of them (an engine without lanes: the
+        one answer of is_equal)"""
+        out = np.zeros(self.lanes, dtype=np.uint8)
+        self._ok(self._lanewise_fn("mi355_lanewise_equal")(self.h, lhs, rhs, _ptr(out), out.size))
+        return [bool(v) for v in out]
+
+    def words_lanes(self, src):
+        """the canonical words of every lane: an array of lanes x word_count (what get_ints is made of)"""
+        w = np.zeros((self.lanes, self.word_count), dtype=np.uint32)
+        self._ok(self._lanewise_fn("mi355_lanewise_get_words")(self.h, src, _ptr(w), w.size))
+        return w
+
+    def get_ints(self, src):
+        """[get_int(src, lane=l) for every lane], read in one launch sequence"""
+        return [int.from_bytes(row.astype("<u4").tobytes(), "little") for row in self.words_lanes(src)]
 
     def pow(self, dst, src, e):
         """dst = src^e, src is erased (engine.h:160-170)."""
