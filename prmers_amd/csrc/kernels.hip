@@ -241,7 +241,8 @@ __device__ __forceinline__ void run_carry_in(const DevPlan& pl, uint32_t sa, uin
 
 // Weighted pair of the digits d of pair (i1, i2), sb = SB[2 i2]: weight = TA * TB / (wrap ? 2 : 1), TB left to the four-step twiddle.  The
 // odd digit takes its exponent split from the second half of SA / TA (plan.hpp) so that both digits of the pair share the column factor
-// TB[2 i2]; the halving sits on TA and the digits that do not wrap are doubled instead (digits are < 2^21: still a mul_u32).
+// TB[2 i2]; the halving sits on TA and the digits that do not wrap are doubled instead (a digit is below 2^width <= 2^30, and below 2^31
+// where it keeps the rest of a carry-in, plan.hpp carry_chain_ok: the doubled digit still fits 32 bits and the product stays a mul_u32).
 __device__ __forceinline__ P2 weigh_pair(const DevPlan& pl, uint32_t i1, uint32_t sb, uint2 d) {
   uint32_t w0, w1; bool wr0, wr1;
   digit_info(pl, pl.SA[i1], sb, w0, wr0);
@@ -403,7 +404,7 @@ __device__ __forceinline__ uint32_t adc_mul(uint64_t u, uint32_t a, uint32_t add
   const uint64_t mask = (uint64_t(1) << width) - 1;
   uint64_t r;
   if (a == 1) {               // the common case (uniform): no 64-bit multiplies
-    r = u + carry + addend;   // u < 2^63 by the size rule (ibdwt.h:28-30), carry < 2^48, addend < 2^32
+    r = u + carry + addend;   // u < P only (up to 0.62 2^64 at the top of a range), carry < 2^(64 - width), addend < 2^32: the sum stays below 2^64 (tests/chain_model.py)
     carry = r >> width;
   } else {                    // adc_mul (marin.cl:194-201): digit first, so that everything stays in 64 bits
     const uint64_t dlo = u & mask, chi = u >> width;

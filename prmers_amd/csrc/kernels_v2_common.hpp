@@ -224,7 +224,7 @@ __device__ __forceinline__ void store_run(uint32_t* __restrict__ digits, size_t 
 }
 // digits of one run -> its ND / 2 weighted pairs (run: index among the thread's runs, for the thread's word of the digit-info table).
 // Weight TA*TB, halved when the exponents wrap: the halving is moved onto TA (once per run: tah, and tah1 for the odd digits, whose exponent
-// is split SA[M1 + i1] + SB[2 i2], plan.hpp) and the un-wrapped digits are doubled instead (digits are < 2^21, the product stays a mul_u32);
+// is split SA[M1 + i1] + SB[2 i2], plan.hpp) and the un-wrapped digits are doubled instead (digits are < 2^31, the product stays a mul_u32);
 // nowrap = ~di: bit 2 idx + 1 of di says that the weight exponents of digit idx wrapped
 template <int ND>
 __device__ __forceinline__ void weigh_run(uint64_t tah, uint64_t tah1, uint32_t nowrap, int run, const uint32_t (&dg)[ND], P2* x) {
@@ -237,7 +237,7 @@ __device__ __forceinline__ void weigh_run(uint64_t tah, uint64_t tah1, uint32_t 
 // one digit of the carry chain: u a + addend + carry -> digit of `width` bits, carry (adc_mul, marin.cl:194-201)
 __device__ __forceinline__ uint32_t adc_mul(uint64_t u, uint32_t a, uint32_t addend, uint32_t width, uint64_t& carry) {
   if (a == 1) {               // the common case (uniform): no 64-bit multiplies
-    const uint64_t r = u + carry + addend;   // u < 2^63 by the size rule (ibdwt.h:28-30), carry < 2^48
+    const uint64_t r = u + carry + addend;   // u < P only, carry < 2^(64 - width), addend < 2^32: below 2^64 (see kernels.hip adc_mul)
     carry = r >> width;
     return __builtin_amdgcn_ubfe(uint32_t(r), 0u, width);   // width < 32: one bit-field extract
   }

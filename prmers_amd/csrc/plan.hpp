@@ -103,9 +103,15 @@ struct Plan {
 };
 
 // Whether the back sweeps' fused x a (adc_mul, marin.cl:194-201: carry = (r >> w) + (u >> w) a in 64 bits) is exact for factor a on a
-// plan with digit widths q / q + 1, n digits and runs of 2C digits, at the worst input: every digit at 2^(q+1) - 1 except the one per run
-// that takes the remainder of the carry-in (apply_carry_in / run_carry_in: three digits absorb it, the fourth keeps the rest: digit E).
-//   convolution sum  u <= sum x_i^2 (Cauchy-Schwarz) = (n - n/2C) D^2 + (n/2C) E^2, which must stay below the field prime;
+// plan with digit widths q / q + 1, n digits and runs of 2C digits.  The inputs it covers: every digit j below 2^w_j, its OWN width (q or
+// q + 1), except the one per run that keeps the remainder of a carry-in (apply_carry_in / run_carry_in: three digits absorb it, the fourth
+// keeps the rest: digit E).  It does NOT cover "2^(q+1) - 1 on every digit", although the terms below are written with D = 2^(q+1) - 1: the
+// unweighted coefficient is z_k = sum x_i x_j 2^c(i,j) with c in {0, 1} the carry of the two weight exponents (sum_product_ok below), and
+// the terms leave that factor 2 out.  With digits inside their own widths two things make up for it: a narrow digit is below D / 2, and
+// chi = U >> q shifts by the narrow width where most digits of a full range are wide.  At the top of a range, all digits at their maximum,
+// the exact carry word at a_fast reaches 0.9999 of 2^64 and stays below it; with 2^(q+1) - 1 on every digit it passes 2^64 (p = 44497: 1.27).
+// tests/chain_model.py is the exact chain, tests/test_factor_bound_cases.py holds both findings and the first factor that overflows.
+//   convolution sum  u ~ sum x_i^2 (Cauchy-Schwarz) = (n - n/2C) D^2 + (n/2C) E^2, which must stay below the field prime;
 //   back sweep       r = dlo a + carry + addend (< 2^32) and carry' = (r >> q) + (u >> q) a below 2^64 at the carry's fixed point;
 //   next sweep       E = D + (carry >> 3q) + 3, the digit the carry word leaves behind (below 2^31, so that x a fits k_scale too).
 // Runs of two digits (C = 1) take their carries at once and the local carry passes restore the digits (Engine::carry_fix_now, sized for

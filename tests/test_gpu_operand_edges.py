@@ -280,8 +280,8 @@ def _check_all_max_digits(e):
 
 @pytest.mark.xfail(strict=True, reason="the reference's size rule takes log2 5 as 2.4 and admits exponents at the top of the 5 2^k "
                    "ranges where the convolution sums of the all-maximum input pass the field prime (the oracle gives the same wrong value)")
-@pytest.mark.parametrize("n", [5 * 2**19, 5 * 2**21])
-def test_all_max_digits_at_the_top_of_the_five_ranges(n, oracle_lib):
+@pytest.mark.parametrize("n", [5 * 2**19, 5 * 2**21, 40, 160, 640, 2560, 10240, 40960])   # (the small ones: the exact coefficients are
+def test_all_max_digits_at_the_top_of_the_five_ranges(n, oracle_lib):                     # 1.20-1.25 P, test_factor_bound_cases.py)
     with Engine(_p_max(n), 4) as e:
         _check_all_max_digits(e)
 

@@ -53,8 +53,12 @@ def test_transform_size_at_the_top_of_every_range(plan_query):
 
 def _worst_case_terms(q, n, c, a):
     """Largest 64-bit term of the fused x a carry (adc_mul: r = dlo a + carry + addend, carry' = (r >> w) + (u >> w) a) over a run of 2c
-    digits at the worst input: digits at 2^(q+1) - 1 except the one per run that keeps the remainder of the carry-in (E), the addend of
-    mul_add at 2^32; -> (largest r / carry seen, convolution bound, E)"""
+    digits, a restatement of plan.hpp carry_chain_ok.  The inputs the bound holds for: digits below 2^w_j of their own width (q or
+    q + 1), except the one per run that keeps the remainder of the carry-in (E); the addend of mul_add at 2^32.  The terms are written
+    with D = 2^(q+1) - 1, but 2^(q+1) - 1 on EVERY digit is not covered: the coefficients are sum x_i x_j 2^c(i,j), and the terms leave
+    the factor 2 of the weight exponents' carry out.  For digits inside their own widths a narrow digit below D / 2 and the shift by the
+    narrow width in chi = U >> q make up for it; the exact chain (chain_model.py, test_factor_bound_cases.py) holds the margins and
+    the overflow of the all-wide input.  -> (largest r / carry seen, convolution bound, E)"""
     D = 2**(q + 1) - 1
     runs = n // (2 * c)
     E_ = D
