@@ -1,4 +1,5 @@
-/* libmi355_engine.so -- lane-wise reads: compare two registers, or read one, on every lane of an engine in one launch sequence.
+/* libmi355_engine.so -- lane-wise reads: compare two registers, or read one, on every lane of an engine in one launch sequence; and the
+ * lane-wise write, mi355_lanewise_set_words, which shares their chunks and their scratch.
  *
  * On an engine with lanes (include/mi355_lanes.h) mi355_engine_equal is refused and mi355_lanes_get_words reads one lane: the canonical
  * form of a lane is seven launches and a synchronising read of its flag words, so a comparison on 512 lanes costs thousands of launches.
@@ -32,6 +33,12 @@ MI355_ENGINE_API int mi355_lanewise_equal(mi355_engine_handle handle, size_t lhs
 /* the canonical residue of every lane of src: lane l in words[l * word_count .. (l + 1) * word_count), each what mi355_lanes_get_words
    returns for that lane.  count must equal mi355_lanes_count(handle) * mi355_engine_word_count(handle). */
 MI355_ENGINE_API int mi355_lanewise_get_words(mi355_engine_handle handle, size_t src, uint32_t* words, size_t count);
+/* The way back: lane l of dst = the residue whose words are words[l * word_count .. (l + 1) * word_count), each as mi355_lanes_set_words
+   takes them for that lane (bits at and above p are folded back in, 2^p = 1).  One upload and one launch per chunk of lanes, where lane by
+   lane every lane is an upload, a launch and a synchronise.  dst becomes a register of residues on every lane: it may have held a
+   multiplicand image or pending run carries.  count must equal mi355_lanes_count(handle) * mi355_engine_word_count(handle).  Under
+   MI355_HOST_CARRY=1 the lanes are cut into digits on the host, one by one. */
+MI355_ENGINE_API int mi355_lanewise_set_words(mi355_engine_handle handle, size_t dst, const uint32_t* words, size_t count);
 /* Informational only: nothing has to be called with its result.  Lanes per chunk for an engine of `lanes` lanes at a transform of
    transform_size digits: the largest count whose scratch, 16 transform_size + 8 ceil(transform_size / 4096) + 64 bytes a lane, fits
    64 MiB; at least 1, at most `lanes`.  It tells a caller how many launch sequences a call above takes and lets the rule be checked

@@ -18,7 +18,8 @@
 // of lane 0, to it.  Lane strides: the input register `in_stride` digits (an engine with lanes: 8n bytes), every natural-order array n
 // digits, the block aggregates and block carries one word per block of the lane, the flags kFlagWords words, the packed words wc words.
 // The one-lane launchers launch grid.y = 1, where all of this is lane 0 as before; canon_launch_lanes and its companions launch a chunk
-// of lanes at once (an engine's lane-wise equal and get_words: engine.hip).
+// of lanes at once (an engine's lane-wise equal and get_words: engine.hip).  k_unpack_words has the same lane form for the way back
+// (canon_unpack_words_lanes: an engine's lane-wise set_words).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -252,10 +253,13 @@ __global__ void __launch_bounds__(256) k_pack_words(CanonGeom g, const T* __rest
 // k_unpack_words: one thread per digit j.  It reads the two words it overlaps (a third when a wide digit starts high in its first word),
 // masks to the width and stores the digit at its memory position: natural order (M1 = 0, the u64 family) or tile-major (pos_of -- the
 // store k_scatter does, without the natural-order array in between).  The words hold a value below 2^p; words at and above wc read as zero.
+// Lanes: lane blockIdx.y reads its wc words behind lane 0's and writes its digits out_stride digits behind lane 0's (size_t: a lane of a
+// large engine begins beyond 4 GiB).
 template <class T>
-__global__ void __launch_bounds__(256) k_unpack_words(CanonGeom g, const uint32_t* __restrict__ words, uint32_t wc, T* __restrict__ digits) {
+__global__ void __launch_bounds__(256) k_unpack_words(CanonGeom g, const uint32_t* __restrict__ words, uint32_t wc, T* __restrict__ digits, size_t out_stride) {
   const uint32_t j = blockIdx.x * 256 + threadIdx.x;
   if (j >= g.n) return;
+  words += size_t(blockIdx.y) * wc; digits += size_t(blockIdx.y) * out_stride;
   const uint64_t o = ceil_pj_n(g, j);
   const uint32_t w = uint32_t(ceil_pj_n(g, uint64_t(j) + 1) - o);
   const uint64_t i = o >> 5;
@@ -322,7 +326,7 @@ template <class T> hipError_t canon_pack_words(const CanonGeom& g, const T* cano
   return hipGetLastError();
 }
 template <class T> hipError_t canon_unpack_words(const CanonGeom& g, const uint32_t* words, T* digits, hipStream_t s) {
-  hipLaunchKernelGGL(k_unpack_words<T>, dim3((g.n + 255) / 256), dim3(256), 0, s, g, words, word_count_of(g), digits);
+  hipLaunchKernelGGL(k_unpack_words<T>, dim3((g.n + 255) / 256), dim3(256), 0, s, g, words, word_count_of(g), digits, size_t(0));
   return hipGetLastError();
 }
 #define MI355_CANON_FOR(T)                                                                                      \
@@ -373,6 +377,12 @@ hipError_t canon_pack_words_lanes(const CanonGeom& g, size_t L, int slot, void* 
   const uint32_t wc = word_count_of(g);   // wc <= n: the words of L lanes fit the first work array
   hipLaunchKernelGGL(k_pack_words<uint32_t>, dim3((wc + 255) / 256, uint32_t(L)), dim3(256), 0, s, gn, w.out[slot & 1], w.A, wc);
   *words = w.A;
+  return hipGetLastError();
+}
+
+hipError_t canon_unpack_words_lanes(const CanonGeom& g, const uint32_t* words, uint32_t* out, size_t out_stride, size_t L, hipStream_t s) {
+  if (g.M1 == 0 || L == 0 || L > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_unpack_words<uint32_t>, dim3((g.n + 255) / 256, uint32_t(L)), dim3(256), 0, s, g, words, word_count_of(g), out, out_stride);
   return hipGetLastError();
 }
 

@@ -40,6 +40,9 @@ hipError_t canon_launch_lanes(const CanonGeom& g, const uint32_t* digits, size_t
 hipError_t canon_compare_lanes(const CanonGeom& g, size_t L, void* scratch, hipStream_t s);   // slot 0 against slot 1 -> flag [2] of each lane
 // slot's canonical digits -> ceil(p / 32) words a lane, lane after lane, in *words (inside the scratch: the work arrays are free by then)
 hipError_t canon_pack_words_lanes(const CanonGeom& g, size_t L, int slot, void* scratch, uint32_t** words, hipStream_t s);
+// the way back: ceil(p / 32) words a lane, lane after lane (each a value below 2^p), -> the digits of L lanes of a register, lane l
+// out_stride digits behind lane 0 (`out`)
+hipError_t canon_unpack_words_lanes(const CanonGeom& g, const uint32_t* words, uint32_t* out, size_t out_stride, size_t L, hipStream_t s);
 
 // natural order only (uint64_t): one local carry pass in -> out (digits of up to w + e bits come out below 2^w + 2^e), and
 // dst += the digit-wise complement of a canonical residue, i.e. dst - canon mod 2^p - 1

@@ -241,6 +241,9 @@ int mi355_lanewise_equal(mi355_engine_handle h, size_t lhs, size_t rhs, uint8_t*
 int mi355_lanewise_get_words(mi355_engine_handle h, size_t src, uint32_t* w, size_t count) {
   return guarded([&] { if (!w) throw std::runtime_error("lanewise_get_words: null buffer"); m(h)->get_words_lanes(src, w, count); });
 }
+int mi355_lanewise_set_words(mi355_engine_handle h, size_t dst, const uint32_t* w, size_t count) {
+  return guarded([&] { if (!w) throw std::runtime_error("lanewise_set_words: null buffer"); m(h)->set_words_lanes(dst, w, count); });
+}
 size_t mi355_lanewise_chunk_lanes(size_t n, size_t lanes) { return mi355::canon_chunk_lanes(n, lanes); }
 
 // ---- include/mi355_batch.h ----

@@ -551,6 +551,43 @@ void Engine::get_words_lanes(size_t src, uint32_t* w, size_t count) {
   }
 }
 
+// The way back: the words of every lane go up a chunk at a time into the same scratch (one copy) and are cut into the digits of the
+// chunk's lanes in one launch (canon.hip k_unpack_words with the lanes as grid.y), where lane by lane each lane is an upload, a launch and a
+// synchronise.  The register becomes digits on every lane; what it held (an image, pending run carries) is gone, as after set_words.
+void Engine::set_words_lanes(size_t dst, const uint32_t* w, size_t count) {
+  if (lanes_ == 1) { RegisterMachine::set_words_lanes(dst, w, count); return; }
+  const size_t wc = word_count();
+  need_register(dst, "lanewise_set_words");
+  if (count != lanes_ * wc) throw std::runtime_error("lanewise_set_words: count must equal lanes x word_count()");
+  HIPCHK(hipSetDevice(device_));
+  if (host_carry_) {
+    for (size_t l = 0; l < lanes_; ++l) put_words(dst, w + l * wc, wc, l, l + 1);
+  } else {
+    const size_t chunk = canon_chunk_lanes(pl_.n, lanes_), stride = reg_bytes_ / 4;
+    uint32_t* dw = static_cast<uint32_t*>(lanes_scratch(chunk));   // wc <= n: the words of a chunk fit its first work array
+    const uint32_t top = pl_.p % 32;
+    std::vector<uint32_t> folded;
+    for (size_t l0 = 0; l0 < lanes_; l0 += chunk) {
+      const size_t L = std::min(chunk, lanes_ - l0);
+      const uint32_t* src = w + l0 * wc;
+      // bits at and above p are folded back on the host (2^p = 1), as put_words does, and only for the lanes that have such bits
+      bool any = false;
+      for (size_t l = 0; top && l < L && !any; ++l) any = (src[l * wc + wc - 1] >> top) != 0;
+      if (any) {
+        folded.assign(src, src + L * wc);
+        for (size_t l = 0; l < L; ++l)
+          if (folded[l * wc + wc - 1] >> top) host_digits::fold_words_mod_mp(folded.data() + l * wc, wc, pl_.p);
+        src = folded.data();
+      }
+      HIPCHK(hipMemcpyAsync(dw, src, L * wc * 4, hipMemcpyHostToDevice, stream()));
+      HIPCHK(canon_unpack_words_lanes(cg_, dw, digits(dst, l0), stride, L, stream()));
+      HIPCHK(hipStreamSynchronize(stream()));
+    }
+  }
+  kind_[dst] = kDigits;
+  pending_carry_[dst] = 0;
+}
+
 // ---- register operations -------------------------------------------------------------------
 
 void Engine::copy(size_t dst, size_t src) {

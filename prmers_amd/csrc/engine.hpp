@@ -46,6 +46,8 @@ class Engine final : public RegisterMachine {
   // and every lane under MI355_HOST_CARRY=1, goes through the host carry
   void equal_lanes(size_t lhs, size_t rhs, uint8_t* out, size_t count) override;
   void get_words_lanes(size_t src, uint32_t* w, size_t count) override;
+  // the words of every lane into dst, one upload and one launch per chunk of lanes (canon.hip canon_unpack_words_lanes); dst becomes digits
+  void set_words_lanes(size_t dst, const uint32_t* w, size_t count) override;
   void copy(size_t dst, size_t src) override;
   void set_multiplicand(size_t dst, size_t src) override;
   void square_mul(size_t r, uint32_t a) override;

@@ -67,6 +67,12 @@ class RegisterMachine {
     need_residue(src, "lanewise_get_words");
     get_words(src, w, count);
   }
+  // and written: lane l of dst = the residue whose words are w[l * word_count() ..); a machine without lanes writes its one lane through set_words
+  virtual void set_words_lanes(size_t dst, const uint32_t* w, size_t count) {
+    if (count != lanes() * word_count()) throw std::runtime_error("lanewise_set_words: count must equal lanes x word_count()");
+    need_register(dst, "lanewise_set_words");
+    set_words(dst, w, count);
+  }
 
   // Batches (include/mi355_batch.h): the register operations between batch_begin and batch_end run as one launch.  Only the Goldilocks
   // engine with one-launch products has them (engine.hpp); stats: operations queued so far, batch launches so far, capacity, pending now.

@@ -1,7 +1,7 @@
 """ECM factoring of a Mersenne number 2^p - 1 on the engine: Montgomery curves, stages 1 and 2 (the reference: src/modes/RunEcm.cpp).
 
     python -m prmers_amd.ecm P B1 [B2] [--sigma S] [--curves N] [--lanes B] [--D 30|210|2310] [--plan SPEC] [--onelaunch] [--batch] [--device N]
-                             [--curve montgomery|edwards] [--check-every N]
+                             [--curve montgomery|edwards] [--check-every N] [--stage2 projective|affine]
 
 Curve:    Suyama's parametrisation from sigma: u = sigma^2 - 5, v = 4 sigma, the point (u^3 : v^3) on B y^2 = x^3 + A x^2 + x with
           a24 = (A + 2) / 4 = (v - u)^3 (3 u + v) / (16 u^3 v).  The start is taken affine, x0 = u^3 / v^3 and Z = 1: one modular inversion
@@ -21,6 +21,18 @@ Stage 2:  the standard continuation on x-coordinates over the wheel D: every pri
           multiplicand images of X_j and of Z_j.  Giant steps: D Q and k0 D Q by short ladders on Q, then (k + 1) D Q = k D Q + D Q with
           difference (k - 1) D Q.  Per pair: 3 products and one set_multiplicand (X_k Z_j, Z_k X_j, the image of the difference, A times
           it).  0 Q = (1 : 0) is a valid giant point: the k = 0 terms are Z_j.
+Affine:   stage2="affine" / --stage2 affine works on x = X / Z instead: the table holds images of -x_j, the giant points become images of
+          x_k, and a pair is A <- A (x_k + (-x_j)), ONE engine call, Engine.mul_sum (one product of 3 sweeps where the plan has the
+          fused sum, the engine's two-product composition where not; the composition copy, mul, mul, add for an object without it).
+          Points are normalised in blocks by Montgomery's trick ON THE ENGINE (_stage2_affine.normalise): prefix products
+          c_i = c_(i-1) Z_i, c_m read on every lane (get_ints), one host inversion per lane (mod_inverses: at small exponents one for
+          all lanes, the trick once more, across the lanes), u written back (set_ints; Mp - u for the baby block, so the negation is
+          free), then inv_i = u c_(i-1), u <- u Z_i, x_i = X_i inv_i: at most 4 products and 4
+          set_multiplicand per point.  The baby table is one block; X_j, Z_j, c_j take 3 |J| registers, of which 2 |J| are free
+          afterwards and hold the giant points in blocks of floor(2 |J| / 3).  A lane whose c_m has no inverse gets u = 1 and rides
+          along.  The host keeps zacc = prod c_m per lane and g2 = gcd(A zacc, Mp) with g1 divided out: the Z product finds a factor
+          modulo which some point is the point at infinity -- which is also how the k = 0 pairs are covered (q = j divides the order
+          exactly when Z_j vanishes), so no pair is walked for k = 0.  Opt-in; the default stays projective.
 
 The driver works on anything with the interface of prmers_amd.Engine; addsub and square_mul_prepare are used when the object has them
 and replaced by the compositions they stand for when it has not.
@@ -67,19 +79,30 @@ def stage1_exponent(b1):
     return e
 
 
-def registers_needed(D):
-    """registers of an engine that runs stage 2 with this D: images of X_j and Z_j for every j in J plus FIXED_REGISTERS"""
+STAGE2_MODES = ("projective", "affine")
+
+
+def _check_mode(stage2):
+    if stage2 not in STAGE2_MODES:
+        raise ValueError('stage2 must be "projective" or "affine"')
+
+
+def registers_needed(D, stage2="projective"):
+    """registers of an engine that runs stage 2 with this D: images of X_j and Z_j for every j in J plus FIXED_REGISTERS; for
+    stage2="affine" X_j, Z_j and the prefix product c_j for every j in J plus FIXED_REGISTERS -- nothing on top: the running inverse of a
+    normalisation lives in R_U, a temporary of the point additions, which do not run meanwhile"""
     if D not in D_CHOICES:
         raise ValueError("D must be one of %s" % (D_CHOICES,))
-    return 2 * len(residues(D)) + FIXED_REGISTERS
+    _check_mode(stage2)
+    return (3 if stage2 == "affine" else 2) * len(residues(D)) + FIXED_REGISTERS
 
 
-def choose_D(n, b1, b2, budget=DEFAULT_BUDGET):
-    """the largest D whose register file (registers_needed(D) + the engine's work buffer, 8 n bytes each) fits `budget` bytes and that is
-    not wider than the interval (B1, B2] itself"""
+def choose_D(n, b1, b2, budget=DEFAULT_BUDGET, stage2="projective"):
+    """the largest D whose register file (registers_needed(D, stage2) + the engine's work buffer, 8 n bytes each) fits `budget` bytes and
+    that is not wider than the interval (B1, B2] itself"""
     best = D_CHOICES[0]
     for D in D_CHOICES[1:]:
-        if (registers_needed(D) + 1) * 8 * n <= budget and D <= max(b2 - b1, D_CHOICES[0]):
+        if (registers_needed(D, stage2) + 1) * 8 * n <= budget and D <= max(b2 - b1, D_CHOICES[0]):
             best = D
     return best
 
@@ -120,6 +143,27 @@ def mod_inverse(x, n, use_gmp=None):
             G.__gmpz_clear(ctypes.byref(z))
 
 
+SHARED_INVERSE_BITS = 1 << 16    # up to here three host products cost less than an inversion (Python's % is quadratic, libgmp's invert is not)
+
+
+def mod_inverses(xs, n, use_gmp=None):
+    """[mod_inverse(x, n) for x in xs], 0 where there is none.  Below SHARED_INVERSE_BITS one inversion serves all of them (Montgomery's
+    trick on the host: three products a value); when that one fails, some value has no inverse and they are inverted one by one."""
+    xs = [int(x) % n for x in xs]
+    if len(xs) > 1 and int(n).bit_length() <= SHARED_INVERSE_BITS:
+        prefix = [1]
+        for x in xs:
+            prefix.append(prefix[-1] * x % n)
+        u = mod_inverse(prefix[-1], n, use_gmp) if prefix[-1] else 0
+        if u:
+            out = [0] * len(xs)
+            for i in range(len(xs) - 1, -1, -1):
+                out[i] = u * prefix[i] % n
+                u = u * xs[i] % n
+            return out
+    return [mod_inverse(x, n, use_gmp) if x else 0 for x in xs]
+
+
 def suyama(sigma, n, use_gmp=None):
     """(x0, a24, 1) of the curve of `sigma` modulo n with the start point affine, or (0, 0, g) when the one inversion fails: g = gcd of
     its argument and n, a factor of n (n itself for a degenerate sigma)"""
@@ -149,6 +193,8 @@ class _Ops:
         self.fused = bool(self.has_prepare and getattr(eng, "square_mul_prepare_is_fused", lambda: False)())
         self.has_addsub = getattr(eng, "addsub", None) is not None
         self.has_mul_copy = getattr(eng, "mul_copy", None) is not None
+        self.has_mul_sum = getattr(eng, "mul_sum", None) is not None
+        self.fused_sum = bool(self.has_mul_sum and getattr(eng, "mul_sum_is_fused", lambda: False)())
 
     # a: the small factor of the engine's products; a call without one is issued without one
     def sq(self, r, a=1):
@@ -166,6 +212,14 @@ class _Ops:
         else:
             self.e.mul(dst, img, *_factor(a)); self.e.copy(dst_copy, dst)
         self.products += 1
+
+    def mul_sum(self, dst, img_a, img_b, tmp):
+        """dst = dst (a + b) for two images: the engine's mul_sum (one product where its plan has the fused sum), else the composition"""
+        if self.has_mul_sum:
+            self.e.mul_sum(dst, img_a, img_b, tmp)
+            self.products += 1 if self.fused_sum else 2
+        else:
+            self.e.copy(tmp, dst); self.mul(dst, img_a); self.mul(tmp, img_b); self.e.add(dst, tmp)
 
     def prep(self, dst, src):
         self.e.set_multiplicand(dst, src)
@@ -211,6 +265,9 @@ class _IO:
     def put(self, reg, values):
         if not self.by_lane:
             self.e.set_int(reg, values[0])
+            return
+        if getattr(self.e, "set_ints", None):
+            self.e.set_ints(reg, values)         # every lane in one upload and one launch (include/mi355_lanewise.h)
             return
         self.e.set(reg, 0)       # a lane is written into a register of residues; the register may hold an image of the last batch
         for l in self.lanes:
@@ -280,10 +337,101 @@ class _Curve:
                 self.add(r1, r0, r1, pt); self.dbl(r0, r0)
 
 
-def _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp):
+def _stage2_affine(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, put, use_gmp):
+    """_stage2 with stage2="affine" (the module's docstring): tables of x-coordinates, one mul_sum per pair.
+    -> the keys an affine run adds to its results"""
+    mp = (1 << p) - 1
+    lanes = range(len(failed))
+    Q = (R_XQ, R_ZQ)
+    info = {"stage2": "affine", "fused_sum": ops.fused_sum, "normalised": 0}
+    pairs = stage2_pairs(b1, b2, D)
+    if not pairs or not any(g1[l] != mp for l in lanes if not failed[l]):
+        return info
+    J = residues(D)
+    triple = [tuple(FIXED_REGISTERS + 3 * i + r for r in range(3)) for i in range(len(J))]      # X_j, Z_j, c_j
+    slot = {j: triple[i][0] for i, j in enumerate(J)}                                            # ... and then the image of -x_j
+    free = [r for t in triple for r in t[1:]]
+    giant = [tuple(free[3 * i:3 * i + 3]) for i in range(max(1, len(free) // 3))]
+    zacc = [1] * len(failed)
+
+    def normalise(block, negate):
+        """block: register triples (X, Z, C) with a point (X : Z) in the first two.  Afterwards X holds the image of x = X / Z (of -x
+        when negate) and Z and C are spent.  Montgomery's trick on the engine: prefix products c_i = c_(i-1) Z_i up, one inversion per
+        lane on the host, inv_i = u c_(i-1) and u <- u Z_i down.  At most 4 products and 4 set_multiplicand per point."""
+        c = [block[0][1]] + [t[2] for t in block[1:]]            # c_1 is Z_1 itself
+        for i in range(1, len(block)):
+            X, Z, C = block[i]
+            ops.prep(Z, Z); eng.copy(C, c[i - 1]); ops.mul(C, Z)
+        cms = get(c[-1])
+        for l, cm in enumerate(cms):
+            zacc[l] = zacc[l] * cm % mp
+        us = [u or 1 for u in mod_inverses(cms, mp, use_gmp)]    # a lane without an inverse rides along on 1: its factor is in zacc
+        put(R_U, [mp - u for u in us] if negate else us)
+        for i in range(len(block) - 1, 0, -1):
+            X, Z, C = block[i]
+            ops.prep(R_IT, R_U); ops.mul(c[i - 1], R_IT)         # inv_i = u c_(i-1)
+            ops.mul(R_U, Z)                                      # u <- u Z_i
+            ops.prep(c[i - 1], c[i - 1]); ops.mul(X, c[i - 1])   # x_i = X_i inv_i
+            ops.prep(X, X)
+        X = block[0][0]
+        ops.prep(R_IT, R_U); ops.mul(X, R_IT); ops.prep(X, X)    # inv_1 = u
+        info["normalised"] += len(block)
+
+    with batched():
+        two = (R_X2, R_Z2)
+        cv.dbl(two, Q)
+        # baby points: the odd multiples of Q as residues, then one block of the normalisation: the table holds images of -x_j
+        prev, cur, nxt = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
+        for r in (0, 1):
+            eng.copy(prev[r], Q[r]); eng.copy(cur[r], Q[r])
+        for j in range(1, J[-1] + 1, 2):
+            if j in slot:
+                eng.copy(slot[j], cur[0]); eng.copy(slot[j] + 1, cur[1])
+            if j + 2 <= J[-1]:
+                cv.add(nxt, cur, two, prev)
+                prev, cur, nxt = cur, nxt, prev
+        normalise(triple, True)
+        eng.set(R_A, 1)
+        # giant steps from k = 1 on (the k = 0 pairs are the Z_j, which are in zacc): cur = k D Q, nxt = (k + 1) D Q, in blocks
+        k, k1 = max(min(pairs), 1), max(pairs)
+        if k <= k1:
+            DQ = (R_XD, R_ZD)
+            cv.small_ladder(DQ, (R_XG0, R_ZG0), D, Q)
+            cur, nxt, spare = (R_XG0, R_ZG0), (R_XG1, R_ZG1), (R_XG2, R_ZG2)
+            cv.small_ladder(cur, nxt, k, DQ)
+        while k <= k1:
+            block = []
+            while k <= k1 and len(block) < len(giant):
+                if pairs.get(k):
+                    t = giant[len(block)]
+                    eng.copy(t[0], cur[0]); eng.copy(t[1], cur[1])
+                    block.append((k, t))
+                if k + 1 < k1:
+                    cv.add(spare, nxt, DQ, cur)
+                    cur, nxt, spare = nxt, spare, cur
+                else:
+                    cur, nxt = nxt, cur
+                k += 1
+            if block:
+                normalise([t for _, t in block], False)
+            for kk, t in block:
+                for j in pairs[kk]:
+                    ops.mul_sum(R_A, t[0], slot[j], R_T)         # A <- A (x_k + (-x_j))
+    for l, acc in enumerate(get(R_A)):
+        if not failed[l] and g1[l] != mp:
+            v = acc * zacc[l] % mp
+            g = mp if v == 0 else big_gcd(v, mp, use_gmp)
+            g2[l] = g // big_gcd(g, g1[l], use_gmp)
+    return info
+
+
+def _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, put=None, stage2="projective"):
     """Stage 2 on the stage-1 point in (R_XQ, R_ZQ) of the Montgomery curve whose a24 is the image in R_A24, for both drivers (this one
     and ecm_edwards): the table of baby points, the giant steps and the accumulator, then g2[l] for every lane that has a stage 2.
-    batched() opens a batch or nothing, get(reg) reads every lane."""
+    batched() opens a batch or nothing, get(reg) reads every lane, put(reg, values) writes every lane (stage2="affine" only).
+    -> the keys the mode adds to the results (none for "projective")"""
+    if stage2 == "affine":
+        return _stage2_affine(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, put, use_gmp)
     mp = (1 << p) - 1
     lanes = range(len(failed))
     Q = (R_XQ, R_ZQ)
@@ -338,11 +486,12 @@ def _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp):
                 g2[l] = g // big_gcd(g, g1[l], use_gmp)
 
 
-def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=False):
+def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=False, mode="projective"):
     """The curves of `sigmas` through one sequence of engine calls: the ladder bits come from B1 and the stage-2 pairs from (B1, B2, D),
     so only the data differ.  by_lane=False: one curve on an engine used as it is (run).  by_lane=True: curve l in lane l of an engine
     with len(sigmas) lanes (run_lanes); every engine call then acts on all of them.  batch: the ladder and the stage-2 loops run inside
-    eng.batch() where the object has one (else as without).  -> one result per curve"""
+    eng.batch() where the object has one (else as without).  mode: the stage 2, "projective" or "affine".  -> one result per curve"""
+    _check_mode(mode)
     if b1 < 2:
         raise ValueError("B1 must be at least 2")
     if min(sigmas) < SIGMA_MIN:
@@ -352,11 +501,11 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=Fa
     stage2 = b2 > b1
     if stage2:
         if D is None:
-            D = max([d for d in D_CHOICES if have is None or registers_needed(d) <= have] or [0])
-            D = min(D, choose_D(eng.n, b1, b2)) if D else 0
+            D = max([d for d in D_CHOICES if have is None or registers_needed(d, mode) <= have] or [0])
+            D = min(D, choose_D(eng.n, b1, b2, stage2=mode)) if D else 0
         if D not in D_CHOICES:
             raise ValueError("stage 2 needs D in %s and an engine with registers_needed(D) registers" % (D_CHOICES,))
-    need = registers_needed(D) if stage2 else FIXED_REGISTERS
+    need = registers_needed(D, mode) if stage2 else FIXED_REGISTERS
     if have is not None and have < need:
         raise ValueError("the engine has %d registers, ECM with D = %s needs %d" % (have, D if stage2 else None, need))
     ops = _Ops(eng, use_fused)
@@ -365,8 +514,8 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=Fa
     io = _IO(eng, len(sigmas), by_lane, batch)
     batched, put, get = io.batched, io.put, io.get
 
-    def results(g1, g2):
-        more = io.launches()
+    def results(g1, g2, more2=None):
+        more = {**(more2 or {}), **io.launches()}
         return [{"p": p, "b1": b1, "b2": b2 if stage2 else 0, "D": D if stage2 else None, "sigma": sigmas[l],
                  "factors": [f for f in (g1[l], g2[l]) if 1 < f < mp], "g1": g1[l], "g2": g2[l],
                  "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused, **more} for l in lanes]
@@ -405,34 +554,40 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=Fa
         if not failed[l]:
             g1[l] = mp if z == 0 else big_gcd(z, mp, use_gmp)
 
+    more2 = None
     if stage2:
-        _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp)
-    return results(g1, g2)
+        more2 = _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, put, mode)
+    return results(g1, g2, more2)
 
 
-def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None, batch=False):
+def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None, batch=False, stage2="projective"):
     """One curve of ECM on 2^p - 1 with bounds B1 and B2 (B2 <= B1: stage 1 only) on `eng`, an engine for exponent p with at least
     FIXED_REGISTERS registers (stage 1) or registers_needed(D) (stage 2).  use_fused=False forces set_multiplicand + square_mul in
     place of square_mul_prepare.  Afterwards registers R_XQ, R_ZQ hold the stage-1 point.  batch=True: the ladder and the stage-2 loops
     run inside eng.batch() (an engine with one-launch products); the result then has "launches", the batch launches it took.
+    stage2="affine": stage 2 on normalised x-coordinates, one mul_sum per pair (the module's docstring); the engine then needs
+    registers_needed(D, "affine") registers and the result of a run with a stage 2 has "stage2": "affine", "fused_sum" (the engine's
+    mul_sum is one product) and "normalised" (points normalised).  The prime factors it finds are those of the projective stage 2 and
+    those modulo which a baby or giant point is the point at infinity.  It is meant for small exponents on lane engines: every block of
+    points costs one modular inversion per lane on the host, which at exponents in the millions is minutes.
     -> {p, b1, b2, D, sigma, factors, g1, g2, squarings, products, prepares, fused}"""
-    return _run_curves(eng, p, b1, b2, [sigma], D, use_fused, use_gmp, False, batch)[0]
+    return _run_curves(eng, p, b1, b2, [sigma], D, use_fused, use_gmp, False, batch, stage2)[0]
 
 
-def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None, batch=False):
+def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None, batch=False, stage2="projective"):
     """len(sigmas) == eng.lanes curves at once on an engine with lanes (Engine(..., lanes=B)), curve l in lane l: the engine calls of ONE
-    run(), each of which acts on every lane.  x0 and a24 are written lane by lane, the stage-1 Z and the stage-2 accumulator read back
-    and gcd'd lane by lane.  A curve whose inversion fails reports that factor as run() does; its lane carries a valid curve whose
+    run(), each of which acts on every lane.  x0 and a24 are written, and the stage-1 Z and the stage-2 accumulator read back, for all lanes
+    at once where the engine has set_ints / get_ints (lane by lane otherwise) and gcd'd lane by lane.  stage2 as for run().  A curve whose inversion fails reports that factor as run() does; its lane carries a valid curve whose
     outcome is dropped.  -> one result per curve in the shape of run(); squarings, products and prepares are those of the batch, which
     are those of one curve."""
     sigmas = list(sigmas)
     if len(sigmas) != getattr(eng, "lanes", 1) or not sigmas:
         raise ValueError("run_lanes needs one sigma per lane: %d given, the engine has %d lanes" % (len(sigmas), getattr(eng, "lanes", 1)))
-    return _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, True, batch)
+    return _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, True, batch, stage2)
 
 
 def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0, lanes=1, onelaunch=False, batch=False,
-        curve="montgomery", check_every=0):
+        curve="montgomery", check_every=0, stage2="projective"):
     """`curves` curves of run() on a fresh prmers_amd.Engine sized for the chosen D, until one finds a factor.  sigma: the first curve's
     (None: drawn like the others, from random.Random(seed)).  -> the result of the last curve run, with "sigmas": every sigma used.
     lanes = B > 1: the curves run B at a time through run_lanes() on one engine with B lanes (whole batches: `curves` rounded up to a
@@ -443,8 +598,11 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
     batch: run() / run_lanes() with batch=True; needs onelaunch (or the token in `plan`) and implies nothing.
     curve: "montgomery" (the ladder of this module) or "edwards": stage 1 in twisted Edwards coordinates with an on-curve check every
     check_every NAF digits and at its end (prmers_amd/ecm_edwards.py: slower per bit, but a wrong result is seen); the results then carry
-    that driver's further keys."""
+    that driver's further keys.
+    stage2: "projective" or "affine" (run()); D and the engine's registers are chosen for it."""
     from .engine import Engine, resolve_plan
+    _check_mode(stage2)
+    mode = {} if stage2 == "projective" else {"stage2": stage2}
     if curve not in ("montgomery", "edwards"):
         raise ValueError('curve must be "montgomery" or "edwards"')
     if check_every and curve != "edwards":
@@ -453,16 +611,16 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
         from . import ecm_edwards
 
         def run_one(eng, s):
-            return ecm_edwards.run(eng, p, b1, b2, s, D, check_every=check_every, batch=batch)
+            return ecm_edwards.run(eng, p, b1, b2, s, D, check_every=check_every, batch=batch, **mode)
 
         def run_many(eng, ss):
-            return ecm_edwards.run_lanes(eng, p, b1, b2, ss, D, check_every=check_every, batch=batch)
+            return ecm_edwards.run_lanes(eng, p, b1, b2, ss, D, check_every=check_every, batch=batch, **mode)
     else:
         def run_one(eng, s):
-            return run(eng, p, b1, b2, s, D, batch=batch)
+            return run(eng, p, b1, b2, s, D, batch=batch, **mode)
 
         def run_many(eng, ss):
-            return run_lanes(eng, p, b1, b2, ss, D, batch=batch)
+            return run_lanes(eng, p, b1, b2, ss, D, batch=batch, **mode)
     if lanes < 1:
         raise ValueError("lanes must be at least 1")
     if batch and not (onelaunch or "onelaunch" in (plan or "")):
@@ -471,8 +629,8 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
         plan = (plan + "," if plan else "") + "onelaunch"
     if b2 > b1 and D is None:
         n = int(resolve_plan(p, plan).split("n=")[1].split(":")[0])
-        D = choose_D(n, b1, b2, budget // lanes)
-    regs = registers_needed(D) if b2 > b1 else FIXED_REGISTERS
+        D = choose_D(n, b1, b2, budget // lanes, stage2)
+    regs = registers_needed(D, stage2) if b2 > b1 else FIXED_REGISTERS
     rng = random.Random(seed)
     sigmas = []
     res = None
@@ -519,12 +677,16 @@ def main(argv=None):
     ap.add_argument("--curve", choices=("montgomery", "edwards"), default="montgomery",
                     help="edwards: stage 1 in twisted Edwards coordinates with an on-curve check and roll-back (slower per bit)")
     ap.add_argument("--check-every", type=int, default=0, help="with --curve edwards: NAF digits between two checks (0: only at the end of stage 1)")
+    ap.add_argument("--stage2", choices=STAGE2_MODES, default="projective",
+                    help="affine: stage 2 on x-coordinates normalised on the engine, one fused product per pair (small exponents, lane engines)")
     a = ap.parse_args(argv)
     more = {"batch": True} if a.batch else {}
     if a.curve != "montgomery":
         more["curve"] = a.curve
     if a.check_every:
         more["check_every"] = a.check_every
+    if a.stage2 != "projective":
+        more["stage2"] = a.stage2
     res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed, a.lanes, a.onelaunch, **more)
     print(json.dumps(res))
     return 0 if res["factors"] else 1

@@ -101,6 +101,7 @@ def load_library():
         # include/mi355_lanewise.h
         "mi355_lanewise_equal": (C.c_int, [vp, sz, sz, vp, sz]),
         "mi355_lanewise_get_words": (C.c_int, [vp, sz, vp, sz]),
+        "mi355_lanewise_set_words": (C.c_int, [vp, sz, vp, sz]),
         "mi355_lanewise_chunk_lanes": (sz, [sz, sz]),
     }
     for name, (res, args) in sig.items():
@@ -139,8 +140,8 @@ LANE_EXPORTS = ["mi355_lanes_count", "mi355_lanes_set_words", "mi355_lanes_get_w
 BATCH_EXPORTS = ["mi355_batch_begin", "mi355_batch_end", "mi355_batch_stats"]
 
 
-# include/mi355_lanewise.h: compare, or read, every lane of a register in one launch sequence
-LANEWISE_EXPORTS = ["mi355_lanewise_equal", "mi355_lanewise_get_words", "mi355_lanewise_chunk_lanes"]
+# include/mi355_lanewise.h: compare, read or write every lane of a register in one launch sequence
+LANEWISE_EXPORTS = ["mi355_lanewise_equal", "mi355_lanewise_get_words", "mi355_lanewise_set_words", "mi355_lanewise_chunk_lanes"]
 
 
 def resolve_plan(p, spec=None):
@@ -332,6 +333,23 @@ class Engine:
     def get_ints(self, src):
         """[get_int(src, lane=l) for every lane], read in one launch sequence"""
         return [int.from_bytes(row.astype("<u4").tobytes(), "little") for row in self.words_lanes(src)]
+
+    def set_words_lanes(self, dst, w):
+        """lane l of dst = the residue of the words w[l]: an array of lanes x word_count, written in one upload and one launch per chunk of
+        lanes.  dst becomes a register of residues whatever it held."""
+        w = np.ascontiguousarray(w, dtype=np.uint32)
+        if w.shape != (self.lanes, self.word_count):
+            raise ValueError("set_words_lanes wants an array of %d x %d words, not %s" % (self.lanes, self.word_count, w.shape))
+        self._ok(self._lanewise_fn("mi355_lanewise_set_words")(self.h, dst, _ptr(w), w.size))
+
+    def set_ints(self, dst, values):
+        """set_int(dst, values[l], lane=l) for every lane, in one launch sequence; each value is reduced mod 2^p - 1 first"""
+        values = list(values)
+        if len(values) != self.lanes:
+            raise ValueError("set_ints wants one value per lane: %d given, the engine has %d lanes" % (len(values), self.lanes))
+        mp, size = (1 << self.p) - 1, self.word_count * 4
+        raw = b"".join((int(v) % mp).to_bytes(size, "little") for v in values)
+        self.set_words_lanes(dst, np.frombuffer(raw, dtype="<u4").reshape(self.lanes, self.word_count))
 
     def pow(self, dst, src, e):
         """dst = src^e, src is erased (engine.h:160-170)."""
