@@ -4,6 +4,7 @@
 #include "../../include/mi355_lanes.h"
 #include "../../include/mi355_batch.h"
 #include "../../include/mi355_lanewise.h"
+#include "../../include/mi355_lanecross.h"
 
 #include <cctype>
 #include <cstring>
@@ -245,6 +246,11 @@ int mi355_lanewise_set_words(mi355_engine_handle h, size_t dst, const uint32_t* 
   return guarded([&] { if (!w) throw std::runtime_error("lanewise_set_words: null buffer"); m(h)->set_words_lanes(dst, w, count); });
 }
 size_t mi355_lanewise_chunk_lanes(size_t n, size_t lanes) { return mi355::canon_chunk_lanes(n, lanes); }
+
+// ---- include/mi355_lanecross.h ----
+int mi355_lanecross_mul_sibling(mi355_engine_handle h, size_t dst, size_t src, size_t alt, uint32_t level) {
+  return guarded([&] { m(h)->mul_sibling(dst, src, alt, level); });
+}
 
 // ---- include/mi355_batch.h ----
 int mi355_batch_begin(mi355_engine_handle h) { return guarded([&] { m(h)->batch_begin(); }); }

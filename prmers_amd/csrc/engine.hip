@@ -250,14 +250,17 @@ void Engine::run_back(size_t r, uint32_t a, hipEvent_t* ev) {
 // into digits(r) with factor a and the extras of back_ext, all in one launch.  The new run carries go to a spare buffer: the launch reads
 // the pending ones of r and of the addend, which may be r itself.  Such plans have runs of four digits or more (plan.hpp), so the carries
 // stay pending.
-void Engine::one_launch(size_t r, int mode, const uint64_t* y, const uint64_t* y2, uint64_t* img, uint32_t a, long copy_to, long add_src) {
+// mode kModeSibling (mul_sibling): y is read at the lane's sibling of `level`, y2 at the own lane.  Never queued: the sibling's image may
+// be what another work-group of the running queue stores, so the queue runs first (stream()) and this is a launch of its own.
+void Engine::one_launch(size_t r, int mode, const uint64_t* y, const uint64_t* y2, uint64_t* img, uint32_t a, long copy_to, long add_src, uint32_t level) {
   OneLaunchArgs oa;
   oa.src = digits(r); oa.src_cbuf = pending_carry_[r] ? cbuf(r) : nullptr;
-  oa.y = y; oa.y2 = y2; oa.img = img; oa.a = a; oa.mode = mode;
+  oa.y = y; oa.y2 = y2; oa.img = img; oa.a = a; oa.mode = mode; oa.level = level;
   oa.TL = one_.TL; oa.K = one_.K; oa.groups = one_.groups;
+  const bool queued = batching_ && mode != kModeSibling;
   BackExt x;
   if (mode == 2) {
-    if (batching_) { BatchOp& op = batch_slot(); op.kind = BatchOp::kProduct; op.oa = oa; }
+    if (queued) { BatchOp& op = batch_slot(); op.kind = BatchOp::kProduct; op.oa = oa; }
     else HIPCHK(launch_onelaunch(dp_, oa, x, stream()));
     return;
   }
@@ -265,7 +268,7 @@ void Engine::one_launch(size_t r, int mode, const uint64_t* y, const uint64_t* y
   if (add_src >= 0) { x.add_digits = digits(size_t(add_src)); x.add_cbuf = pending_carry_[size_t(add_src)] ? cbuf(size_t(add_src)) : nullptr; }
   uint64_t* fresh = take_spare_cbuf();
   oa.dst = digits(r); oa.dst_cbuf = fresh;
-  if (batching_) { BatchOp& op = batch_slot(); op.kind = BatchOp::kProduct; op.oa = oa; op.x = x; }   // the pointers as they are resolved now
+  if (queued) { BatchOp& op = batch_slot(); op.kind = BatchOp::kProduct; op.oa = oa; op.x = x; }   // the pointers as they are resolved now
   else HIPCHK(launch_onelaunch(dp_, oa, x, stream()));
   adopt_cbuf(r, fresh);
   kind_[r] = kDigits; pending_carry_[r] = 1;
@@ -450,7 +453,14 @@ void Engine::put_words(size_t dst, const uint32_t* w, size_t count, size_t lane0
     // the words go up as they are and are cut into digits on the device (canon.hip k_unpack_words), straight into tile-major order
     uint32_t* dw = reinterpret_cast<uint32_t*>(work());
     HIPCHK(hipMemcpyAsync(dw, w, count * 4, hipMemcpyHostToDevice, stream()));
-    for (size_t l = lane0; l < lane1; ++l) HIPCHK(canon_unpack_words(cg_, dw, digits(dst, l), stream()));
+    HIPCHK(canon_unpack_words(cg_, dw, digits(dst, lane0), stream()));
+    // The same value on every lane (set_words on a lane engine; the broadcast of prmers_amd/lanecross.py): the first lane is cut into digits,
+    // the others are copies of it, doubling -- log2 B copies where a launch a lane was 512 launches.  Whole lanes of 8 n bytes: what lies
+    // behind a lane's 4 n bytes of digits is read by nothing while the register holds digits.
+    for (size_t have = 1; have < lane1 - lane0; have *= 2) {
+      const size_t more = std::min(have, lane1 - lane0 - have);
+      HIPCHK(hipMemcpyAsync(slot_[dst] + (lane0 + have) * reg_bytes_, slot_[dst] + lane0 * reg_bytes_, more * reg_bytes_, hipMemcpyDeviceToDevice, stream()));
+    }
     HIPCHK(hipStreamSynchronize(stream()));
     return;
   }
@@ -659,6 +669,19 @@ void Engine::mul(size_t dst, size_t src, uint32_t a) {
     run_back(dst, a > pl_.a_fast ? 1u : a);
   }
   if (a > pl_.a_fast) scale(dst, a);
+}
+
+// dst[l] = dst[l] x src[sibling of l at `level`] where that lane exists, else dst[l] x alt[l] (include/mi355_lanecross.h): mul with factor 1
+// whose row sweep takes its image from another lane (kernels.hip k_middle_sibling / k_onelaunch_sibling).  Everything is checked before the
+// first launch.  Inside a batch the queue runs first (one_launch, stream()).
+void Engine::mul_sibling(size_t dst, size_t src, size_t alt, uint32_t level) {
+  if (lanes_ == 1) { RegisterMachine::mul_sibling(dst, src, alt, level); return; }   // no sibling in range: mul(dst, alt)
+  check_mul_sibling(dst, src, alt, level);
+  HIPCHK(hipSetDevice(device_));
+  if (pl_.onelaunch) { one_launch(dst, kModeSibling, image(src), image(alt), nullptr, 1, -1, -1, level); return; }
+  run_front(dst);
+  HIPCHK(launch_middle_sibling(dp_, work(), image(src), image(alt), work(), level, stream()));
+  run_back(dst, 1);
 }
 
 // r = r x a, run-wise (kernels.hip k_scale): the factors above the plan's fused bound follow the operation with factor 1

@@ -52,6 +52,8 @@ class Engine final : public RegisterMachine {
   void set_multiplicand(size_t dst, size_t src) override;
   void square_mul(size_t r, uint32_t a) override;
   void mul(size_t dst, size_t src, uint32_t a) override;
+  // across lanes (include/mi355_lanecross.h): mul by the image of the lane's sibling block's first lane, by alt's own-lane image where there is none
+  void mul_sibling(size_t dst, size_t src, size_t alt, uint32_t level) override;
   void add(size_t dst, size_t src) override;
   void sub_reg(size_t dst, size_t src) override;
   void sub_u32(size_t r, uint32_t v) override;
@@ -132,7 +134,7 @@ class Engine final : public RegisterMachine {
   void adopt_cbuf(size_t r, uint64_t* fresh);       // r's pending carries are now in `fresh`; its old buffer becomes spare
   void back_ext(size_t dst, uint32_t a, long copy_to, long add_src);
   // a whole product in one launch (plan token onelaunch): front, rows in `mode`, back with factor a and the extras of back_ext
-  void one_launch(size_t r, int mode, const uint64_t* y, const uint64_t* y2, uint64_t* img, uint32_t a, long copy_to, long add_src);
+  void one_launch(size_t r, int mode, const uint64_t* y, const uint64_t* y2, uint64_t* img, uint32_t a, long copy_to, long add_src, uint32_t level = 0);
   void normalize(size_t r);          // apply deferred run carries
   void carry_fix_now(size_t r, int excess = -1);   // run carries into the digits right away (plans with runs of two digits cannot defer
                                                    // them); excess: bits of a carry word above the first digit's width (-1: a <= 15)

@@ -384,6 +384,17 @@ __global__ void __launch_bounds__(1024) k_middle_keep(DevPlan pl, const uint64_t
   middle_body<true>(pl, lane_reg<LANES>(pl, Win), nullptr, nullptr, lane_reg<LANES>(pl, Wout), 0, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x,
                     lane_reg<LANES>(pl, Wimg));
 }
+// Across lanes (include/mi355_lanecross.h): the one place where a lane reads another lane's data.  The sibling block of size 2^level of
+// lane l starts at lane ((l >> level) ^ 1) << level (level <= 31, so below 2^32 for every lane an engine can have; 64 bits all the same).
+__device__ __forceinline__ uint64_t sibling_lane(uint32_t lane, uint32_t level) { return ((uint64_t(lane) >> level) ^ 1u) << level; }
+// mode 1 whose multiplicand image is the sibling lane's image of Ysrc where that lane exists, else the own lane's image of Yalt (lane
+// engines only: the lane is blockIdx.y).  Ysrc, Yalt are those of lane 0; a lane is pl.n words of 8 bytes, offsets in 64 bits.
+__global__ void __launch_bounds__(1024) k_middle_sibling(DevPlan pl, const uint64_t* __restrict__ Win, const uint64_t* __restrict__ Ysrc,
+                                                        const uint64_t* __restrict__ Yalt, uint64_t* __restrict__ Wout, uint32_t level) {
+  const uint64_t g = sibling_lane(blockIdx.y, level);
+  const uint64_t* Y = g < pl.lanes ? Ysrc + g * pl.n : Yalt + uint64_t(blockIdx.y) * pl.n;
+  middle_body(pl, lane_reg<true>(pl, Win), Y, nullptr, lane_reg<true>(pl, Wout), 1, blockIdx.x, reinterpret_cast<P2*>(smem_raw), threadIdx.x, blockDim.x);
+}
 
 // ---------------------------------------------------------------------------------------------
 // back: inverse of front + unweight + carry over the tile's M1 runs of 2C digits
@@ -543,7 +554,10 @@ __device__ __forceinline__ LanePlace lane_place(const DevPlan& pl, uint32_t TL, 
 // The three phases of a product for the thread at t, for k_onelaunch and k_batch alike.  again() hands out plan, operands and extras anew
 // (a view of three references behind a pointer the compiler does not see through); every trip of every phase asks for them, so nothing of
 // one phase is held in scalar registers through another.  Every thread of the group reaches every barrier; mode 2 ends after the rows.
-template <bool EXT, class Again>
+// SIB (k_onelaunch_sibling only; oa.mode is kModeSibling): the rows multiply by the image at oa.y of the lane's sibling of oa.level where
+// that lane exists, else by the own lane's image at oa.y2.  The choice is the thread's: the lanes of a group, and of a wave where TL < 64,
+// have different partners.  A lane beyond the last one multiplies by the last lane's choice, like everything it does.
+template <bool EXT, bool SIB = false, class Again>
 __device__ __forceinline__ void product_phases(const LanePlace& t, Again again) {
   for (uint32_t T = t.cteam; T < t.NT; T += t.cteams) {
     const auto& g = again();
@@ -557,6 +571,11 @@ __device__ __forceinline__ void product_phases(const LanePlace& t, Again again) 
     uint64_t* img = lane_at(g.oa.img, t.lane, t.rb);
     if (mode == 2) middle_body(g.pl, t.W, nullptr, nullptr, img, 2, row, t.Xr, t.rtid, t.rt, nullptr, t.live);
     else if (mode == 4) middle_body<true>(g.pl, t.W, nullptr, nullptr, t.W, 0, row, t.Xr, t.rtid, t.rt, img, t.live);
+    else if constexpr (SIB) {
+      const uint64_t sib = sibling_lane(t.lane, g.oa.level);
+      const uint64_t* y = sib < g.pl.lanes ? lane_at(g.oa.y, uint32_t(sib), t.rb) : lane_at(g.oa.y2, t.lane, t.rb);   // (lane x bytes in 64 bits)
+      middle_body(g.pl, t.W, y, nullptr, t.W, 1, row, t.Xr, t.rtid, t.rt);
+    }
     else middle_body(g.pl, t.W, lane_at(g.oa.y, t.lane, t.rb), lane_at(g.oa.y2, t.lane, t.rb), t.W, int(mode), row, t.Xr, t.rtid, t.rt);
     __syncthreads();
   }
@@ -582,6 +601,15 @@ __global__ void __launch_bounds__(1024) k_onelaunch(OneLaunchPack) {
     t = lane_place(g.pl, g.oa.TL, g.oa.K);
   }
   product_phases<EXT>(t, OneLaunchAgain());
+}
+// the product by a sibling lane's image (product_phases SIB): an entry point of its own, k_onelaunch and k_batch keep their code
+__global__ void __launch_bounds__(1024) k_onelaunch_sibling(OneLaunchPack) {
+  LanePlace t;
+  {
+    const OneLaunchPack& g = args_again();
+    t = lane_place(g.pl, g.oa.TL, g.oa.K);
+  }
+  product_phases<false, true>(t, OneLaunchAgain());
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -934,6 +962,12 @@ hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t*
   else hipLaunchKernelGGL(pl.lanes > 1 ? k_middle<true> : k_middle<false>, grid, block, size_t(pl.M2) * 16, s, pl, Win, Y, Y2, Wout, mode);
   return hipGetLastError();
 }
+// the row sweep of a product by a sibling lane's image (k_middle_sibling): lane engines only, grid and block of launch_middle
+hipError_t launch_middle_sibling(const DevPlan& pl, const uint64_t* Win, const uint64_t* Ysrc, const uint64_t* Yalt, uint64_t* Wout, uint32_t level, hipStream_t s) {
+  if (pl.lanes < 2 || level > 31 || !Ysrc || !Yalt) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_middle_sibling, dim3(pl.M1, pl.lanes), dim3(block_for_small(pl, pl.M2)), size_t(pl.M2) * 16, s, pl, Win, Ysrc, Yalt, Wout, level);
+  return hipGetLastError();
+}
 template <bool EXT>
 static hipError_t launch_back_of(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s) {
   const size_t tile = size_t(pl.M1) * pl.C;
@@ -950,7 +984,12 @@ hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digit
 constexpr size_t kOneLaunchMaxLds = 128 * 1024;   // n = 8192: 4096 pairs of work buffer and as much scratch
 hipError_t launch_onelaunch(const DevPlan& pl, const OneLaunchArgs& oa, const BackExt& x, hipStream_t s) {
   const size_t lds = size_t(oa.K) * pl.m * 32;
-  if (oa.mode < 0 || oa.mode > 4 || !oa.TL || !oa.K || oa.K * oa.TL > 1024 || lds > kOneLaunchMaxLds || size_t(oa.groups) * oa.K < pl.lanes) return hipErrorInvalidValue;
+  if (oa.mode < 0 || oa.mode > kModeSibling || !oa.TL || !oa.K || oa.K * oa.TL > 1024 || lds > kOneLaunchMaxLds || size_t(oa.groups) * oa.K < pl.lanes) return hipErrorInvalidValue;
+  if (oa.mode == kModeSibling) {   // no extras, both images, a level that keeps the sibling's lane below 2^32
+    if (x.any() || !oa.y || !oa.y2 || oa.level > 31) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_onelaunch_sibling, dim3(oa.groups), dim3(oa.K * oa.TL), lds, s, OneLaunchPack{pl, oa, x});
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(x.any() ? k_onelaunch<true> : k_onelaunch<false>, dim3(oa.groups), dim3(oa.K * oa.TL), lds, s, OneLaunchPack{pl, oa, x});
   return hipGetLastError();
 }
@@ -1029,6 +1068,8 @@ hipError_t configure_kernels(size_t lds_front, size_t lds_mid, uint32_t lanes, b
   if (e == hipSuccess && onelaunch) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_onelaunch<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kOneLaunchMaxLds));
   if (e == hipSuccess && onelaunch) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_onelaunch<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kOneLaunchMaxLds));
   if (e == hipSuccess && onelaunch) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch), hipFuncAttributeMaxDynamicSharedMemorySize, int(kOneLaunchMaxLds));
+  if (e == hipSuccess && onelaunch && lanes > 1) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_onelaunch_sibling), hipFuncAttributeMaxDynamicSharedMemorySize, int(kOneLaunchMaxLds));
+  if (e == hipSuccess && lanes > 1 && lds_mid > 48 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_middle_sibling), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_mid));
   return e;
 }
 

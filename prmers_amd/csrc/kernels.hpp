@@ -97,6 +97,9 @@ struct ColSweeps { FrontFn front; BackFn back; BackExtFn back_ext; FourStepFn bu
 hipError_t configure_kernels(size_t lds_front, size_t lds_mid, uint32_t lanes, bool onelaunch);
 hipError_t launch_front(const DevPlan& pl, const uint32_t* digits, const uint64_t* cbuf_in, uint64_t* W, hipStream_t s);
 hipError_t launch_middle(const DevPlan& pl, const uint64_t* Win, const uint64_t* Y, const uint64_t* Y2, uint64_t* Wimg, uint64_t* Wout, int mode, hipStream_t s);
+// rows in mode 1 with the image of lane l read from Ysrc at l's sibling lane of `level` where that lane exists, else from Yalt at lane l
+// (include/mi355_lanecross.h; k_middle_sibling).  Lane engines only, level <= 31.
+hipError_t launch_middle_sibling(const DevPlan& pl, const uint64_t* Win, const uint64_t* Ysrc, const uint64_t* Yalt, uint64_t* Wout, uint32_t level, hipStream_t s);
 hipError_t launch_back(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, hipStream_t s);
 hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digits, uint64_t* cbuf, uint32_t a, const BackExt& x, hipStream_t s);
 // One-launch products (plan token onelaunch, n <= 8192; kernels.hip k_onelaunch): front sweep, row sweep and back sweep of a lane in one
@@ -104,13 +107,18 @@ hipError_t launch_back_ext(const DevPlan& pl, const uint64_t* W, uint32_t* digit
 //   src (+ src_cbuf: its pending run carries, nullable) -> front; rows in `mode` (the modes of RowsFn above: y, y2 read in modes 1 and 3, img
 //   written in modes 2 and 4); unless mode 2: back into dst, dst_cbuf with factor a and the extras x.  dst may be src: a lane's digits are all
 //   read before the first is written.  dst_cbuf must not be src_cbuf or x.add_cbuf.
+//   mode kModeSibling (lane engines; k_onelaunch_sibling, a launch of its own, never a descriptor of a batch): mode 1 whose image is read at y
+//   from the lane's sibling of `level` -- lane ((l >> level) ^ 1) << level -- where that lane exists, else at y2 from the own lane; no extras.
+constexpr int kModeSibling = 5;
 struct OneLaunchArgs {
   const uint32_t* src = nullptr; const uint64_t* src_cbuf = nullptr;
   const uint64_t* y = nullptr; const uint64_t* y2 = nullptr; uint64_t* img = nullptr;
   uint32_t* dst = nullptr; uint64_t* dst_cbuf = nullptr;
   uint32_t a = 1; int mode = 0;
   uint32_t TL = 0, K = 0, groups = 0;
+  uint32_t level = 0;   // kModeSibling only.  In what was padding: the size and every other member's offset are what they were
 };
+static_assert(sizeof(OneLaunchArgs) == 80, "OneLaunchArgs: the level sits in the padding, the argument block of the existing kernels is unchanged");
 hipError_t launch_onelaunch(const DevPlan& pl, const OneLaunchArgs& oa, const BackExt& x, hipStream_t s);
 // Batches (kernels.hip k_batch): a run of register operations of a one-launch engine as ONE launch with the grid, block and
 // LDS of k_onelaunch.  Every work-group walks the descriptors in order for its own lanes, a group barrier after each.  All pointers are

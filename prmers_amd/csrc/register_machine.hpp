@@ -74,6 +74,16 @@ class RegisterMachine {
     set_words(dst, w, count);
   }
 
+  // Across lanes (include/mi355_lanecross.h): dst[l] = dst[l] * src[g] with g = ((l >> level) ^ 1) << level, the first lane of l's sibling
+  // block of size 2^level, where g is a lane; dst[l] * alt[l] where it is not.  src and alt are multiplicand images, the factor is 1.
+  // A machine with one lane has no sibling in range at any level, so the operation is mul(dst, alt): written here, once, for both
+  // families.  An engine with lanes overrides it.  Checked before the first launch.
+  virtual void mul_sibling(size_t dst, size_t src, size_t alt, uint32_t level) {
+    check_mul_sibling(dst, src, alt, level);
+    if (lanes() != 1) throw std::runtime_error("mul_sibling: not implemented for this engine with lanes");
+    mul(dst, alt, 1);
+  }
+
   // Batches (include/mi355_batch.h): the register operations between batch_begin and batch_end run as one launch.  Only the Goldilocks
   // engine with one-launch products has them (engine.hpp); stats: operations queued so far, batch launches so far, capacity, pending now.
   virtual void batch_begin() { throw std::runtime_error("batch_begin: batches are not implemented for the crt field family"); }
@@ -188,6 +198,12 @@ class RegisterMachine {
     need_residue(dst, "mul_sum"); need_image(src_a, "mul_sum"); need_image(src_b, "mul_sum"); need_register(tmp, "mul_sum");
     if (dst == tmp || tmp == src_a || tmp == src_b)
       throw std::runtime_error("mul_sum: dst, tmp and the multiplicands must be different registers (src_a == src_b is allowed)");
+  }
+  void check_mul_sibling(size_t dst, size_t src, size_t alt, uint32_t level) const {
+    need_register(dst, "mul_sibling"); need_register(src, "mul_sibling"); need_register(alt, "mul_sibling");
+    if (dst == src || dst == alt) throw std::runtime_error("mul_sibling: dst must differ from src and from alt (src == alt is allowed)");
+    need_residue(dst, "mul_sibling"); need_image(src, "mul_sibling"); need_image(alt, "mul_sibling");
+    if (level > 31) throw std::runtime_error("mul_sibling: level must be at most 31 (a sibling block has 2^level lanes)");
   }
   void check_square_mul_prepare(size_t src, size_t img_out, uint32_t factor) const {
     need_residue(src, "square_mul_prepare"); need_register(img_out, "square_mul_prepare"); need_factor(factor, "square_mul_prepare");

@@ -1,7 +1,7 @@
 """ECM factoring of a Mersenne number 2^p - 1 on the engine: Montgomery curves, stages 1 and 2 (the reference: src/modes/RunEcm.cpp).
 
     python -m prmers_amd.ecm P B1 [B2] [--sigma S] [--curves N] [--lanes B] [--D 30|210|2310] [--plan SPEC] [--onelaunch] [--batch] [--device N]
-                             [--curve montgomery|edwards] [--check-every N] [--stage2 projective|affine]
+                             [--curve montgomery|edwards] [--check-every N] [--stage2 projective|affine] [--inverse host|engine]
 
 Curve:    Suyama's parametrisation from sigma: u = sigma^2 - 5, v = 4 sigma, the point (u^3 : v^3) on B y^2 = x^3 + A x^2 + x with
           a24 = (A + 2) / 4 = (v - u)^3 (3 u + v) / (16 u^3 v).  The start is taken affine, x0 = u^3 / v^3 and Z = 1: one modular inversion
@@ -33,6 +33,14 @@ Affine:   stage2="affine" / --stage2 affine works on x = X / Z instead: the tabl
           along.  The host keeps zacc = prod c_m per lane and g2 = gcd(A zacc, Mp) with g1 divided out: the Z product finds a factor
           modulo which some point is the point at infinity -- which is also how the k = 0 pairs are covered (q = j divides the order
           exactly when Z_j vanishes), so no pair is walked for k = 0.  Opt-in; the default stays projective.
+Engine inverse:  inverse="engine" / --inverse engine (affine only, an engine with mul_sibling, include/mi355_lanecross.h): the read of
+          c_m on every lane, the host's inversions and the write of every lane become lanecross.invert -- Montgomery's trick ACROSS the
+          lanes on the engine, 2 ceil(log2 B) products by a sibling lane's image, one lane read, ONE host inversion and one broadcast
+          write a block whatever B is.  The Z product stays on the engine too: ZACC <- ZACC c_m a block (one set_multiplicand, one
+          product) and A ZACC is formed there at the end and read once.  A block in which some lane's c_m has no inverse (a point at
+          infinity, a factor in a Z) makes the product over the lanes non-invertible: that block runs the host's way, with the same
+          inverses as before (1 for the lanes without one), and is counted in "inverse_fallbacks".  Inverses are unique, so g1, g2,
+          the accumulator and "normalised" are those of inverse="host".  L + 3 registers on top (registers_needed).  Opt-in too.
 
 The driver works on anything with the interface of prmers_amd.Engine; addsub and square_mul_prepare are used when the object has them
 and replaced by the compositions they stand for when it has not.
@@ -87,22 +95,45 @@ def _check_mode(stage2):
         raise ValueError('stage2 must be "projective" or "affine"')
 
 
-def registers_needed(D, stage2="projective"):
+INVERSE_MODES = ("host", "engine")
+
+
+def _check_inverse(inverse, stage2):
+    if inverse not in INVERSE_MODES:
+        raise ValueError('inverse must be "host" or "engine"')
+    if inverse == "engine" and stage2 != "affine":
+        raise ValueError('inverse="engine" belongs to stage2="affine": the projective stage 2 inverts nothing')
+
+
+def _check_engine_inverse(eng, inverse, stage2):
+    """_check_inverse, and for "engine" that the object has the product across lanes"""
+    _check_inverse(inverse, stage2)
+    if inverse == "engine" and getattr(eng, "mul_sibling", None) is None:
+        raise ValueError('inverse="engine" needs an engine with mul_sibling (include/mi355_lanecross.h); this object has none')
+
+
+def registers_needed(D, stage2="projective", lanes=1, inverse="host"):
     """registers of an engine that runs stage 2 with this D: images of X_j and Z_j for every j in J plus FIXED_REGISTERS; for
     stage2="affine" X_j, Z_j and the prefix product c_j for every j in J plus FIXED_REGISTERS -- nothing on top: the running inverse of a
-    normalisation lives in R_U, a temporary of the point additions, which do not run meanwhile"""
+    normalisation lives in R_U, a temporary of the point additions, which do not run meanwhile.  inverse="engine" on `lanes` lanes adds
+    L + 3, L = ceil(log2 lanes): the Z product and the L + 2 of lanecross.invert (its copy, the image of 1, an image a level)"""
     if D not in D_CHOICES:
         raise ValueError("D must be one of %s" % (D_CHOICES,))
     _check_mode(stage2)
-    return (3 if stage2 == "affine" else 2) * len(residues(D)) + FIXED_REGISTERS
+    _check_inverse(inverse, stage2)
+    more = 0
+    if inverse == "engine":
+        from . import lanecross
+        more = 1 + lanecross.registers_needed(lanes)
+    return (3 if stage2 == "affine" else 2) * len(residues(D)) + FIXED_REGISTERS + more
 
 
-def choose_D(n, b1, b2, budget=DEFAULT_BUDGET, stage2="projective"):
-    """the largest D whose register file (registers_needed(D, stage2) + the engine's work buffer, 8 n bytes each) fits `budget` bytes and
-    that is not wider than the interval (B1, B2] itself"""
+def choose_D(n, b1, b2, budget=DEFAULT_BUDGET, stage2="projective", lanes=1, inverse="host"):
+    """the largest D whose register file (registers_needed(D, stage2, lanes, inverse) + the engine's work buffer, 8 n bytes each) fits
+    `budget` bytes and that is not wider than the interval (B1, B2] itself"""
     best = D_CHOICES[0]
     for D in D_CHOICES[1:]:
-        if (registers_needed(D, stage2) + 1) * 8 * n <= budget and D <= max(b2 - b1, D_CHOICES[0]):
+        if (registers_needed(D, stage2, lanes, inverse) + 1) * 8 * n <= budget and D <= max(b2 - b1, D_CHOICES[0]):
             best = D
     return best
 
@@ -337,13 +368,18 @@ class _Curve:
                 self.add(r1, r0, r1, pt); self.dbl(r0, r0)
 
 
-def _stage2_affine(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, put, use_gmp):
+def _stage2_affine(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, put, use_gmp, inverse="host"):
     """_stage2 with stage2="affine" (the module's docstring): tables of x-coordinates, one mul_sum per pair.
+    inverse="engine": a block's inverses by lanecross.invert and the Z product in a register (the module's docstring, "Engine inverse").
     -> the keys an affine run adds to its results"""
     mp = (1 << p) - 1
     lanes = range(len(failed))
     Q = (R_XQ, R_ZQ)
     info = {"stage2": "affine", "fused_sum": ops.fused_sum, "normalised": 0}
+    on_engine = inverse == "engine"
+    if on_engine:
+        from . import lanecross
+        info.update({"inverse": "engine", "inverse_fallbacks": 0})
     pairs = stage2_pairs(b1, b2, D)
     if not pairs or not any(g1[l] != mp for l in lanes if not failed[l]):
         return info
@@ -353,6 +389,9 @@ def _stage2_affine(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, put
     free = [r for t in triple for r in t[1:]]
     giant = [tuple(free[3 * i:3 * i + 3]) for i in range(max(1, len(free) // 3))]
     zacc = [1] * len(failed)
+    if on_engine:        # behind the table: the Z product, then lanecross.invert's copy, image of 1 and an image a level
+        R_ZACC = FIXED_REGISTERS + 3 * len(J)
+        cross = list(range(R_ZACC + 1, R_ZACC + 1 + lanecross.registers_needed(len(failed))))
 
     def normalise(block, negate):
         """block: register triples (X, Z, C) with a point (X : Z) in the first two.  Afterwards X holds the image of x = X / Z (of -x
@@ -362,11 +401,18 @@ def _stage2_affine(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, put
         for i in range(1, len(block)):
             X, Z, C = block[i]
             ops.prep(Z, Z); eng.copy(C, c[i - 1]); ops.mul(C, Z)
-        cms = get(c[-1])
-        for l, cm in enumerate(cms):
-            zacc[l] = zacc[l] * cm % mp
-        us = [u or 1 for u in mod_inverses(cms, mp, use_gmp)]    # a lane without an inverse rides along on 1: its factor is in zacc
-        put(R_U, [mp - u for u in us] if negate else us)
+        done = False
+        if on_engine:
+            ops.prep(R_IT, c[-1]); ops.mul(R_ZACC, R_IT)         # the Z product stays on the engine
+            done = lanecross.invert(eng, c[-1], R_U, cross, negate, use_gmp, ops)[0]
+            info["inverse_fallbacks"] += not done                # some lane's c_m has no inverse: this block the host's way
+        if not done:
+            cms = get(c[-1])
+            if not on_engine:
+                for l, cm in enumerate(cms):
+                    zacc[l] = zacc[l] * cm % mp
+            us = [u or 1 for u in mod_inverses(cms, mp, use_gmp)]    # a lane without an inverse rides along on 1: its factor is in zacc
+            put(R_U, [mp - u for u in us] if negate else us)
         for i in range(len(block) - 1, 0, -1):
             X, Z, C = block[i]
             ops.prep(R_IT, R_U); ops.mul(c[i - 1], R_IT)         # inv_i = u c_(i-1)
@@ -378,6 +424,9 @@ def _stage2_affine(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, put
         info["normalised"] += len(block)
 
     with batched():
+        if on_engine:
+            lanecross.prepare_one(eng, cross[1])
+            eng.set(R_ZACC, 1)
         two = (R_X2, R_Z2)
         cv.dbl(two, Q)
         # baby points: the odd multiples of Q as residues, then one block of the normalisation: the table holds images of -x_j
@@ -417,7 +466,9 @@ def _stage2_affine(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, put
             for kk, t in block:
                 for j in pairs[kk]:
                     ops.mul_sum(R_A, t[0], slot[j], R_T)         # A <- A (x_k + (-x_j))
-    for l, acc in enumerate(get(R_A)):
+        if on_engine:                                            # A zacc, formed on the engine beside A
+            ops.prep(R_IT, R_ZACC); eng.copy(R_T, R_A); ops.mul(R_T, R_IT)
+    for l, acc in enumerate(get(R_T if on_engine else R_A)):
         if not failed[l] and g1[l] != mp:
             v = acc * zacc[l] % mp
             g = mp if v == 0 else big_gcd(v, mp, use_gmp)
@@ -425,13 +476,15 @@ def _stage2_affine(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, put
     return info
 
 
-def _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, put=None, stage2="projective"):
+def _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, put=None, stage2="projective", inverse="host"):
     """Stage 2 on the stage-1 point in (R_XQ, R_ZQ) of the Montgomery curve whose a24 is the image in R_A24, for both drivers (this one
     and ecm_edwards): the table of baby points, the giant steps and the accumulator, then g2[l] for every lane that has a stage 2.
     batched() opens a batch or nothing, get(reg) reads every lane, put(reg, values) writes every lane (stage2="affine" only).
+    inverse: "host" or, for stage2="affine" on an object with mul_sibling, "engine".
     -> the keys the mode adds to the results (none for "projective")"""
+    _check_engine_inverse(eng, inverse, stage2)
     if stage2 == "affine":
-        return _stage2_affine(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, put, use_gmp)
+        return _stage2_affine(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, put, use_gmp, inverse)
     mp = (1 << p) - 1
     lanes = range(len(failed))
     Q = (R_XQ, R_ZQ)
@@ -486,12 +539,15 @@ def _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, p
                 g2[l] = g // big_gcd(g, g1[l], use_gmp)
 
 
-def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=False, mode="projective"):
+def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=False, mode="projective", inverse="host"):
     """The curves of `sigmas` through one sequence of engine calls: the ladder bits come from B1 and the stage-2 pairs from (B1, B2, D),
     so only the data differ.  by_lane=False: one curve on an engine used as it is (run).  by_lane=True: curve l in lane l of an engine
     with len(sigmas) lanes (run_lanes); every engine call then acts on all of them.  batch: the ladder and the stage-2 loops run inside
-    eng.batch() where the object has one (else as without).  mode: the stage 2, "projective" or "affine".  -> one result per curve"""
+    eng.batch() where the object has one (else as without).  mode: the stage 2, "projective" or "affine"; inverse: who inverts in the affine
+    one, "host" or "engine".  -> one result per curve"""
     _check_mode(mode)
+    _check_engine_inverse(eng, inverse, mode)
+    size = {"lanes": len(sigmas), "inverse": inverse} if inverse != "host" else {}
     if b1 < 2:
         raise ValueError("B1 must be at least 2")
     if min(sigmas) < SIGMA_MIN:
@@ -501,11 +557,11 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=Fa
     stage2 = b2 > b1
     if stage2:
         if D is None:
-            D = max([d for d in D_CHOICES if have is None or registers_needed(d, mode) <= have] or [0])
-            D = min(D, choose_D(eng.n, b1, b2, stage2=mode)) if D else 0
+            D = max([d for d in D_CHOICES if have is None or registers_needed(d, mode, **size) <= have] or [0])
+            D = min(D, choose_D(eng.n, b1, b2, stage2=mode, **size)) if D else 0
         if D not in D_CHOICES:
             raise ValueError("stage 2 needs D in %s and an engine with registers_needed(D) registers" % (D_CHOICES,))
-    need = registers_needed(D, mode) if stage2 else FIXED_REGISTERS
+    need = registers_needed(D, mode, **size) if stage2 else FIXED_REGISTERS
     if have is not None and have < need:
         raise ValueError("the engine has %d registers, ECM with D = %s needs %d" % (have, D if stage2 else None, need))
     ops = _Ops(eng, use_fused)
@@ -556,11 +612,11 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=Fa
 
     more2 = None
     if stage2:
-        more2 = _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, put, mode)
+        more2 = _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, put, mode, inverse)
     return results(g1, g2, more2)
 
 
-def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None, batch=False, stage2="projective"):
+def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None, batch=False, stage2="projective", inverse="host"):
     """One curve of ECM on 2^p - 1 with bounds B1 and B2 (B2 <= B1: stage 1 only) on `eng`, an engine for exponent p with at least
     FIXED_REGISTERS registers (stage 1) or registers_needed(D) (stage 2).  use_fused=False forces set_multiplicand + square_mul in
     place of square_mul_prepare.  Afterwards registers R_XQ, R_ZQ hold the stage-1 point.  batch=True: the ladder and the stage-2 loops
@@ -570,24 +626,28 @@ def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None,
     mul_sum is one product) and "normalised" (points normalised).  The prime factors it finds are those of the projective stage 2 and
     those modulo which a baby or giant point is the point at infinity.  It is meant for small exponents on lane engines: every block of
     points costs one modular inversion per lane on the host, which at exponents in the millions is minutes.
+    inverse="engine" (with stage2="affine", on an object with mul_sibling): a block's inverses by Montgomery's trick across the lanes on
+    the engine, one host inversion a block whatever the lane count, and the Z product kept in a register (prmers_amd/lanecross.py); the
+    engine then needs registers_needed(D, "affine", lanes, "engine") registers and the result has "inverse": "engine" and
+    "inverse_fallbacks", the blocks that went the host's way because some lane's product had no inverse.  Same g1, g2 and accumulator.
     -> {p, b1, b2, D, sigma, factors, g1, g2, squarings, products, prepares, fused}"""
-    return _run_curves(eng, p, b1, b2, [sigma], D, use_fused, use_gmp, False, batch, stage2)[0]
+    return _run_curves(eng, p, b1, b2, [sigma], D, use_fused, use_gmp, False, batch, stage2, inverse)[0]
 
 
-def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None, batch=False, stage2="projective"):
+def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None, batch=False, stage2="projective", inverse="host"):
     """len(sigmas) == eng.lanes curves at once on an engine with lanes (Engine(..., lanes=B)), curve l in lane l: the engine calls of ONE
     run(), each of which acts on every lane.  x0 and a24 are written, and the stage-1 Z and the stage-2 accumulator read back, for all lanes
-    at once where the engine has set_ints / get_ints (lane by lane otherwise) and gcd'd lane by lane.  stage2 as for run().  A curve whose inversion fails reports that factor as run() does; its lane carries a valid curve whose
+    at once where the engine has set_ints / get_ints (lane by lane otherwise) and gcd'd lane by lane.  stage2 and inverse as for run().  A curve whose inversion fails reports that factor as run() does; its lane carries a valid curve whose
     outcome is dropped.  -> one result per curve in the shape of run(); squarings, products and prepares are those of the batch, which
     are those of one curve."""
     sigmas = list(sigmas)
     if len(sigmas) != getattr(eng, "lanes", 1) or not sigmas:
         raise ValueError("run_lanes needs one sigma per lane: %d given, the engine has %d lanes" % (len(sigmas), getattr(eng, "lanes", 1)))
-    return _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, True, batch, stage2)
+    return _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, True, batch, stage2, inverse)
 
 
 def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0, lanes=1, onelaunch=False, batch=False,
-        curve="montgomery", check_every=0, stage2="projective"):
+        curve="montgomery", check_every=0, stage2="projective", inverse="host"):
     """`curves` curves of run() on a fresh prmers_amd.Engine sized for the chosen D, until one finds a factor.  sigma: the first curve's
     (None: drawn like the others, from random.Random(seed)).  -> the result of the last curve run, with "sigmas": every sigma used.
     lanes = B > 1: the curves run B at a time through run_lanes() on one engine with B lanes (whole batches: `curves` rounded up to a
@@ -599,10 +659,16 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
     curve: "montgomery" (the ladder of this module) or "edwards": stage 1 in twisted Edwards coordinates with an on-curve check every
     check_every NAF digits and at its end (prmers_amd/ecm_edwards.py: slower per bit, but a wrong result is seen); the results then carry
     that driver's further keys.
-    stage2: "projective" or "affine" (run()); D and the engine's registers are chosen for it."""
+    stage2: "projective" or "affine" (run()); D and the engine's registers are chosen for it.
+    inverse: "host" or, with stage2="affine", "engine" (run()); the registers are chosen for it too."""
     from .engine import Engine, resolve_plan
     _check_mode(stage2)
+    _check_inverse(inverse, stage2)
     mode = {} if stage2 == "projective" else {"stage2": stage2}
+    size = {}
+    if inverse != "host":
+        mode["inverse"] = inverse
+        size = {"lanes": lanes, "inverse": inverse}
     if curve not in ("montgomery", "edwards"):
         raise ValueError('curve must be "montgomery" or "edwards"')
     if check_every and curve != "edwards":
@@ -629,8 +695,8 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
         plan = (plan + "," if plan else "") + "onelaunch"
     if b2 > b1 and D is None:
         n = int(resolve_plan(p, plan).split("n=")[1].split(":")[0])
-        D = choose_D(n, b1, b2, budget // lanes, stage2)
-    regs = registers_needed(D, stage2) if b2 > b1 else FIXED_REGISTERS
+        D = choose_D(n, b1, b2, budget // lanes, stage2, **size)
+    regs = registers_needed(D, stage2, **size) if b2 > b1 else FIXED_REGISTERS
     rng = random.Random(seed)
     sigmas = []
     res = None
@@ -679,6 +745,8 @@ def main(argv=None):
     ap.add_argument("--check-every", type=int, default=0, help="with --curve edwards: NAF digits between two checks (0: only at the end of stage 1)")
     ap.add_argument("--stage2", choices=STAGE2_MODES, default="projective",
                     help="affine: stage 2 on x-coordinates normalised on the engine, one fused product per pair (small exponents, lane engines)")
+    ap.add_argument("--inverse", choices=INVERSE_MODES, default="host",
+                    help="with --stage2 affine: engine = the inverses of a block across the lanes on the engine, one host inversion a block")
     a = ap.parse_args(argv)
     more = {"batch": True} if a.batch else {}
     if a.curve != "montgomery":
@@ -687,6 +755,8 @@ def main(argv=None):
         more["check_every"] = a.check_every
     if a.stage2 != "projective":
         more["stage2"] = a.stage2
+    if a.inverse != "host":
+        more["inverse"] = a.inverse
     res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed, a.lanes, a.onelaunch, **more)
     print(json.dumps(res))
     return 0 if res["factors"] else 1

@@ -48,9 +48,10 @@ class EcmCheckError(RuntimeError):
         self.lanes, self.position = list(lanes), position
 
 
-def registers_needed(D=None, stage2="projective"):
-    """registers of an engine for this driver: stage 1 alone (D=None) or with ecm.py's stage 2 over the wheel D, in its mode `stage2`"""
-    return FIXED_REGISTERS if D is None else M.registers_needed(D, stage2)
+def registers_needed(D=None, stage2="projective", lanes=1, inverse="host"):
+    """registers of an engine for this driver: stage 1 alone (D=None) or with ecm.py's stage 2 over the wheel D, in its mode `stage2` and
+    with its `inverse` on `lanes` lanes"""
+    return FIXED_REGISTERS if D is None else M.registers_needed(D, stage2, lanes, inverse)
 
 
 def naf(e):
@@ -144,8 +145,10 @@ POINT = (R_X, R_Y, R_Z, R_T)
 KEEP = (R_KX, R_KY, R_KZ, R_KT)
 
 
-def _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, by_lane, batch, mode="projective"):
+def _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, by_lane, batch, mode="projective", inverse="host"):
     M._check_mode(mode)
+    M._check_engine_inverse(eng, inverse, mode)
+    size = {"lanes": len(sigmas), "inverse": inverse} if inverse != "host" else {}
     if b1 < 2:
         raise ValueError("B1 must be at least 2")
     if min(sigmas) < M.SIGMA_MIN:
@@ -157,11 +160,11 @@ def _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, by_lane,
     stage2 = b2 > b1
     if stage2:
         if D is None:
-            D = max([d for d in D_CHOICES if have is None or M.registers_needed(d, mode) <= have] or [0])
-            D = min(D, M.choose_D(eng.n, b1, b2, stage2=mode)) if D else 0
+            D = max([d for d in D_CHOICES if have is None or M.registers_needed(d, mode, **size) <= have] or [0])
+            D = min(D, M.choose_D(eng.n, b1, b2, stage2=mode, **size)) if D else 0
         if D not in D_CHOICES:
             raise ValueError("stage 2 needs D in %s and an engine with registers_needed(D) registers" % (D_CHOICES,))
-    need = registers_needed(D if stage2 else None, mode)
+    need = registers_needed(D if stage2 else None, mode, **size)
     if have is not None and have < need:
         raise ValueError("the engine has %d registers, ECM on Edwards curves with D = %s needs %d" % (have, D if stage2 else None, need))
     ops = M._Ops(eng)
@@ -250,23 +253,23 @@ def _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, by_lane,
     if stage2:
         ops.addsub(M.R_XQ, M.R_ZQ, R_Z, R_Y)     # (R_XQ and R_ZQ are two of the keep registers, which are done; stage 2 leaves the point alone)
         put(M.R_A24, [c[4] for c in setup]); ops.prep(M.R_A24, M.R_A24)
-        more2 = M._stage2(eng, ops, M._Curve(ops), p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, put, mode)
+        more2 = M._stage2(eng, ops, M._Curve(ops), p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, put, mode, inverse)
     return results(g1, g2, more2)
 
 
-def run(eng, p, b1, b2=0, sigma=M.SIGMA_MIN, D=None, check_every=0, fault=None, use_gmp=None, batch=False, stage2="projective"):
+def run(eng, p, b1, b2=0, sigma=M.SIGMA_MIN, D=None, check_every=0, fault=None, use_gmp=None, batch=False, stage2="projective", inverse="host"):
     """One twisted Edwards curve of ECM on 2^p - 1 with bounds B1 and B2 (B2 <= B1: stage 1 only) on `eng`, an engine for exponent p with
     registers_needed(D) registers.  check_every: NAF digits between two on-curve checks (0: only the one at the end of stage 1).
     fault(position, eng), for tests, is called after every NAF digit.  batch=True: the stretches between checks run inside eng.batch().
-    Afterwards R_X, R_Y, R_Z, R_T hold the stage-1 point.  stage2: the mode of ecm.py's stage 2, as for ecm.run.
+    Afterwards R_X, R_Y, R_Z, R_T hold the stage-1 point.  stage2, inverse: the mode of ecm.py's stage 2 and who inverts in it, as for ecm.run.
     -> the keys of ecm.run, and curve: "edwards", doublings, additions (those carried out, repeated ones included), checks, rollbacks"""
-    return _run_curves(eng, p, b1, b2, [sigma], D, check_every, fault, use_gmp, False, batch, stage2)[0]
+    return _run_curves(eng, p, b1, b2, [sigma], D, check_every, fault, use_gmp, False, batch, stage2, inverse)[0]
 
 
-def run_lanes(eng, p, b1, b2, sigmas, D=None, check_every=0, fault=None, use_gmp=None, batch=False, stage2="projective"):
+def run_lanes(eng, p, b1, b2, sigmas, D=None, check_every=0, fault=None, use_gmp=None, batch=False, stage2="projective", inverse="host"):
     """len(sigmas) == eng.lanes curves at once, curve l in lane l, through the engine calls of ONE run(); the check compares every lane in
     one launch sequence (Engine.equal_lanes) and a failure in any lane takes all lanes back.  -> one result per curve"""
     sigmas = list(sigmas)
     if len(sigmas) != getattr(eng, "lanes", 1) or not sigmas:
         raise ValueError("run_lanes needs one sigma per lane: %d given, the engine has %d lanes" % (len(sigmas), getattr(eng, "lanes", 1)))
-    return _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, True, batch, stage2)
+    return _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, True, batch, stage2, inverse)

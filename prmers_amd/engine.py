@@ -103,11 +103,13 @@ def load_library():
         "mi355_lanewise_get_words": (C.c_int, [vp, sz, vp, sz]),
         "mi355_lanewise_set_words": (C.c_int, [vp, sz, vp, sz]),
         "mi355_lanewise_chunk_lanes": (sz, [sz, sz]),
+        # include/mi355_lanecross.h
+        "mi355_lanecross_mul_sibling": (C.c_int, [vp, sz, sz, sz, u32]),
     }
     for name, (res, args) in sig.items():
-        if name in LANE_EXPORTS + BATCH_EXPORTS + LANEWISE_EXPORTS and os.environ.get("MI355_ENGINE_LIB") and not hasattr(L, name):
-            continue           # an A/B library from before the lanes, the batches or the lane-wise reads (tools/time_lanes.py): Engine.lanes
-                               # reads 1, batch() and equal_lanes() raise
+        if name in LANE_EXPORTS + BATCH_EXPORTS + LANEWISE_EXPORTS + LANECROSS_EXPORTS and os.environ.get("MI355_ENGINE_LIB") and not hasattr(L, name):
+            continue           # an A/B library from before the lanes, the batches, the lane-wise reads or the product across lanes
+                               # (tools/time_lanes.py): Engine.lanes reads 1, batch(), equal_lanes() and mul_sibling() raise
         f = getattr(L, name)   # AttributeError here = the library does not export what the header declares
         f.restype, f.argtypes = res, args
     _lib = L
@@ -142,6 +144,10 @@ BATCH_EXPORTS = ["mi355_batch_begin", "mi355_batch_end", "mi355_batch_stats"]
 
 # include/mi355_lanewise.h: compare, read or write every lane of a register in one launch sequence
 LANEWISE_EXPORTS = ["mi355_lanewise_equal", "mi355_lanewise_get_words", "mi355_lanewise_set_words", "mi355_lanewise_chunk_lanes"]
+
+
+# include/mi355_lanecross.h: a product whose multiplicand image comes from another lane
+LANECROSS_EXPORTS = ["mi355_lanecross_mul_sibling"]
 
 
 def resolve_plan(p, spec=None):
@@ -350,6 +356,17 @@ class Engine:
         mp, size = (1 << self.p) - 1, self.word_count * 4
         raw = b"".join((int(v) % mp).to_bytes(size, "little") for v in values)
         self.set_words_lanes(dst, np.frombuffer(raw, dtype="<u4").reshape(self.lanes, self.word_count))
+
+    # --- across lanes (include/mi355_lanecross.h) ---
+    def mul_sibling(self, dst, src, alt, level):
+        """dst[l] = dst[l] * src[g] on every lane l, g = ((l >> level) ^ 1) << level the first lane of l's sibling block of 2^level lanes,
+        the image read from lane g of src; where g is no lane, dst[l] * alt[l].  src and alt are multiplicand images (keep the image of 1
+        in alt), left as they are.  An engine with one lane: mul(dst, alt).  prmers_amd/lanecross.py builds the inverse on every lane
+        from it."""
+        f = getattr(self.L, "mi355_lanecross_mul_sibling", None)
+        if f is None:
+            raise EngineError("%s does not export mi355_lanecross_mul_sibling (a library from before the product across lanes)" % LIB_PATH)
+        self._ok(f(self.h, dst, src, alt, u32_arg("level", level)))
 
     def pow(self, dst, src, e):
         """dst = src^e, src is erased (engine.h:160-170)."""
