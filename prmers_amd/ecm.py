@@ -2,6 +2,9 @@
 
     python -m prmers_amd.ecm P B1 [B2] [--sigma S] [--curves N] [--lanes B] [--D 30|210|2310] [--plan SPEC] [--onelaunch] [--batch] [--device N]
                              [--curve montgomery|edwards] [--check-every N] [--stage2 projective|affine] [--inverse host|engine]
+                             [--save FILE] [--checkpoint FILE] [--checkpoint-every STEPS] [--stop-after STEPS]
+    python -m prmers_amd.ecm --resume-file FILE B2 [--lanes B] [--D ..] [--stage2 ..] [--inverse ..] [--onelaunch] [--batch] [...]
+    exit code 0: a factor was found, 1: none, 2: the arguments, 3: stopped at --stop-after with the checkpoint written
 
 Curve:    Suyama's parametrisation from sigma: u = sigma^2 - 5, v = 4 sigma, the point (u^3 : v^3) on B y^2 = x^3 + A x^2 + x with
           a24 = (A + 2) / 4 = (v - u)^3 (3 u + v) / (16 u^3 v).  The start is taken affine, x0 = u^3 / v^3 and Z = 1: one modular inversion
@@ -56,15 +59,28 @@ Edwards:  --curve edwards / ecm(curve="edwards") runs stage 1 in twisted Edwards
           at the end, on all lanes at once (Engine.equal_lanes), with a roll-back to the last point that passed.  It costs more sweeps
           per bit than the ladder: it buys the check, not speed.  Stage 2 is the one below for both (_stage2).  The
           per-lane reads at the end of a stage go through Engine.get_ints where the object has it: one launch sequence for all lanes.
-Not here: PRAC chains, checkpoints, ECM= worktodo lines, the PrimeNet JSON, a C++ twin.
+Restart:  all opt-in; with none of it given the calls below are the calls of before.  checkpoint= / --checkpoint FILE names the file of
+          the stage-1 state (prmers_amd/ecm_files.py): every checkpoint_every ladder steps, and once more when stop_after steps are done,
+          the running batch ends, the four ladder registers are read on all lanes (get_ints: canonical residues, so the file fits any
+          plan, with or without onelaunch and batches), the file is replaced (os.replace) and a new batch begins; at stop_after the run
+          raises EcmStopped (the command line: exit code 3).  Where the file exists the run goes on from it: the header must name this
+          run's p, B1, scalar, curve form, sigmas and group, a24 and x0 are rebuilt from the sigmas, the registers go back with set_ints
+          and the ladder goes on at the recorded bit; the exact arithmetic modulo 2^p - 1 reaches the residues of the run that was never
+          stopped.  Stage 2 gets NO checkpoint: it restarts from the stage-1 line.  save= / --save FILE appends, after stage 1, the
+          GMP-ECM / Prime95 resume line of every curve with gcd(Z_Q, N) = 1, x = X_Q / Z_Q; run_saved() / ecm_saved() /
+          --resume-file FILE B2 run stage 2 alone on such lines (a24 from sigma, the point (x : 1)), ours or another program's.
+Not here: PRAC chains, stage-2 checkpoints, raw images of lane engines, resume lines with PARAM != 0, ECM= worktodo
+          lines, the PrimeNet JSON, a C++ twin.
 """
 import argparse
 import contextlib
 import ctypes
 import json
+import os
 import random
 import sys
 
+from . import ecm_files
 from .pm1 import D_CHOICES, DEFAULT_BUDGET, SLOW_GCD_BITS, big_gcd, load_gmp, primes_upto, residues, stage2_pairs
 
 # ladder points a and b, the stage-1 result Q, 2 Q, D Q, three giant points, temporaries, images, the accumulator
@@ -539,20 +555,8 @@ def _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, p
                 g2[l] = g // big_gcd(g, g1[l], use_gmp)
 
 
-def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=False, mode="projective", inverse="host"):
-    """The curves of `sigmas` through one sequence of engine calls: the ladder bits come from B1 and the stage-2 pairs from (B1, B2, D),
-    so only the data differ.  by_lane=False: one curve on an engine used as it is (run).  by_lane=True: curve l in lane l of an engine
-    with len(sigmas) lanes (run_lanes); every engine call then acts on all of them.  batch: the ladder and the stage-2 loops run inside
-    eng.batch() where the object has one (else as without).  mode: the stage 2, "projective" or "affine"; inverse: who inverts in the affine
-    one, "host" or "engine".  -> one result per curve"""
-    _check_mode(mode)
-    _check_engine_inverse(eng, inverse, mode)
-    size = {"lanes": len(sigmas), "inverse": inverse} if inverse != "host" else {}
-    if b1 < 2:
-        raise ValueError("B1 must be at least 2")
-    if min(sigmas) < SIGMA_MIN:
-        raise ValueError("sigma must be at least %d" % SIGMA_MIN)
-    mp = (1 << p) - 1
+def _wheel(eng, b1, b2, D, mode, size):
+    """the D of a run on `eng` (given, or the largest the engine's registers and the interval allow), checked against its registers"""
     have = getattr(eng, "reg_count", None)
     stage2 = b2 > b1
     if stage2:
@@ -564,17 +568,147 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=Fa
     need = registers_needed(D, mode, **size) if stage2 else FIXED_REGISTERS
     if have is not None and have < need:
         raise ValueError("the engine has %d registers, ECM with D = %s needs %d" % (have, D if stage2 else None, need))
+    return D
+
+
+class EcmStopped(Exception):
+    """stage 1 stopped at stop_after and its checkpoint is written; .path: the checkpoint, .step: the steps of stage 1 that are done"""
+
+    def __init__(self, path, step):
+        Exception.__init__(self, "ECM stage 1 stopped after step %d; checkpoint %s" % (step, path))
+        self.path, self.step = path, step
+
+
+class _Restart:
+    """the checkpoints of a stage 1, for both drivers (this one and ecm_edwards).  A step is one scalar digit below the leading one: a
+    ladder step here, a NAF digit there.  With no path it says "go to the end" once and is never heard of again: nothing it does touches
+    the engine unless a checkpoint is due."""
+
+    def __init__(self, path, every, stop_after, form, p, b1, b2, D, sigmas, failed, scalar, group, get, regs):
+        if every < 0 or stop_after < 0:
+            raise ValueError("checkpoint_every and stop_after are numbers of steps, 0 for none")
+        if (every or stop_after) and not path:
+            raise ValueError("checkpoint_every and stop_after need checkpoint=, the file the state goes to")
+        self.path, self.every, self.stop_after, self.get, self.regs = path, every, stop_after, get, regs
+        self.start, self.resumed = 0, False
+        if path:
+            bits, digest = ecm_files.scalar_digest(scalar)
+            self.header = {"p": p, "b1": b1, "b2": b2, "D": D, "curve": form, "sigmas": [int(s) for s in sigmas],
+                           "substitutes": [l for l, bad in enumerate(failed) if bad], "scalar_bits": bits, "scalar_sha256": digest,
+                           "group": group}
+
+    def load(self, steps):
+        """the registers' values of an existing checkpoint (then .start is its step, of the run's `steps`), None without one;
+        CheckpointError when the file is another run's.  The engine is not touched."""
+        if not self.path or not os.path.exists(self.path):
+            return None
+        header, values = ecm_files.read_checkpoint(self.path)
+        for k, what in (("p", "exponent"), ("b1", "B1"), ("curve", "curve form"), ("sigmas", "sigmas (or their number: one a lane)"),
+                        ("substitutes", "substitute lanes"), ("scalar_bits", "stage-1 scalar (B1, and B2 and D below 11)"),
+                        ("scalar_sha256", "stage-1 scalar (B1, and B2 and D below 11)"), ("group", "group of curves")):
+            if header[k] != self.header[k]:
+                raise ecm_files.CheckpointError("%s is the checkpoint of another run: its %s is not this run's" % (self.path, what))
+        if header["registers"] != len(self.regs) or not 0 <= header["next"] - 1 <= steps:
+            raise ecm_files.CheckpointError("%s: %d registers at digit %d do not fit this run" % (self.path, header["registers"], header["next"]))
+        self.start, self.resumed = header["next"] - 1, True
+        return values
+
+    def mark(self, step, steps):
+        """the step up to which the run goes on from `step` before it looks here again"""
+        m = steps
+        if self.every:
+            m = min(m, (step // self.every + 1) * self.every)
+        if self.stop_after > step:
+            m = min(m, self.stop_after)
+        return m
+
+    def reached(self, step, steps):
+        """after the batch that ended at `step` is closed: write what is due; at stop_after raise EcmStopped"""
+        if not self.path or step <= self.start:
+            return
+        stop = step == self.stop_after
+        if stop or (self.every and step % self.every == 0 and step < steps):
+            ecm_files.write_checkpoint(self.path, dict(self.header, next=step + 1), [self.get(r) for r in self.regs])
+        if stop:
+            raise EcmStopped(self.path, step)
+
+    def finish(self):
+        """a normal end: the file has served"""
+        if self.path and os.path.exists(self.path):
+            os.remove(self.path)
+
+    def more(self):
+        return {"resumed_at": self.start} if self.resumed else {}
+
+
+def _save_stage1(eng, ops, get, p, b1, sigmas, failed, g1, zs, path, inverse, use_gmp):
+    """The resume lines of a finished stage 1 whose point is in (R_XQ, R_ZQ), zs = the lanes' Z_Q: x = X_Q / Z_Q for every curve that
+    has one -- its start was set up, stage 1 found nothing and Z_Q is invertible -- appended to `path`.  The inverses come from the host
+    (mod_inverses) or, for inverse="engine", from lanecross.invert in the temporaries of the ladder, which are free now; where some lane's
+    Z_Q has no inverse that one cannot succeed, and the host does it.  R_XQ, R_ZQ and the constants stay.  -> {lane: x}"""
+    mp = (1 << p) - 1
+    want = [l for l in range(len(sigmas)) if not failed[l] and g1[l] == 1 and zs[l] % mp]
+    xs = {}
+    if not want:
+        return xs
+    done = False
+    if inverse == "engine":
+        from . import lanecross
+        work = [R_X2, R_Z2, R_XD, R_ZD, R_XG0, R_ZG0, R_XG1, R_ZG1, R_XG2, R_ZG2, R_S, R_D, R_W, R_T, R_IS, R_ID, R_IT, R_A]
+        work = work[:lanecross.registers_needed(len(sigmas))]
+        lanecross.prepare_one(eng, work[1])
+        done = lanecross.invert(eng, R_ZQ, R_U, work, False, use_gmp, ops)[0]
+        if done:
+            ops.prep(R_U, R_U); eng.copy(R_V, R_XQ); ops.mul(R_V, R_U)
+            values = get(R_V)
+            xs = {l: values[l] for l in want}
+    if not done:
+        xq = get(R_XQ)
+        xs = {l: xq[l] * u % mp for l, u in zip(want, mod_inverses([zs[l] for l in want], mp, use_gmp)) if u}
+    ecm_files.append_resume_lines(path, [ecm_files.resume_line(p, sigmas[l], b1, xs[l]) for l in sorted(xs)])
+    return xs
+
+
+LADDER = (R_XA, R_ZA, R_XB, R_ZB)            # the state of an interrupted stage 1
+
+
+def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=False, mode="projective", inverse="host",
+                checkpoint=None, checkpoint_every=0, stop_after=0, save=None, group=0):
+    """The curves of `sigmas` through one sequence of engine calls: the ladder bits come from B1 and the stage-2 pairs from (B1, B2, D),
+    so only the data differ.  by_lane=False: one curve on an engine used as it is (run).  by_lane=True: curve l in lane l of an engine
+    with len(sigmas) lanes (run_lanes); every engine call then acts on all of them.  batch: the ladder and the stage-2 loops run inside
+    eng.batch() where the object has one (else as without).  mode: the stage 2, "projective" or "affine"; inverse: who inverts in the affine
+    one, "host" or "engine".  checkpoint, checkpoint_every, stop_after, save, group: run().  -> one result per curve"""
+    _check_mode(mode)
+    _check_engine_inverse(eng, inverse, mode)
+    size = {"lanes": len(sigmas), "inverse": inverse} if inverse != "host" else {}
+    if b1 < 2:
+        raise ValueError("B1 must be at least 2")
+    if min(sigmas) < SIGMA_MIN:
+        raise ValueError("sigma must be at least %d" % SIGMA_MIN)
+    mp = (1 << p) - 1
+    stage2 = b2 > b1
+    D = _wheel(eng, b1, b2, D, mode, size)
+    e = stage1_exponent(b1)
+    if stage2:   # the primes in (B1, B2] that divide D have no residue class in stage 2
+        for q in (2, 3, 5, 7, 11):
+            if D % q == 0 and b1 < q <= b2:
+                if save:
+                    raise ValueError("save: with B1 = %d < 11 and a stage 2 over D = %d the stage-1 scalar also takes the prime %d, so the "
+                                     "line would claim a B1 it does not describe; save a stage-1-only run" % (b1, D, q))
+                e *= q
     ops = _Ops(eng, use_fused)
     cv = _Curve(ops)
     lanes = range(len(sigmas))
     io = _IO(eng, len(sigmas), by_lane, batch)
     batched, put, get = io.batched, io.put, io.get
 
-    def results(g1, g2, more2=None):
+    def results(g1, g2, more2=None, xs=None):
         more = {**(more2 or {}), **io.launches()}
         return [{"p": p, "b1": b1, "b2": b2 if stage2 else 0, "D": D if stage2 else None, "sigma": sigmas[l],
                  "factors": [f for f in (g1[l], g2[l]) if 1 < f < mp], "g1": g1[l], "g2": g2[l],
-                 "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused, **more} for l in lanes]
+                 "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused, **more,
+                 **({"x": xs[l]} if xs and l in xs else {})} for l in lanes]
 
     setup = [suyama(s, mp, use_gmp) for s in sigmas]
     failed = [g != 1 for _, _, g in setup]   # the inversion failed: its argument shares g with Mp, which is the curve's result
@@ -588,35 +722,51 @@ def _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, by_lane, batch=Fa
             s += 1
         setup = [suyama(s, mp, use_gmp) if bad else c for c, bad in zip(setup, failed)]
 
-    # ---- stage 1 ----
-    e = stage1_exponent(b1)
-    if stage2:   # the primes in (B1, B2] that divide D have no residue class in stage 2
-        for q in (2, 3, 5, 7, 11):
-            if D % q == 0 and b1 < q <= b2:
-                e *= q
+    # ---- stage 1: the ladder, in one stretch or, with checkpoints, in stretches that end where one is due ----
+    restart = _Restart(checkpoint, checkpoint_every, stop_after, "montgomery", p, b1, b2 if stage2 else 0, D if stage2 else None,
+                       sigmas, failed, e, group, get, LADDER)
+    steps = e.bit_length() - 1                   # step k works on bit steps - 1 - k
+    state = restart.load(steps)                  # a checkpoint of another run is refused here, before anything is written
     put(R_A24, [c[1] for c in setup]); ops.prep(R_A24, R_A24)
     put(R_X0, [c[0] for c in setup]); ops.prep(R_X0, R_X0)
     a, b = (R_XA, R_ZA), (R_XB, R_ZB)
-    put(R_XA, [c[0] for c in setup]); eng.set(R_ZA, 1)
-    with batched():
-        cv.dbl(b, a)                             # (a, b) = (P, 2 P)
-        for i in range(e.bit_length() - 2, -1, -1):
-            if (e >> i) & 1:
-                cv.ladder_step(b, a)
-            else:
-                cv.ladder_step(a, b)
-        eng.copy(R_XQ, a[0]); eng.copy(R_ZQ, a[1])
-    for l, z in enumerate(get(R_ZQ)):
+    if state is None:
+        put(R_XA, [c[0] for c in setup]); eng.set(R_ZA, 1)
+    else:
+        for reg, values in zip(LADDER, state):
+            put(reg, values)
+    step = restart.start
+    while True:
+        upto = restart.mark(step, steps)
+        with batched():
+            if state is None and step == 0:
+                cv.dbl(b, a)                     # (a, b) = (P, 2 P)
+            for i in range(steps - 1 - step, steps - 1 - upto, -1):
+                if (e >> i) & 1:
+                    cv.ladder_step(b, a)
+                else:
+                    cv.ladder_step(a, b)
+            if upto == steps:
+                eng.copy(R_XQ, a[0]); eng.copy(R_ZQ, a[1])
+        step = upto
+        restart.reached(step, steps)
+        if step == steps:
+            break
+    zs = get(R_ZQ)
+    for l, z in enumerate(zs):
         if not failed[l]:
             g1[l] = mp if z == 0 else big_gcd(z, mp, use_gmp)
+    xs = _save_stage1(eng, ops, get, p, b1, sigmas, failed, g1, zs, save, inverse, use_gmp) if save else None
 
     more2 = None
     if stage2:
         more2 = _stage2(eng, ops, cv, p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, put, mode, inverse)
-    return results(g1, g2, more2)
+    restart.finish()
+    return results(g1, g2, {**(more2 or {}), **restart.more()}, xs)
 
 
-def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None, batch=False, stage2="projective", inverse="host"):
+def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None, batch=False, stage2="projective", inverse="host",
+        checkpoint=None, checkpoint_every=0, stop_after=0, save=None, group=0):
     """One curve of ECM on 2^p - 1 with bounds B1 and B2 (B2 <= B1: stage 1 only) on `eng`, an engine for exponent p with at least
     FIXED_REGISTERS registers (stage 1) or registers_needed(D) (stage 2).  use_fused=False forces set_multiplicand + square_mul in
     place of square_mul_prepare.  Afterwards registers R_XQ, R_ZQ hold the stage-1 point.  batch=True: the ladder and the stage-2 loops
@@ -630,24 +780,108 @@ def run(eng, p, b1, b2=0, sigma=SIGMA_MIN, D=None, use_fused=True, use_gmp=None,
     the engine, one host inversion a block whatever the lane count, and the Z product kept in a register (prmers_amd/lanecross.py); the
     engine then needs registers_needed(D, "affine", lanes, "engine") registers and the result has "inverse": "engine" and
     "inverse_fallbacks", the blocks that went the host's way because some lane's product had no inverse.  Same g1, g2 and accumulator.
+    checkpoint (a path), checkpoint_every, stop_after (ladder steps; the module's docstring, "Restart"): every checkpoint_every steps, and
+    when stop_after steps are done, the batch ends, the four ladder registers are read and the file is replaced; at stop_after the run
+    then raises EcmStopped.  Where the file exists when the run begins, stage 1 goes on from it -- after the header has been compared with
+    this run's p, B1, scalar, curve form, sigmas and group (CheckpointError, the engine untouched) -- and the result has "resumed_at",
+    the step.  A stop_after that the checkpoint is past already is not met again.  A normal end removes the file.  group: the index of
+    this group of curves in ecm()'s sequence, kept in the header.
+    save (a path): after stage 1 the resume line of the curve (prmers_amd/ecm_files.py) is appended to that file and the result has "x",
+    the affine x of the stage-1 point -- unless stage 1 found a factor or the start's inversion failed: then there is no line.  The inverse
+    of Z_Q comes from the host, or for inverse="engine" from lanecross.invert.  Refused where the stage-1 scalar holds more than E(B1).
     -> {p, b1, b2, D, sigma, factors, g1, g2, squarings, products, prepares, fused}"""
-    return _run_curves(eng, p, b1, b2, [sigma], D, use_fused, use_gmp, False, batch, stage2, inverse)[0]
+    return _run_curves(eng, p, b1, b2, [sigma], D, use_fused, use_gmp, False, batch, stage2, inverse,
+                       checkpoint, checkpoint_every, stop_after, save, group)[0]
 
 
-def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None, batch=False, stage2="projective", inverse="host"):
+def run_lanes(eng, p, b1, b2, sigmas, D=None, use_fused=True, use_gmp=None, batch=False, stage2="projective", inverse="host",
+              checkpoint=None, checkpoint_every=0, stop_after=0, save=None, group=0):
     """len(sigmas) == eng.lanes curves at once on an engine with lanes (Engine(..., lanes=B)), curve l in lane l: the engine calls of ONE
     run(), each of which acts on every lane.  x0 and a24 are written, and the stage-1 Z and the stage-2 accumulator read back, for all lanes
     at once where the engine has set_ints / get_ints (lane by lane otherwise) and gcd'd lane by lane.  stage2 and inverse as for run().  A curve whose inversion fails reports that factor as run() does; its lane carries a valid curve whose
     outcome is dropped.  -> one result per curve in the shape of run(); squarings, products and prepares are those of the batch, which
-    are those of one curve."""
+    are those of one curve.  checkpoint, checkpoint_every, stop_after, save, group as for run(): one checkpoint holds every lane (the
+    registers are read with get_ints and written back with set_ints), and every lane that has a line gets it, in lane order."""
     sigmas = list(sigmas)
     if len(sigmas) != getattr(eng, "lanes", 1) or not sigmas:
         raise ValueError("run_lanes needs one sigma per lane: %d given, the engine has %d lanes" % (len(sigmas), getattr(eng, "lanes", 1)))
-    return _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, True, batch, stage2, inverse)
+    return _run_curves(eng, p, b1, b2, sigmas, D, use_fused, use_gmp, True, batch, stage2, inverse,
+                       checkpoint, checkpoint_every, stop_after, save, group)
+
+
+def run_saved(eng, lines, b2, D=None, stage2="projective", inverse="host", batch=False, use_gmp=None):
+    """Stage 2 alone, on stage-1 results from resume lines: `lines` are parsed lines (ecm_files.parse_resume_line) of one p and one b1, one
+    per lane of `eng` (one line on an engine without lanes).  a24 comes from each sigma, R_XQ <- x, R_ZQ <- 1, then the stage 2 of run().
+    The lines' stage 1 ran to E(B1) exactly, so a prime of (B1, B2] that divides D -- there is one only for B1 < 11 -- would be covered
+    by nothing: that is refused.  -> one result per line in the shape of run_lanes(), with g1 = 1"""
+    lines = list(lines)
+    count = getattr(eng, "lanes", 1)
+    if len(lines) != count or not lines:
+        raise ValueError("run_saved needs one line per lane: %d given, the engine has %d lanes" % (len(lines), count))
+    p, b1 = lines[0]["p"], lines[0]["b1"]
+    if any((l["p"], l["b1"]) != (p, b1) for l in lines) or p != eng.p:
+        raise ValueError("run_saved needs lines of one p, the engine's, and one B1")
+    if b2 <= b1:
+        raise ValueError("run_saved runs stage 2: B2 must be above the lines' B1 = %d" % b1)
+    _check_mode(stage2)
+    _check_engine_inverse(eng, inverse, stage2)
+    sigmas = [l["sigma"] for l in lines]
+    if min(sigmas) < SIGMA_MIN:
+        raise ValueError("sigma must be at least %d" % SIGMA_MIN)
+    size = {"lanes": count, "inverse": inverse} if inverse != "host" else {}
+    D = _wheel(eng, b1, b2, D, stage2, size)
+    for q in (2, 3, 5, 7, 11):
+        if D % q == 0 and b1 < q <= b2:
+            raise ValueError("the lines' stage 1 ran to B1 = %d and stage 2 over D = %d has no residue class for the prime %d" % (b1, D, q))
+    mp = (1 << p) - 1
+    setup = [suyama(s, mp, use_gmp) for s in sigmas]
+    if any(g != 1 for _, _, g in setup):
+        raise ValueError("a line names a sigma whose curve cannot be set up modulo 2^%d - 1: no stage 1 can have ended on it" % p)
+    ops = _Ops(eng)
+    io = _IO(eng, count, count > 1, batch)
+    failed, g1, g2 = [False] * count, [1] * count, [1] * count
+    io.put(R_A24, [c[1] for c in setup]); ops.prep(R_A24, R_A24)
+    io.put(R_XQ, [l["x"] for l in lines]); eng.set(R_ZQ, 1)
+    more = _stage2(eng, ops, _Curve(ops), p, b1, b2, D, failed, g1, g2, io.batched, io.get, use_gmp, io.put, stage2, inverse) or {}
+    return [{"p": p, "b1": b1, "b2": b2, "D": D, "sigma": sigmas[l], "factors": [f for f in (g2[l],) if 1 < f < mp], "g1": 1, "g2": g2[l],
+             "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused, **more, **io.launches()}
+            for l in range(count)]
+
+
+def ecm_saved(path, b2, lanes=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, onelaunch=False, batch=False, stage2="projective",
+              inverse="host"):
+    """run_saved() for a file of resume lines: the lines are grouped by (p, B1) and run `lanes` at a time on a fresh prmers_amd.Engine
+    with that many lanes; a short last group is padded by repeating its first line and the padding's results are dropped.
+    -> {"factors": all of them, "curves": lines run, "results": one per line, each group's in the file's order}"""
+    from .engine import Engine, resolve_plan
+    _check_mode(stage2)
+    _check_inverse(inverse, stage2)
+    if lanes < 1:
+        raise ValueError("lanes must be at least 1")
+    if batch and not (onelaunch or "onelaunch" in (plan or "")):
+        raise ValueError("batch needs an engine with one-launch products: say onelaunch=True (--onelaunch) as well")
+    if onelaunch:
+        plan = (plan + "," if plan else "") + "onelaunch"
+    size = {"lanes": lanes, "inverse": inverse} if inverse != "host" else {}
+    groups = {}
+    for line in ecm_files.read_resume_file(path):
+        groups.setdefault((line["p"], line["b1"]), []).append(line)
+    out = []
+    for (p, b1), lines in groups.items():
+        d = D
+        if d is None:
+            n = int(resolve_plan(p, plan).split("n=")[1].split(":")[0])
+            d = choose_D(n, b1, b2, budget // lanes, stage2, **size)
+        with Engine(p, registers_needed(d, stage2, **size), device=device, plan=plan, lanes=lanes) as eng:
+            for at in range(0, len(lines), lanes):
+                part = lines[at:at + lanes]
+                res = run_saved(eng, part + [part[0]] * (lanes - len(part)), b2, d, stage2, inverse, batch)
+                out.extend(res[:len(part)])
+    return {"factors": sorted({f for r in out for f in r["factors"]}), "curves": len(out), "results": out}
 
 
 def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=DEFAULT_BUDGET, seed=0, lanes=1, onelaunch=False, batch=False,
-        curve="montgomery", check_every=0, stage2="projective", inverse="host"):
+        curve="montgomery", check_every=0, stage2="projective", inverse="host", checkpoint=None, checkpoint_every=0, stop_after=0, save=None):
     """`curves` curves of run() on a fresh prmers_amd.Engine sized for the chosen D, until one finds a factor.  sigma: the first curve's
     (None: drawn like the others, from random.Random(seed)).  -> the result of the last curve run, with "sigmas": every sigma used.
     lanes = B > 1: the curves run B at a time through run_lanes() on one engine with B lanes (whole batches: `curves` rounded up to a
@@ -660,7 +894,11 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
     check_every NAF digits and at its end (prmers_amd/ecm_edwards.py: slower per bit, but a wrong result is seen); the results then carry
     that driver's further keys.
     stage2: "projective" or "affine" (run()); D and the engine's registers are chosen for it.
-    inverse: "host" or, with stage2="affine", "engine" (run()); the registers are chosen for it too."""
+    inverse: "host" or, with stage2="affine", "engine" (run()); the registers are chosen for it too.
+    checkpoint, checkpoint_every, stop_after: those of run(), for whichever group of curves is running (a curve, or `lanes` of them); the
+    header keeps the group's index.  Where the file exists, the groups before its index are skipped -- they found nothing, or the call
+    would have ended -- their sigmas are drawn all the same, and the group's own are compared with the header's: another seed, sigma or
+    lane count is refused (CheckpointError).  EcmStopped passes through.  save: run()'s, every group appends its lines."""
     from .engine import Engine, resolve_plan
     _check_mode(stage2)
     _check_inverse(inverse, stage2)
@@ -676,17 +914,17 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
     if curve == "edwards":
         from . import ecm_edwards
 
-        def run_one(eng, s):
-            return ecm_edwards.run(eng, p, b1, b2, s, D, check_every=check_every, batch=batch, **mode)
+        def run_one(eng, s, **kw):
+            return ecm_edwards.run(eng, p, b1, b2, s, D, check_every=check_every, batch=batch, **mode, **kw)
 
-        def run_many(eng, ss):
-            return ecm_edwards.run_lanes(eng, p, b1, b2, ss, D, check_every=check_every, batch=batch, **mode)
+        def run_many(eng, ss, **kw):
+            return ecm_edwards.run_lanes(eng, p, b1, b2, ss, D, check_every=check_every, batch=batch, **mode, **kw)
     else:
-        def run_one(eng, s):
-            return run(eng, p, b1, b2, s, D, batch=batch, **mode)
+        def run_one(eng, s, **kw):
+            return run(eng, p, b1, b2, s, D, batch=batch, **mode, **kw)
 
-        def run_many(eng, ss):
-            return run_lanes(eng, p, b1, b2, ss, D, batch=batch, **mode)
+        def run_many(eng, ss, **kw):
+            return run_lanes(eng, p, b1, b2, ss, D, batch=batch, **mode, **kw)
     if lanes < 1:
         raise ValueError("lanes must be at least 1")
     if batch and not (onelaunch or "onelaunch" in (plan or "")):
@@ -705,16 +943,35 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
         s = sigma if (not sigmas and sigma is not None) else rng.randrange(SIGMA_MIN, 1 << 32)
         sigmas.append(s)
         return s
+    if (checkpoint_every or stop_after) and not checkpoint:
+        raise ValueError("checkpoint_every and stop_after need checkpoint=, the file the state goes to")
+    keep = {"save": save} if save else {}
+    first = 0                                    # the first group to run: the checkpoint's when there is one
+    if checkpoint or checkpoint_every or stop_after:
+        keep.update(checkpoint=checkpoint, checkpoint_every=checkpoint_every, stop_after=stop_after)
+        if checkpoint and os.path.exists(checkpoint):
+            first = ecm_files.read_checkpoint(checkpoint)[0]["group"]
+            if not 0 <= first < -(-max(1, curves) // lanes):
+                raise ecm_files.CheckpointError("%s is the checkpoint of another run: its group %d is none of this call's" % (checkpoint, first))
+
+    def group(c):
+        return dict(keep, group=c) if "checkpoint" in keep else keep
     if lanes == 1:
         with Engine(p, regs, device=device, plan=plan) as eng:
             for c in range(max(1, curves)):
-                res = run_one(eng, draw())
+                s = draw()
+                if c < first:
+                    continue
+                res = run_one(eng, s, **group(c))
                 if res["factors"]:
                     break
     else:
         with Engine(p, regs, device=device, plan=plan, lanes=lanes) as eng:
             for c in range(0, max(1, curves), lanes):
-                out = run_many(eng, [draw() for _ in range(lanes)])
+                ss = [draw() for _ in range(lanes)]
+                if c // lanes < first:
+                    continue
+                out = run_many(eng, ss, **group(c // lanes))
                 found = [r for r in out if r["factors"]]
                 res = dict(found[0] if found else out[-1])
                 res["factors"] = sorted({f for r in out for f in r["factors"]})
@@ -725,10 +982,13 @@ def ecm(p, b1, b2=0, sigma=None, curves=1, D=None, plan=None, device=0, budget=D
     return res
 
 
+EXIT_STOPPED = 3              # 0: a factor, 1: none, 2: the arguments (argparse), 3: stopped at --stop-after with the checkpoint written
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m prmers_amd.ecm", description="ECM factoring of 2^P - 1 (Montgomery curves, stages 1 and 2) on an MI355X")
-    ap.add_argument("p", type=int)
-    ap.add_argument("b1", type=int)
+    ap.add_argument("p", type=int, nargs="?", default=None)
+    ap.add_argument("b1", type=int, nargs="?", default=None)
     ap.add_argument("b2", type=int, nargs="?", default=0)
     ap.add_argument("--sigma", type=int, default=None, help="Suyama parameter of the first curve (default: drawn from the seeded generator)")
     ap.add_argument("--curves", type=int, default=1)
@@ -747,7 +1007,29 @@ def main(argv=None):
                     help="affine: stage 2 on x-coordinates normalised on the engine, one fused product per pair (small exponents, lane engines)")
     ap.add_argument("--inverse", choices=INVERSE_MODES, default="host",
                     help="with --stage2 affine: engine = the inverses of a block across the lanes on the engine, one host inversion a block")
+    ap.add_argument("--save", metavar="FILE", default=None, help="append the resume line of every curve whose stage 1 ended without a factor (GMP-ECM / Prime95 format)")
+    ap.add_argument("--checkpoint", metavar="FILE", default=None, help="the stage-1 checkpoint: written there, and stage 1 goes on from it where it exists")
+    ap.add_argument("--checkpoint-every", type=int, default=0, metavar="STEPS", help="stage-1 steps between two checkpoints (default: none are written)")
+    ap.add_argument("--stop-after", type=int, default=0, metavar="STEPS",
+                    help="write the checkpoint when this many stage-1 steps are done and exit with code %d; the same command again goes on from it" % EXIT_STOPPED)
+    ap.add_argument("--resume-file", nargs=2, metavar=("FILE", "B2"), default=None,
+                    help="in place of P B1: stage 2 to B2 on the stage-1 results of the file's resume lines, --lanes at a time")
     a = ap.parse_args(argv)
+    if a.resume_file:
+        if a.p is not None:
+            ap.error("--resume-file FILE B2 stands in place of P B1 [B2]")
+        for name in ("sigma", "save", "checkpoint", "checkpoint_every", "stop_after", "check_every"):
+            if getattr(a, name):
+                ap.error("--resume-file runs stage 2 only: --%s has nothing to act on" % name.replace("_", "-"))
+        try:
+            b2 = int(a.resume_file[1])
+        except ValueError:
+            ap.error("--resume-file FILE B2: B2 must be an integer")
+        res = ecm_saved(a.resume_file[0], b2, a.lanes, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.onelaunch, a.batch, a.stage2, a.inverse)
+        print(json.dumps(res))
+        return 0 if res["factors"] else 1
+    if a.p is None or a.b1 is None:
+        ap.error("P and B1 are needed (or --resume-file FILE B2)")
     more = {"batch": True} if a.batch else {}
     if a.curve != "montgomery":
         more["curve"] = a.curve
@@ -757,7 +1039,14 @@ def main(argv=None):
         more["stage2"] = a.stage2
     if a.inverse != "host":
         more["inverse"] = a.inverse
-    res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed, a.lanes, a.onelaunch, **more)
+    for name in ("save", "checkpoint", "checkpoint_every", "stop_after"):
+        if getattr(a, name):
+            more[name] = getattr(a, name)
+    try:
+        res = ecm(a.p, a.b1, a.b2, a.sigma, a.curves, a.D, a.plan, a.device, int(a.budget_gib * 2**30), a.seed, a.lanes, a.onelaunch, **more)
+    except EcmStopped as stop:
+        print(json.dumps({"stopped_at": stop.step, "checkpoint": stop.path}))
+        return EXIT_STOPPED
     print(json.dumps(res))
     return 0 if res["factors"] else 1
 

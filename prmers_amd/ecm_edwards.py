@@ -27,7 +27,12 @@ Check:    L = a X^2 + Y^2 and R = Z^2 + d T^2 in scratch registers, compared on 
           the comparison runs between two batches.  The engine operations and the lane and batch plumbing are ecm.py's (_Ops, _IO).
 Stage 2:  Q maps to the Montgomery point (Z + Y : Z - Y); that goes into ecm.R_XQ, ecm.R_ZQ, a24 as an image into ecm.R_A24, and
           ecm._stage2 runs as it does for ecm.run.  (No invariant there: the check covers stage 1.)
-Not here: the reference's torsion-16 and iv163 families, windowed NAF, a twisted Edwards stage 2, checkpoints.
+Restart:  checkpoint=, checkpoint_every=, stop_after= as in ecm.py (its docstring), counted in NAF digits; the state is the extended
+          point's four registers as canonical residues and the index of the next digit.  A checkpoint is written only from a point that has
+          just passed the check, so no file ever holds a point off the curve: checkpoint_every is rounded up to a multiple of check_every,
+          a check stands behind digit stop_after, and check_every = 0 with a checkpoint is refused.  save= writes the line of the
+          Montgomery curve of the same sigma, x = (Z + Y) / (Z - Y).  Stage 2 has no checkpoint; it restarts from that line.
+Not here: the reference's torsion-16 and iv163 families, windowed NAF, a twisted Edwards stage 2, stage-2 checkpoints.
 """
 from . import ecm as M
 from .pm1 import D_CHOICES, big_gcd
@@ -145,7 +150,8 @@ POINT = (R_X, R_Y, R_Z, R_T)
 KEEP = (R_KX, R_KY, R_KZ, R_KT)
 
 
-def _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, by_lane, batch, mode="projective", inverse="host"):
+def _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, by_lane, batch, mode="projective", inverse="host",
+                checkpoint=None, checkpoint_every=0, stop_after=0, save=None, group=0):
     M._check_mode(mode)
     M._check_engine_inverse(eng, inverse, mode)
     size = {"lanes": len(sigmas), "inverse": inverse} if inverse != "host" else {}
@@ -155,6 +161,11 @@ def _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, by_lane,
         raise ValueError("sigma must be at least %d" % M.SIGMA_MIN)
     if check_every < 0:
         raise ValueError("check_every must be 0 (the end of stage 1 only) or a number of NAF digits")
+    if checkpoint and not check_every:
+        raise ValueError("a checkpoint is written only from a point that has just passed the on-curve check, so that no file ever holds a "
+                         "point that is off the curve: with check_every = 0 the only check stands at the end of stage 1; give check_every")
+    if checkpoint_every and check_every:         # ... and so only at a check: the next multiple of check_every
+        checkpoint_every = -(-checkpoint_every // check_every) * check_every
     mp = (1 << p) - 1
     have = getattr(eng, "reg_count", None)
     stage2 = b2 > b1
@@ -174,11 +185,12 @@ def _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, by_lane,
     batched, put, get = io.batched, io.put, io.get
     count = {"doublings": 0, "additions": 0, "checks": 0, "rollbacks": 0}
 
-    def results(g1, g2, more2=None):
+    def results(g1, g2, more2=None, xs=None):
         more = {**(more2 or {}), **io.launches()}
         return [{"p": p, "b1": b1, "b2": b2 if stage2 else 0, "D": D if stage2 else None, "sigma": sigmas[l],
                  "factors": [f for f in (g1[l], g2[l]) if 1 < f < mp], "g1": g1[l], "g2": g2[l],
-                 "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused, "curve": "edwards", **count, **more} for l in lanes]
+                 "squarings": ops.squarings, "products": ops.products, "prepares": ops.prepares, "fused": ops.fused, "curve": "edwards", **count, **more,
+                 **({"x": xs[l]} if xs and l in xs else {})} for l in lanes]
 
     setup = [curve(s, mp, use_gmp) for s in sigmas]
     failed = [c[5] != 1 for c in setup]          # the inversion failed: its argument shares g with Mp, which is the curve's result
@@ -197,15 +209,25 @@ def _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, by_lane,
     if stage2:   # the primes in (B1, B2] that divide D have no residue class in stage 2
         for q in (2, 3, 5, 7, 11):
             if D % q == 0 and b1 < q <= b2:
+                if save:
+                    raise ValueError("save: with B1 = %d < 11 and a stage 2 over D = %d the stage-1 scalar also takes the prime %d, so the "
+                                     "line would claim a B1 it does not describe; save a stage-1-only run" % (b1, D, q))
                 e *= q
     digits = naf(e)
+    restart = M._Restart(checkpoint, checkpoint_every, stop_after, "edwards", p, b1, b2 if stage2 else 0, D if stage2 else None,
+                         sigmas, failed, e, group, get, POINT)
+    state = restart.load(len(digits) - 1)        # a checkpoint of another run is refused here, before anything is written
     for reg, f in ((R_IA, lambda a, d, x, y: a), (R_ID, lambda a, d, x, y: d), (R_IY0, lambda a, d, x, y: y),
                    (R_IXP, lambda a, d, x, y: x), (R_IXM, lambda a, d, x, y: -x),
                    (R_IAXP, lambda a, d, x, y: a * x), (R_IAXM, lambda a, d, x, y: -a * x),
                    (R_IDTP, lambda a, d, x, y: d * x * y), (R_IDTM, lambda a, d, x, y: -d * x * y)):
         put(reg, [f(*c[:4]) % mp for c in setup]); ops.prep(reg, reg)
-    put(R_X, [c[2] for c in setup]); put(R_Y, [c[3] for c in setup]); eng.set(R_Z, 1)
-    put(R_T, [c[2] * c[3] % mp for c in setup])
+    if state is None:
+        put(R_X, [c[2] for c in setup]); put(R_Y, [c[3] for c in setup]); eng.set(R_Z, 1)
+        put(R_T, [c[2] * c[3] % mp for c in setup])
+    else:                                        # the point of the checkpoint: it had passed the check when it was written
+        for reg, values in zip(POINT, state):
+            put(reg, values)
 
     def check():
         """the lanes in which a X^2 + Y^2 != Z^2 + d T^2, from the two sides in R_L and R_R"""
@@ -221,10 +243,14 @@ def _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, by_lane,
     # ---- stage 1: the NAF from the top, in stretches that end in a check ----
     # A stretch is one batch: the four copies the last check asks for (the point to the keep registers after a pass, back from them after
     # a failure), the digits, the two sides of the check.  Between two batches only the comparison runs.
-    pos, last = 1, len(digits)                   # digits[0] = 1 is the start point itself
+    # A check stands behind every check_every-th digit counted from the top, whatever digit the run began at, behind digit stop_after and
+    # at the end.  A step of the checkpoints is a digit below the leading one: pos - 1 of them are done.
+    pos, last = restart.start + 1, len(digits)   # digits[0] = 1 is the start point itself
     passed = True                                # the start point is on the curve (curve() asserts it)
     while pos < last or count["checks"] == 0:
-        end = min(last, pos + check_every) if check_every else last
+        end = min(last, ((pos - 1) // check_every + 1) * check_every + 1) if check_every else last
+        if stop_after > pos - 1:
+            end = min(end, stop_after + 1)
         for attempt in (0, 1):
             with batched():
                 for k, r in zip(KEEP, POINT):
@@ -244,32 +270,46 @@ def _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, by_lane,
                 raise EcmCheckError(bad, end - 1)
             count["rollbacks"] += 1
         pos = end
+        restart.reached(pos - 1, last - 1)
     for l, x in enumerate(get(R_X)):
         if not failed[l]:
             g1[l] = mp if x == 0 else big_gcd(x, mp, use_gmp)
 
     # ---- stage 2: ecm.py's, on the Montgomery point (Z + Y : Z - Y) ----
-    more2 = None
-    if stage2:
+    more2 = xs = None
+    if stage2 or save:
         ops.addsub(M.R_XQ, M.R_ZQ, R_Z, R_Y)     # (R_XQ and R_ZQ are two of the keep registers, which are done; stage 2 leaves the point alone)
+    if save:                                     # the line of the Montgomery curve of the same sigma: x = (Z + Y) / (Z - Y)
+        xs = M._save_stage1(eng, ops, get, p, b1, sigmas, failed, g1, get(M.R_ZQ), save, inverse, use_gmp)
+    if stage2:
         put(M.R_A24, [c[4] for c in setup]); ops.prep(M.R_A24, M.R_A24)
         more2 = M._stage2(eng, ops, M._Curve(ops), p, b1, b2, D, failed, g1, g2, batched, get, use_gmp, put, mode, inverse)
-    return results(g1, g2, more2)
+    restart.finish()
+    return results(g1, g2, {**(more2 or {}), **restart.more()}, xs)
 
 
-def run(eng, p, b1, b2=0, sigma=M.SIGMA_MIN, D=None, check_every=0, fault=None, use_gmp=None, batch=False, stage2="projective", inverse="host"):
+def run(eng, p, b1, b2=0, sigma=M.SIGMA_MIN, D=None, check_every=0, fault=None, use_gmp=None, batch=False, stage2="projective", inverse="host",
+        checkpoint=None, checkpoint_every=0, stop_after=0, save=None, group=0):
     """One twisted Edwards curve of ECM on 2^p - 1 with bounds B1 and B2 (B2 <= B1: stage 1 only) on `eng`, an engine for exponent p with
     registers_needed(D) registers.  check_every: NAF digits between two on-curve checks (0: only the one at the end of stage 1).
     fault(position, eng), for tests, is called after every NAF digit.  batch=True: the stretches between checks run inside eng.batch().
     Afterwards R_X, R_Y, R_Z, R_T hold the stage-1 point.  stage2, inverse: the mode of ecm.py's stage 2 and who inverts in it, as for ecm.run.
+    checkpoint, checkpoint_every, stop_after, group: as for ecm.run, in NAF digits, with the state (R_X, R_Y, R_Z, R_T) and the digit's
+    index.  A checkpoint is written only from a point that has just passed the check: checkpoint_every is rounded up to a multiple of
+    check_every, a check stands behind digit stop_after, and check_every = 0 with a checkpoint is a ValueError.  A resumed run checks
+    behind the same digits as an uninterrupted one; its doublings, additions and checks count from the checkpoint on.
+    save: as for ecm.run; the line is that of the Montgomery curve of the same sigma, x = (Z + Y) / (Z - Y).
     -> the keys of ecm.run, and curve: "edwards", doublings, additions (those carried out, repeated ones included), checks, rollbacks"""
-    return _run_curves(eng, p, b1, b2, [sigma], D, check_every, fault, use_gmp, False, batch, stage2, inverse)[0]
+    return _run_curves(eng, p, b1, b2, [sigma], D, check_every, fault, use_gmp, False, batch, stage2, inverse,
+                       checkpoint, checkpoint_every, stop_after, save, group)[0]
 
 
-def run_lanes(eng, p, b1, b2, sigmas, D=None, check_every=0, fault=None, use_gmp=None, batch=False, stage2="projective", inverse="host"):
+def run_lanes(eng, p, b1, b2, sigmas, D=None, check_every=0, fault=None, use_gmp=None, batch=False, stage2="projective", inverse="host",
+              checkpoint=None, checkpoint_every=0, stop_after=0, save=None, group=0):
     """len(sigmas) == eng.lanes curves at once, curve l in lane l, through the engine calls of ONE run(); the check compares every lane in
     one launch sequence (Engine.equal_lanes) and a failure in any lane takes all lanes back.  -> one result per curve"""
     sigmas = list(sigmas)
     if len(sigmas) != getattr(eng, "lanes", 1) or not sigmas:
         raise ValueError("run_lanes needs one sigma per lane: %d given, the engine has %d lanes" % (len(sigmas), getattr(eng, "lanes", 1)))
-    return _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, True, batch, stage2, inverse)
+    return _run_curves(eng, p, b1, b2, sigmas, D, check_every, fault, use_gmp, True, batch, stage2, inverse,
+                       checkpoint, checkpoint_every, stop_after, save, group)
